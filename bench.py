@@ -22,6 +22,8 @@ What the one JSON line holds (rank 0):
                    profiles/r02_valu_roof.txt); the profile-derived fields are stamped with the hash
                    of the kernel source they were measured on and nulled when it differs
   cpu_baseline     the CPU oracle on this host: 1 thread and all usable cores, bounded samples
+  dump_outputs     (--dump-outputs DIR) where the last timed step's records went: DIR/<field>.npy, float64, a row per
+                   pair; the frames are rendered from fixed seeds, so two builds can be compared array for array
 
 N > 1: one process per GPU (torch.distributed, backend nccl == RCCL); no data-path collective.
   --shard sequences  (default) rank r tracks its own sequence; poses only gathered to rank 0.  weak.
@@ -95,9 +97,16 @@ def parse():
                          "barrier / all-reduce of the N > 1 path through it -- the rehearsal of the RCCL calls a one-GPU box allows")
     ap.add_argument("--frames-cache", default="", help="torch file to load/save the rendered S0 frames "
                     "(keeps profiler traces free of the renderer's torch kernels)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the records the LAST timed step returned (rank 0; one float64 array per "
+                         "svo_step_result field, a row per pair) as DIR/<field>.npy, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 and not args.config5:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.scaling_table:
+        ap.error("--dump-outputs cannot be combined with --scaling-table (every run would overwrite the same files)")
     if args.config5 and args.shard == "pairs":
         # the ranks of --config5 run DIFFERENT step counts; --shard pairs has a collective in every step
         ap.error("--config5 deals whole sequences to the ranks: it cannot be combined with --shard pairs")
@@ -561,6 +570,25 @@ def e2e_leg(args, n, frame_source, P1, width, png_level=3):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, recs, seed=20261015):
+    """`--dump-outputs`: the step records of the last timed step as DIR/<field>.npy, float64 (the int32 counts are exact in
+    it), one row per pair; `pair_index.npy` holds which pairs of the step they are.  Above 64 MB in all, a fixed seeded
+    sample of the pairs (sorted) is written instead."""
+    per_pair = 8 * (1 + sum(int(np.prod(recs.dtype[k].shape or (1,))) for k in recs.dtype.names))
+    idx = np.arange(len(recs))
+    if per_pair * len(recs) > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(len(recs), size=DUMP_LIMIT_BYTES // per_pair, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pair_index.npy"), idx.astype(np.float64))
+    for k in recs.dtype.names:
+        np.save(os.path.join(out_dir, k + ".npy"), recs[k][idx].astype(np.float64))
+    return {"dir": out_dir, "pairs": int(len(idx)), "pairs_of_step": int(len(recs)), "sampled": bool(len(idx) < len(recs)),
+            "arrays": ["pair_index"] + list(recs.dtype.names)}
+
+
 def usable_cores():
     try:
         n = len(os.sched_getaffinity(0))
@@ -889,6 +917,8 @@ def main():
                                         f"relative motions, prefix product on rank 0") if by_pairs else
                                        (f"sequence-per-GPU x{world}, RCCL gather of poses only" if world > 1 else "1 GPU"))},
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, res)
         if args.config5:
             busys = [p["busy_s"] for p in per_rank]
             out["config"]["config5"] = {"kitti_lengths": list(mg.KITTI_LENGTHS), "per_rank": per_rank,
