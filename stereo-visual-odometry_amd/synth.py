@@ -7,6 +7,11 @@ cx = 607.193, cy = 185.216, baseline 0.537 m) along a forward trajectory with a 
 yaw.  Left and right views are rendered from the two camera centres, so stereo disparity, temporal
 flow and the PnP geometry are all consistent with the known SE(3) motion.
 
+Two options, both off by default (the default rendering is unchanged byte for byte): `texture=` replaces the hashed
+value noise with a 2-D image in [0, 1] sampled bilinearly with wrap-around (natural content: flat and saturated areas,
+smooth gradients), and per-camera photometry (`gain`, `offset`, `gamma`, each a scalar or a (left, right) pair)
+applied to the intensity before the clamp to uint8 (exposure differences, and stereo without brightness constancy).
+
 Written with torch so the same code renders small CPU cases for tests and full-size frames on
 cuda for bench.py.  Only integer hashing and float32 arithmetic that is independent of reduction
 order is used, but CPU and GPU renderings are NOT required to match bit for bit: every consumer
@@ -36,6 +41,14 @@ def _hash01(u, v, k):
     return (h & 0xFFFF).to(torch.float32) / 65536.0
 
 
+def _per_cam(v):
+    """A scalar for both cameras, or a (left, right) pair -> (left, right) floats."""
+    if isinstance(v, (tuple, list)):
+        assert len(v) == 2, v
+        return float(v[0]), float(v[1])
+    return float(v), float(v)
+
+
 class StereoSequence:
     """Procedural corridor seen by a forward-moving rectified stereo rig."""
 
@@ -43,7 +56,7 @@ class StereoSequence:
                  fx=None, fy=None, cx=None, cy=None, baseline=KITTI_BASELINE,
                  step=1.0, yaw_amp=0.02, yaw_period=48.0, scales=(0.35, 1.4, 5.6),
                  weights=(0.55, 0.3, 0.15), supersample=2, half_width=7.0, cam_height=1.65,
-                 ceil_height=6.0, fog=90.0):
+                 ceil_height=6.0, fog=90.0, texture=None, texel=0.03, gain=1.0, offset=0.0, gamma=1.0):
         # default intrinsics: KITTI at full size, scaled with the image width otherwise
         s = width / 1241.0
         self.w, self.h = int(width), int(height)
@@ -60,6 +73,14 @@ class StereoSequence:
         self.step, self.yaw_amp, self.yaw_period = step, yaw_amp, yaw_period
         self.scales, self.weights, self.ss = scales, weights, int(supersample)
         self.half_width, self.cam_height, self.ceil_height, self.fog = half_width, cam_height, ceil_height, fog
+        self.tex = None
+        if texture is not None:
+            tex = torch.as_tensor(texture, dtype=torch.float32)
+            assert tex.dim() == 2 and tex.shape[0] >= 2 and tex.shape[1] >= 2, tex.shape
+            assert float(tex.min()) >= 0.0 and float(tex.max()) <= 1.0, "texture values must lie in [0, 1]"
+            self.tex = tex.to(self.device).contiguous()
+        self.texel = float(texel)                  # metres per texel of `texture` (3 cm: finer aliases into value noise far off)
+        self.gain, self.offset, self.gamma = _per_cam(gain), _per_cam(offset), _per_cam(gamma)
         self._poses = self._make_poses()
 
     # ---- trajectory ------------------------------------------------------------------------
@@ -92,12 +113,31 @@ class StereoSequence:
 
     # ---- rendering -------------------------------------------------------------------------
     def _texture(self, u, v, plane):
+        if self.tex is not None:
+            return self._sample(u, v, plane)
         val = torch.zeros_like(u)
         for k, (sc, wt) in enumerate(zip(self.scales, self.weights)):
             iu = torch.floor(u / sc).to(torch.int64)
             iv = torch.floor(v / sc).to(torch.int64)
             val = val + wt * _hash01(iu, iv, self.seed % 65521 + 131 * plane + 17 * k)
         return val
+
+    def _sample(self, u, v, plane):
+        """Bilinear lookup of `texture` with wrap-around at `texel` metres per texel; each plane starts at its own
+        offset into the image so that the four surfaces do not repeat each other."""
+        th, tw = self.tex.shape
+        fu = u / self.texel + (0.37 * plane) * tw
+        fv = v / self.texel + (0.61 * plane) * th
+        u0, v0 = torch.floor(fu), torch.floor(fv)
+        au, av = fu - u0, fv - v0
+        iu0 = torch.remainder(u0.to(torch.int64), tw)
+        iv0 = torch.remainder(v0.to(torch.int64), th)
+        iu1 = torch.remainder(iu0 + 1, tw)
+        iv1 = torch.remainder(iv0 + 1, th)
+        t = self.tex
+        top = t[iv0, iu0] * (1.0 - au) + t[iv0, iu1] * au
+        bot = t[iv1, iu0] * (1.0 - au) + t[iv1, iu1] * au
+        return top * (1.0 - av) + bot * av
 
     def _shade(self, ox, oy, oz, dx, dy, dz):
         """Nearest hit among ground (y = cam_height), ceiling (y = -ceil_height), walls
@@ -141,7 +181,16 @@ class StereoSequence:
                     dy = R[1, 0] * xcg + R[1, 1] * ycg + R[1, 2]
                     dz = R[2, 0] * xcg + R[2, 1] * ycg + R[2, 2]
                     acc += self._shade(float(o[0]), float(o[1]), float(o[2]), dx, dy, dz)
-            img = (acc / (ss * ss) * 255.0).clamp(0, 255).round().to(torch.uint8)
+            val = acc / (ss * ss)
+            # the photometry; each step is skipped at its identity so that the default bytes are unchanged
+            if self.gamma[cam] != 1.0:
+                val = val.clamp(min=0.0).pow(self.gamma[cam])
+            val = val * 255.0
+            if self.gain[cam] != 1.0:
+                val = val * self.gain[cam]
+            if self.offset[cam] != 0.0:
+                val = val + self.offset[cam]
+            img = val.clamp(0, 255).round().to(torch.uint8)
             out.append(img)
         return out[0], out[1]
 

@@ -169,6 +169,36 @@ def test_pnp_ransac_orb_mode_first_phase_is_the_whole_search(pkg, oracle, tc, n,
     c.close()
 
 
+# (band, n, n_out, seed, iterations): planted inlier ratios that put the oracle's adaptive stop in three bands
+# (cv::solvePnPRansac's 5-point model: 0.99 confidence needs ~57 hypotheses at 60 % inliers, ~450 at 40 %, ~760 at 36 %)
+_EARLY_STOP = [("a", 400, 120, 60, 500), ("a", 60, 24, 61, 500), ("a", 12, 3, 62, 500),
+               ("b", 200, 120, 61, 500), ("b", 400, 220, 60, 500), ("b", 300, 170, 62, 500),
+               ("c", 400, 256, 60, 1000), ("c", 300, 190, 61, 1000), ("c", 60, 38, 63, 1000)]
+_BANDS = {"a": (1, 63), "b": (64, 512), "c": (513, 999)}
+
+
+@pytest.mark.parametrize("mode", ["orb", "lk"])
+@pytest.mark.parametrize("band,n,n_out,seed,iterations", _EARLY_STOP)
+def test_pnp_ransac_early_stop_in_each_phase_band(pkg, oracle, tc, mode, band, n, n_out, seed, iterations):
+    """The adaptive stop firing before iterationsCount, with the first phase sized per track mode (pnp_first_cap: 512
+    hypotheses in ORB mode, 64 in LK mode): (a) stops inside 64 -- inside the first phase of both; (b) between 64 and
+    512 -- inside ORB mode's first phase (the case natural content reaches, where ORB's inlier ratio is higher than
+    the renderer's), across a phase boundary in LK mode; (c) past 512 of 1000 -- across a boundary in both.  The
+    oracle's count is asserted to land in the band; iterations, winner, mask and pose must equal the oracle's."""
+    kw = dict(track_mode=pkg.MODE_ORB, min_move2=0.0, max_move2=1e9) if mode == "orb" else {}
+    c = pkg.Context(416, 128, device=0, **kw)
+    X, x, r, t = _planted(n, seed, n_out, noise=0.02)
+    ref = oracle.pnp_ransac(X, x, K, iterations=iterations)
+    lo, hi = _BANDS[band]
+    assert ref["ok"] == 1 and lo <= ref["ransac_iters"] <= hi, (band, ref["ransac_iters"])
+    assert ref["ransac_iters"] < iterations                     # the stop fired
+    got = c.pnp_ransac(X, x, K, iterations=iterations)
+    _check_pnp(got, ref)
+    got_d = c.pnp_ransac(tc.from_numpy(X).cuda(), tc.from_numpy(x).cuda(), K, iterations=iterations)
+    _check_pnp(got_d, ref)
+    c.close()
+
+
 def _check_step(g, r, first=False):
     assert int(g["ok"]) == r["ok"] and int(g["fail_stage"]) == r["fail_stage"]
     assert int(g["n_cur_kps"]) == r["n_cur_kps"]
