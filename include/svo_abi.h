@@ -80,7 +80,17 @@ typedef struct {
     double  P1[12], P2[12];         /* projMatr1_/projMatr2_, src/parameter.cpp:44-45          */
     /* track_mode (config/default.yaml:75) and the ORBextractor constructor arguments (:89-93)   */
     int32_t track_mode;             /* SVO_MODE_LK ("LK_stereof2f_pnp") or SVO_MODE_ORB ("ORB_stereof2f_pnp");
-                                       in ORB mode min_move2 / max_move2 = minmove^2 / maxmove^2 (:87-88) */
+                                       in ORB mode min_move2 / max_move2 = minmove^2 / maxmove^2 (:87-88).
+                                       ORB mode refuses (SVO_ERR_ARG) a configuration with
+                                       - more than 1024 cells on a pyramid level: level 0 has ((w - 32) / 30) x
+                                         ((h - 32) / 30) cells, so about 1 MP at most (992x992 = 1024 cells is accepted,
+                                         1920x1080 = 2108 cells is refused);
+                                       - a level WITH cells whose keypoint area (w_l - 32) x (h_l - 32) rounds to more
+                                         than 64 : 1 (the quadtree's root strips); levels without cells are not checked;
+                                       - a level that rounds to 0 px (w or h / scale_factor^l < 0.5);
+                                       - max_keypoints > 16384.
+                                       A level whose keypoint area is more than twice as tall as wide yields no keypoints
+                                       (DistributeOctTree's nIni = 0: DESIGN.md section 2). */
     int32_t orb_nfeatures;          /* nFeatures 2000 */
     float   orb_scale_factor;       /* fScaleFactor 1.2 */
     int32_t orb_nlevels;            /* nLevels 8 */

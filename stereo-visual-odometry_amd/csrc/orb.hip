@@ -1618,7 +1618,8 @@ __global__ __launch_bounds__(256) void orb_blur_kernel(OrbGeom g, const uint8_t 
     const uint32_t k456 = (uint32_t)g.gk[4] | ((uint32_t)g.gk[5] << 8) | ((uint32_t)g.gk[6] << 16);
     // byte shuffles that put the reflected columns into an edge thread's 12-byte window (columns x0-4 .. x0+7 =
     // window bytes 0..11): every column a valid output needs (<= w+2, >= -3) reflects to a column inside the same
-    // window.  Window byte i takes byte sidx(i); two v_perm per dword (one over d0|d1, one bringing in d2).
+    // window (for w >= 4; a narrower level keeps in-window bytes that no keypoint reads: it has no cells).  Window byte i
+    // takes byte sidx(i); two v_perm per dword (one over d0|d1, one bringing in d2).
     uint32_t selA[3], selB[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -1649,7 +1650,10 @@ __global__ __launch_bounds__(256) void orb_blur_kernel(OrbGeom g, const uint8_t 
         }
     };
     auto load_row = [&](int yy, uint32_t (&d)[3]) {
-        yy = yy < 0 ? -yy : (yy >= h ? 2 * h - 2 - yy : yy);        // reflect-101 (one reflection: |offset| < 32 <= h)
+        // reflect-101 by one reflection: exact for the rows an output uses (|offset| <= 3) on levels of h >= 4.  The rows
+        // loaded past a band's end (offset < 32) and every row of a level under 4 px are clamped into the level instead:
+        // read, never used -- a level under 62 px has no cells, so no keypoint ever reads its blurred bytes.
+        yy = yy < 0 ? -yy : (yy >= h ? 2 * h - 2 - yy : yy);
         yy = min(max(yy, 0), h - 1);
         // (a thread at a row end reads a few bytes past it -- the slot's unused frame area, or an input row's padding --; the
         //  dword LEFT of a row's first one is never needed, the reflection replaces every byte of it: the row's first thread
@@ -2276,9 +2280,11 @@ int orb_alloc(svo_ctx *ctx)
     if (rc) { ctx->err = "ORB geometry: unsupported image size / level count"; return rc; }
     // DistributeOctTree starts from nIni = round(width / height) root strips of the level's keypoint area; both quadtree
     // kernels hold at most 64 of them.  A panorama beyond 64 : 1 is refused here instead of losing the strips silently.
+    // Only levels with a cell grid can hand the quadtree a key (no cells, no candidates: both kernels return before
+    // they compute nIni), so a strip-shaped level without cells -- 1041x128's level 7, 258 x 4 -- is no reason to refuse.
     for (int l = 0; l < g.nlevels; l++) {
         const int aw = g.w[l] - 32, ah = g.h[l] - 32;
-        if (aw > 0 && ah > 0 && (int)roundf((float)aw / (float)ah) > 64) {
+        if (g.ncell[l] > 0 && aw > 0 && ah > 0 && (int)roundf((float)aw / (float)ah) > 64) {
             ctx->err = "ORB mode: a pyramid level is wider than 64 : 1 (more than 64 quadtree root strips): unsupported";
             return SVO_ERR_ARG;
         }
