@@ -77,7 +77,11 @@ typedef struct {
     double  feature_match_error;    /* :66                                                     */
     double  inlier_rate;            /* :77                                                     */
     double  min_move2, max_move2;   /* squared translation gate; LK mode: 0.0005^2, 100 (:311) */
-    double  P1[12], P2[12];         /* projMatr1_/projMatr2_, src/parameter.cpp:44-45          */
+    double  P1[12], P2[12];         /* projMatr1_/projMatr2_, src/parameter.cpp:44-45, row-major 3x4.
+                                       The pose stage takes K from P1 alone: fx = P1[0], fy = P1[5], cx = P1[2],
+                                       cy = P1[6]; as in OpenCV 3 (K = P1(Rect(0, 0, 3, 3)), src/tracking.cpp:476-477)
+                                       it ignores P1's skew P1[1] and its 4th column.  Triangulation reads all 24
+                                       entries: P2 is fully general (K2 [R_rl | t_rl] of any rig).                */
     /* track_mode (config/default.yaml:75) and the ORBextractor constructor arguments (:89-93)   */
     int32_t track_mode;             /* SVO_MODE_LK ("LK_stereof2f_pnp") or SVO_MODE_ORB ("ORB_stereof2f_pnp");
                                        in ORB mode min_move2 / max_move2 = minmove^2 / maxmove^2 (:87-88).

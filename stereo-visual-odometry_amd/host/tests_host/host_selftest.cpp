@@ -170,6 +170,12 @@ int main(int argc, char **argv)
     printf("dataset_path=%s\n", p.dataset_path_.c_str());
     printf("fx=%.6f cx=%.6f cy=%.6f\n", p.fx1_, p.cx1_, p.cy1_);
     printf("P2_03=%.9f\n", p.projMatr2_[3]);
+    for (int m = 0; m < 2; m++) {
+        const double *P = m == 0 ? p.projMatr1_ : p.projMatr2_;
+        printf("P%d=", m + 1);
+        for (int i = 0; i < 12; i++) printf(i ? " %.17g" : "%.17g", P[i]);
+        printf("\n");
+    }
     printf("feature_match_error=%.3f num_features_tracking=%d inlier_rate=%.4f\n", p.feature_match_error_,
            p.num_features_tracking_, p.inlier_rate_);
     printf("iterationsCount=%d reprojectionError=%.3f confidence=%.3f\n", p.iterationsCount_,

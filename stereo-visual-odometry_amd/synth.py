@@ -12,6 +12,11 @@ value noise with a 2-D image in [0, 1] sampled bilinearly with wrap-around (natu
 smooth gradients), and per-camera photometry (`gain`, `offset`, `gamma`, each a scalar or a (left, right) pair)
 applied to the intensity before the clamp to uint8 (exposure differences, and stereo without brightness constancy).
 
+The right camera may also be a general one (`fx2`, `fy2`, `cx2`, `cy2`, `R_rl`, `t_rl`, all off by default): proj() then
+returns P1 = K1 [I|0] and P2 = K2 [R_rl | t_rl], the reference's construction (t_lr* / R_lr* row-major, src/parameter.cpp),
+and the right view is cast from C_r = -R_rl^T t_rl along R_wc R_rl^T K2^-1 [u v 1]^T.  The default rig keeps the float32
+rectified code path, so its bytes do not change either.
+
 Written with torch so the same code renders small CPU cases for tests and full-size frames on
 cuda for bench.py.  Only integer hashing and float32 arithmetic that is independent of reduction
 order is used, but CPU and GPU renderings are NOT required to match bit for bit: every consumer
@@ -56,7 +61,8 @@ class StereoSequence:
                  fx=None, fy=None, cx=None, cy=None, baseline=KITTI_BASELINE,
                  step=1.0, yaw_amp=0.02, yaw_period=48.0, scales=(0.35, 1.4, 5.6),
                  weights=(0.55, 0.3, 0.15), supersample=2, half_width=7.0, cam_height=1.65,
-                 ceil_height=6.0, fog=90.0, texture=None, texel=0.03, gain=1.0, offset=0.0, gamma=1.0):
+                 ceil_height=6.0, fog=90.0, texture=None, texel=0.03, gain=1.0, offset=0.0, gamma=1.0,
+                 fx2=None, fy2=None, cx2=None, cy2=None, R_rl=None, t_rl=None):
         # default intrinsics: KITTI at full size, scaled with the image width otherwise
         s = width / 1241.0
         self.w, self.h = int(width), int(height)
@@ -81,6 +87,18 @@ class StereoSequence:
             self.tex = tex.to(self.device).contiguous()
         self.texel = float(texel)                  # metres per texel of `texture` (3 cm: finer aliases into value noise far off)
         self.gain, self.offset, self.gamma = _per_cam(gain), _per_cam(offset), _per_cam(gamma)
+        # the right camera: K2 [R_rl | t_rl] (x_right = R_rl x_left + t_rl), by default the rectified K1 [I | (-b, 0, 0)]
+        self.fx2 = float(fx2) if fx2 is not None else float(self.fx)
+        self.fy2 = float(fy2) if fy2 is not None else float(self.fy)
+        self.cx2 = float(cx2) if cx2 is not None else float(self.cx)
+        self.cy2 = float(cy2) if cy2 is not None else float(self.cy)
+        self.R_rl = torch.eye(3, dtype=torch.float64) if R_rl is None else \
+            torch.as_tensor(R_rl, dtype=torch.float64).reshape(3, 3).clone()
+        self.t_rl = torch.tensor([-float(baseline), 0.0, 0.0], dtype=torch.float64) if t_rl is None else \
+            torch.as_tensor(t_rl, dtype=torch.float64).reshape(3).clone()
+        self.rectified = ((self.fx2, self.fy2, self.cx2, self.cy2) == (float(self.fx), float(self.fy), float(self.cx), float(self.cy))
+                          and torch.equal(self.R_rl, torch.eye(3, dtype=torch.float64))
+                          and self.t_rl.tolist() == [-float(baseline), 0.0, 0.0])
         self._poses = self._make_poses()
 
     # ---- trajectory ------------------------------------------------------------------------
@@ -109,7 +127,39 @@ class StereoSequence:
         return torch.linalg.inv(self._poses[t]) @ self._poses[t - 1]
 
     def proj(self):
-        return proj_matrices(self.fx, self.fy, self.cx, self.cy, self.baseline)
+        if self.rectified:
+            return proj_matrices(self.fx, self.fy, self.cx, self.cy, self.baseline)
+        K2 = self.K(1)
+        P1 = [self.fx, 0.0, self.cx, 0.0, 0.0, self.fy, self.cy, 0.0, 0.0, 0.0, 1.0, 0.0]
+        P2 = (K2 @ torch.cat([self.R_rl, self.t_rl[:, None]], 1)).reshape(12).tolist()
+        return P1, P2
+
+    def K(self, cam):
+        """3x3 float64 intrinsics of camera `cam` (0 left, 1 right)."""
+        fx, fy, cx, cy = (self.fx, self.fy, self.cx, self.cy) if cam == 0 else (self.fx2, self.fy2, self.cx2, self.cy2)
+        return torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=torch.float64)
+
+    def camera(self, t, cam):
+        """(centre (3,), M (3, 3)) in world coordinates, float64: the ray through pixel (u, v) of camera `cam` at frame t
+        is centre + s * M [u v 1]^T.  Right camera: centre p + R_wc C_r with C_r = -R_rl^T t_rl, M = R_wc R_rl^T K2^-1."""
+        T = self._poses[t]
+        R, p = T[:3, :3], T[:3, 3]
+        if cam == 0:
+            return p.clone(), R @ torch.linalg.inv(self.K(0))
+        return p + R @ (-self.R_rl.T @ self.t_rl), R @ self.R_rl.T @ torch.linalg.inv(self.K(1))
+
+    def depth(self, t, cam, u, v):
+        """Camera-frame depth Z of the nearest surface seen through pixel coordinates (u, v) (float64 tensors of one
+        shape, no supersampling) of camera `cam` at frame t, ray-cast in float64 through camera()."""
+        o, M = self.camera(t, cam)
+        u = torch.as_tensor(u, dtype=torch.float64)
+        v = torch.as_tensor(v, dtype=torch.float64)
+        d = [M[i, 0] * u + M[i, 1] * v + M[i, 2] for i in range(3)]
+        s = self._hit(float(o[0]), float(o[1]), float(o[2]), *d)
+        Rc = self._poses[t][:3, :3] if cam == 0 else self._poses[t][:3, :3] @ self.R_rl.T
+        # camera-frame direction = Rc^T d: its z component scales the hit distance to depth
+        dz = Rc[0, 2] * d[0] + Rc[1, 2] * d[1] + Rc[2, 2] * d[2]
+        return s * dz
 
     # ---- rendering -------------------------------------------------------------------------
     def _texture(self, u, v, plane):
@@ -139,15 +189,23 @@ class StereoSequence:
         bot = t[iv1, iu0] * (1.0 - au) + t[iv1, iu1] * au
         return top * (1.0 - av) + bot * av
 
-    def _shade(self, ox, oy, oz, dx, dy, dz):
-        """Nearest hit among ground (y = cam_height), ceiling (y = -ceil_height), walls
-        (x = +-half_width); returns intensity in [0,1]."""
+    def _planes(self, ox, oy, oz, dx, dy, dz):
+        """Ray parameters of the ground (y = cam_height), ceiling (y = -ceil_height) and walls (x = +-half_width)."""
         big = 1e9
         eps = 1e-9
         sg = torch.where(dy > eps, (self.cam_height - oy) / dy, torch.full_like(dy, big))
         sc = torch.where(dy < -eps, (-self.ceil_height - oy) / dy, torch.full_like(dy, big))
         sl = torch.where(dx < -eps, (-self.half_width - ox) / dx, torch.full_like(dx, big))
         sr = torch.where(dx > eps, (self.half_width - ox) / dx, torch.full_like(dx, big))
+        return sg, sc, sl, sr
+
+    def _hit(self, ox, oy, oz, dx, dy, dz):
+        sg, sc, sl, sr = self._planes(ox, oy, oz, dx, dy, dz)
+        return torch.minimum(torch.minimum(sg, sc), torch.minimum(sl, sr))
+
+    def _shade(self, ox, oy, oz, dx, dy, dz):
+        """Nearest hit among the four planes; returns intensity in [0,1]."""
+        sg, sc, sl, sr = self._planes(ox, oy, oz, dx, dy, dz)
         s = torch.minimum(torch.minimum(sg, sc), torch.minimum(sl, sr))
         X, Y, Z = ox + s * dx, oy + s * dy, oz + s * dz
         tex = torch.where(s == sg, self._texture(X, Z, 0),
@@ -169,18 +227,30 @@ class StereoSequence:
         us = torch.arange(self.w, device=dev, dtype=torch.float32)
         out = []
         for cam in range(2):
-            # camera centre in world: left at p, right at p + R * (baseline, 0, 0)
-            o = p + T[:3, 0] * (self.baseline * cam)
             acc = torch.zeros(self.h, self.w, device=dev, dtype=torch.float32)
-            for oy_ in offs:
-                for ox_ in offs:
-                    xc = ((us + ox_) - self.cx) / self.fx
-                    yc = ((vs + oy_) - self.cy) / self.fy
-                    xcg, ycg = torch.meshgrid(xc, yc, indexing="xy")
-                    dx = R[0, 0] * xcg + R[0, 1] * ycg + R[0, 2]
-                    dy = R[1, 0] * xcg + R[1, 1] * ycg + R[1, 2]
-                    dz = R[2, 0] * xcg + R[2, 1] * ycg + R[2, 2]
-                    acc += self._shade(float(o[0]), float(o[1]), float(o[2]), dx, dy, dz)
+            if cam == 0 or self.rectified:
+                # camera centre in world: left at p, right at p + R * (baseline, 0, 0)
+                o = p + T[:3, 0] * (self.baseline * cam)
+                for oy_ in offs:
+                    for ox_ in offs:
+                        xc = ((us + ox_) - self.cx) / self.fx
+                        yc = ((vs + oy_) - self.cy) / self.fy
+                        xcg, ycg = torch.meshgrid(xc, yc, indexing="xy")
+                        dx = R[0, 0] * xcg + R[0, 1] * ycg + R[0, 2]
+                        dy = R[1, 0] * xcg + R[1, 1] * ycg + R[1, 2]
+                        dz = R[2, 0] * xcg + R[2, 1] * ycg + R[2, 2]
+                        acc += self._shade(float(o[0]), float(o[1]), float(o[2]), dx, dy, dz)
+            else:
+                # a general right camera (camera()): float32 rays from its own centre through R_wc R_rl^T K2^-1
+                o, M = self.camera(t, 1)
+                M = M.to(torch.float32).to(dev)
+                for oy_ in offs:
+                    for ox_ in offs:
+                        ug, vg = torch.meshgrid(us + ox_, vs + oy_, indexing="xy")
+                        dx = M[0, 0] * ug + M[0, 1] * vg + M[0, 2]
+                        dy = M[1, 0] * ug + M[1, 1] * vg + M[1, 2]
+                        dz = M[2, 0] * ug + M[2, 1] * vg + M[2, 2]
+                        acc += self._shade(float(o[0]), float(o[1]), float(o[2]), dx, dy, dz)
             val = acc / (ss * ss)
             # the photometry; each step is skipped at its identity so that the default bytes are unchanged
             if self.gamma[cam] != 1.0:

@@ -23,22 +23,22 @@ camera_l.fx: {fx}
 camera_l.fy: {fy}
 camera_l.cx: {cx}
 camera_l.cy: {cy}
-camera_r.fx: {fx}
-camera_r.fy: {fy}
-camera_r.cx: {cx}
-camera_r.cy: {cy}
+camera_r.fx: {fx2}
+camera_r.fy: {fy2}
+camera_r.cx: {cx2}
+camera_r.cy: {cy2}
 t_lr0: {tlr0}
-t_lr1: 0.00
-t_lr2: 0.00
-R_lr0: 1.0
-R_lr1: 0.0
-R_lr2: 0.0
-R_lr3: 0.0
-R_lr4: 1.0
-R_lr5: 0.0
-R_lr6: 0.0
-R_lr7: 0.0
-R_lr8: 1.0
+t_lr1: {tlr1}
+t_lr2: {tlr2}
+R_lr0: {R0}
+R_lr1: {R1}
+R_lr2: {R2}
+R_lr3: {R3}
+R_lr4: {R4}
+R_lr5: {R5}
+R_lr6: {R6}
+R_lr7: {R7}
+R_lr8: {R8}
 num_features: 500
 num_features_init: 20
 init_landmarks: 5
@@ -72,9 +72,20 @@ def host_built(pkg):
     return HOST
 
 
-def _write_yaml(path, dataset, fx=718.856, fy=718.856, cx=607.193, cy=185.216, mode="LK_stereof2f_pnp", baseline=0.537):
+_R_IDENTITY = ("1.0", "0.0", "0.0", "0.0", "1.0", "0.0", "0.0", "0.0", "1.0")
+
+
+def _write_yaml(path, dataset, fx=718.856, fy=718.856, cx=607.193, cy=185.216, mode="LK_stereof2f_pnp", baseline=0.537,
+                camera_r=None, t_lr=None, R_lr=None):
+    """The reference's config layout.  camera_r = (fx, fy, cx, cy) of the right camera (default: the left one's),
+    t_lr = its three t_lr* (default (-baseline, 0, 0)), R_lr = the nine R_lr*, row-major (default I); given values are
+    written with repr(), so that the loader reads back the same doubles."""
+    fx2, fy2, cx2, cy2 = (fx, fy, cx, cy) if camera_r is None else tuple(repr(float(v)) for v in camera_r)
+    tl = (repr(-float(baseline)), "0.00", "0.00") if t_lr is None else tuple(repr(float(v)) for v in t_lr)
+    Rl = _R_IDENTITY if R_lr is None else tuple(repr(float(v)) for v in np.asarray(R_lr, np.float64).reshape(9))
     with open(path, "w", encoding="utf-8") as f:
-        f.write(YAML.format(dataset=dataset, fx=fx, fy=fy, cx=cx, cy=cy, mode=mode, tlr0=repr(-float(baseline))))
+        f.write(YAML.format(dataset=dataset, fx=fx, fy=fy, cx=cx, cy=cy, mode=mode, fx2=fx2, fy2=fy2, cx2=cx2, cy2=cy2,
+                            tlr0=tl[0], tlr1=tl[1], tlr2=tl[2], **{f"R{i}": Rl[i] for i in range(9)}))
 
 
 def _write_pgm(path, img):
@@ -117,6 +128,45 @@ def test_yaml_surface_and_image_readers(host_built, tmp_path):
           rgb[..., 2].astype(np.int64) * 1868 + 8192) >> 14).astype(np.uint8)
     assert f"image3 ok=1 rows=21 cols=34 hash={_hash(g)}" in out
     assert "image4 ok=0" in out
+
+
+def _selftest_P(out):
+    """The 12 entries of projMatr1_ and projMatr2_ as host_selftest prints them (%.17g: the exact doubles)."""
+    rows = dict(l.split("=", 1) for l in out.splitlines() if l.startswith(("P1=", "P2=")))
+    return [np.array([float(v) for v in rows[k].split()]).reshape(3, 4) for k in ("P1", "P2")]
+
+
+def test_general_rig_projection_matrices(host_built, tmp_path):
+    """lzb_vio::Parameter on a rig with distinct camera_r.*, a non-symmetric R_lr0..8 and all three t_lr*: projMatr1_ =
+    K1 [I|0] and projMatr2_ = K2 [R_rl | t_rl] (reference src/parameter.cpp, R_lr* row-major) against numpy.  Entries
+    that are a single product (or a copy) must be exact, sums of two products within 1 ulp (the summation order)."""
+    import _rigs
+    fx, fy, cx, cy = 718.856, 0.85 * 718.856, 631.5, 171.25                       # R1's left camera
+    cam_r = (_rigs.RIGS["R2"][k] for k in ("fx2", "fy2", "cx2", "cy2"))            # R2's right camera
+    cam_r = tuple(cam_r)
+    R, t = np.asarray(_rigs.RIGS["R3"]["R_rl"]), np.asarray(_rigs.R3_T)            # R3's rotation and translation
+    assert not np.allclose(R, R.T) and np.all(t != 0)
+    _write_yaml(tmp_path / "cfg.yaml", "/data/kitti/00", fx=repr(fx), fy=repr(fy), cx=repr(cx), cy=repr(cy),
+                camera_r=cam_r, t_lr=t, R_lr=R)
+    out = subprocess.check_output([os.path.join(host_built, "host_selftest"), str(tmp_path / "cfg.yaml")],
+                                  stderr=subprocess.DEVNULL).decode()
+    P1, P2 = _selftest_P(out)
+    K1 = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+    K2 = np.array([[cam_r[0], 0, cam_r[2]], [0, cam_r[1], cam_r[3]], [0, 0, 1.0]])
+    assert np.array_equal(P1, np.hstack([K1, np.zeros((3, 1))]))
+    want = K2 @ np.hstack([R, t[:, None]])
+    assert np.array_equal(P2[2], want[2])                                          # 1 * R[2, c], 1 * t[2]
+    assert np.all(np.abs(P2 - want) <= np.spacing(np.abs(want))), P2 - want
+    assert "P2_03=%.9f" % want[0, 3] in out
+    # the default rig: P2 = K1 [I | (-0.537, 0, 0)] exactly, and the historical P2_03 line
+    _write_yaml(tmp_path / "kitti.yaml", "/data/kitti/00")
+    out = subprocess.check_output([os.path.join(host_built, "host_selftest"), str(tmp_path / "kitti.yaml")],
+                                  stderr=subprocess.DEVNULL).decode()
+    P1, P2 = _selftest_P(out)
+    K = np.array([[718.856, 0, 607.193], [0, 718.856, 185.216], [0, 0, 1.0]])
+    assert np.array_equal(P1, np.hstack([K, np.zeros((3, 1))]))
+    assert np.array_equal(P2, np.hstack([K, [[718.856 * -0.537], [0], [0]]]))
+    assert "P2_03=%.9f" % (718.856 * -0.537) in out
 
 
 def test_png_reader_stream_shapes(host_built, tmp_path):
