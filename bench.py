@@ -9,21 +9,28 @@ consecutive frame pair of the reference is independent, so
 batches back to back; step k tracks chunk k of the rendered sequence (DISTINCT frames every step; at
 most --chunks chunks are rendered and cycled).
 
-What the one JSON line holds (rank 0):
+A plain run does only what the headline needs: render the frames, warm up, time the steps, write
+--dump-outputs, print the line.  What the one JSON line holds (rank 0):
   value            whole-job pairs/s with the frames RESIDENT IN HBM when the timed region starts (the
                    task contract's definition of `value`)
-  m1               SURVEY.md 8(d) M1: the same steps with the frames in PAGE-LOCKED HOST memory, the
-                   host-to-device copies INSIDE the timed region (double-buffered on a copy stream),
-                   from the first svo_track_* call to the last record on the host       (N = 1 only)
-  online           config #2 "single-stream": svo_add_frame, one pair per call, host frames (N = 1 only)
   roofline         lk_kernel: algorithmic HBM bytes per launch / launch time (HIP events on the launch
                    stream) against the 8 TB/s roof, the PMC-measured HBM traffic, and the VALU issue
                    roof the kernel actually sits under (measured instruction issue rates:
                    profiles/r02_valu_roof.txt); the profile-derived fields are stamped with the hash
                    of the kernel source they were measured on and nulled when it differs
-  cpu_baseline     the CPU oracle on this host: 1 thread and all usable cores, bounded samples
   dump_outputs     (--dump-outputs DIR) where the last timed step's records went: DIR/<field>.npy, float64, a row per
                    pair; the frames are rendered from fixed seeds, so two builds can be compared array for array
+--full adds, after the timed steps (N = 1 only; each has a --no-* / size option to leave it out):
+  self_check       the last timed step against the CPU oracle; a mismatch makes bench.py exit with 3
+  m1               SURVEY.md 8(d) M1: the same steps with the frames in PAGE-LOCKED HOST memory, the
+                   host-to-device copies INSIDE the timed region (double-buffered on a copy stream),
+                   from the first svo_track_* call to the last record on the host
+  online           config #2 "single-stream": svo_add_frame, one pair per call, host frames
+  stream, lk_accum_sse2 / _simd128 / _sse2_legacy, orb, hd, value_x86_order
+                   the pipelined stream, the LK tracker in x86 float orders, configs #3 and #4 -- each on a
+                   context of its own, timed and self-checked
+  cpu_baseline     the CPU oracle on this host: 1 thread and all usable cores, bounded samples
+  e2e, e2e_full    run_kitti_stereo from image files, process start included
 
 N > 1: one process per GPU (torch.distributed, backend nccl == RCCL); no data-path collective.
   --shard sequences  (default) rank r tracks its own sequence; poses only gathered to rank 0.  weak.
@@ -57,23 +64,27 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the oracle self-check, cpu_baseline, the m1 / online / "
+                         "stream legs, the lk_accum_* / orb / hd legs and the e2e legs (off: set up, warm up, time the steps, "
+                         "--dump-outputs, print the line)")
     ap.add_argument("--batch", type=int, default=256, help="stereo pairs per step (per GPU)")
     ap.add_argument("--chunks", type=int, default=4, help="distinct B-pair chunks of the sequence rendered (steps cycle through them)")
-    ap.add_argument("--cpu-pairs", type=int, default=100, help="pairs of the 1-thread cpu_baseline sample: BASELINE config #1 says "
+    ap.add_argument("--cpu-pairs", type=int, default=100, help="(--full) pairs of the 1-thread cpu_baseline sample: BASELINE config #1 says "
                     "\"first 100 pairs\" (0 = skip cpu_baseline)")
-    ap.add_argument("--e2e-frames", type=int, default=1025, help="frames of the end-to-end leg (run_kitti_stereo from PGM and PNG "
+    ap.add_argument("--e2e-frames", type=int, default=1025, help="(--full) frames of the end-to-end leg (run_kitti_stereo from PGM and PNG "
                     "files on disk, process start included; 0 = skip)")
-    ap.add_argument("--e2e-full-frames", type=int, default=4541, help="frames of the full-sequence end-to-end leg (KITTI-00's length; "
+    ap.add_argument("--e2e-full-frames", type=int, default=4541, help="(--full) frames of the full-sequence end-to-end leg (KITTI-00's length; "
                     "0 = skip; rendered, written to PGM and PNG and removed again: about a minute of set-up)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the m1 / online legs (value, roofline, cpu_baseline only)")
-    ap.add_argument("--no-self-check", action="store_true", help="skip the oracle comparison of the last step's pairs")
-    ap.add_argument("--self-check-pairs", type=int, default=256, help="pairs of the LAST timed step compared with the oracle in the main "
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the m1 / online / stream, lk_accum_* / orb / hd and e2e legs")
+    ap.add_argument("--no-self-check", action="store_true", help="(--full) skip the oracle comparison of the last step's pairs")
+    ap.add_argument("--self-check-pairs", type=int, default=256, help="(--full) pairs of the LAST timed step compared with the oracle in the main "
                     "measurement and the lk_accum_sse2 leg (256 = every pair of a default step; the orb and hd legs check an eighth, at least 32)")
     ap.add_argument("--self-check-sabotage", action="store_true",
-                    help="(test of the test) run the main self-check's oracle in the OTHER accumulation order: it must fail and "
+                    help="(--full; test of the test) run the main self-check's oracle in the OTHER accumulation order: it must fail and "
                          "bench.py must exit with 3")
-    ap.add_argument("--no-legs", action="store_true", help="skip the lk_accum_sse2 / orb (config #3) / hd (config #4) legs")
-    ap.add_argument("--hd-batch", type=int, default=128, help="pairs per step of the hd leg (1920x1080, exactly 2000 corners)")
+    ap.add_argument("--no-legs", action="store_true", help="(--full) skip the stream / lk_accum_* / orb (config #3) / hd (config #4) legs")
+    ap.add_argument("--hd-batch", type=int, default=128, help="(--full) pairs per step of the hd leg (1920x1080, exactly 2000 corners)")
     ap.add_argument("--no-timing-marks", action="store_true")
     ap.add_argument("--no-overlap", action="store_true", help="run the pose stage in stream order")
     ap.add_argument("--mode", choices=["lk", "orb"], default="lk",
@@ -105,6 +116,8 @@ def parse():
         ap.error("--gpus must be >= 1")
     if args.steps < 1 and not args.config5:
         ap.error("--steps must be >= 1")
+    if args.self_check_sabotage and not args.full:
+        ap.error("--self-check-sabotage needs --full (a plain run has no self-check)")
     if args.dump_outputs and args.scaling_table:
         ap.error("--dump-outputs cannot be combined with --scaling-table (every run would overwrite the same files)")
     if args.config5 and args.shard == "pairs":
@@ -906,7 +919,7 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic",
             "config": {"workload": wl + f", batched frame pairs ({B} per step, {NC} distinct chunks cycled), frames resident in HBM "
-                                      "for `value`; `m1` = host-resident frames, H2D included",
+                                      "for `value`; `m1` (--full) = host-resident frames, H2D included",
                        "lk_accum": (None if args.mode != "lk" else
                                     "exact (canonical C0: the five LK sums as exact integers, order-free; NOT an x86 OpenCV's float order -- "
                                     "see the lk_accum_* legs and value_x86_order)" if args.lk_accum == "exact" else
@@ -935,7 +948,7 @@ def main():
                                        profile=("lk_" + args.lk_accum if args.lk_accum in ("simd128", "sse2_legacy") else None))   # (counters exist for exact / sse2)
                            if stage_ms.get("lk") else
                            roofline_orb(stage_ms, B, W, H) if stage_ms.get("orb_cellfast") else None)
-        if world == 1 and not args.config5 and not args.no_self_check and steps > 0:
+        if args.full and world == 1 and not args.config5 and not args.no_self_check and steps > 0:
             O = entry.load_oracle()
             O.build()
             # the context still holds the last step's tracks and masks (B pairs, overlap on, chunks cycled)
@@ -944,8 +957,8 @@ def main():
                                                  else args.lk_accum == "exact"),
                                            n_check=args.self_check_pairs if args.mode == "lk" else max(32, args.self_check_pairs // 8))
 
-    # ---- secondary legs (N = 1): M1 with H2D inside the timed region, and the online path ---------
-    if world == 1 and not args.no_secondary and not args.config5:
+    # ---- secondary legs (--full, N = 1): M1 with H2D inside the timed region, and the online path ---------
+    if args.full and world == 1 and not args.no_secondary and not args.config5:
         hostL = [ctx.host_frames(B + 1, PITCH) for _ in range(NC)]
         hostR = [ctx.host_frames(B + 1, PITCH) for _ in range(NC)]
         for c in range(NC):
@@ -1100,8 +1113,8 @@ def main():
                 del Lh, Rh
 
     if rank == 0:
-        # ---- cpu_baseline: the oracle (CPU restatement of the reference path) on bounded samples
-        if args.cpu_pairs > 0 and world == 1 and args.mode == "lk":
+        # ---- cpu_baseline (--full): the oracle (CPU restatement of the reference path) on bounded samples
+        if args.full and args.cpu_pairs > 0 and world == 1 and args.mode == "lk":
             O = entry.load_oracle()
             O.build()
             prm = O.make_params(P1, P2)
@@ -1149,7 +1162,7 @@ def main():
                                                                           "sample": f"first {nn} pairs in sequence, OpenMP over the LK points, {cores} threads"}}}
             out["vs_cpu_baseline_1_thread"] = round(out["value"] / v1, 1)
             out["vs_cpu_baseline_all_cores"] = round(out["value"] / vp, 1)
-        elif args.cpu_pairs > 0 and world == 1 and args.mode == "orb":
+        elif args.full and args.cpu_pairs > 0 and world == 1 and args.mode == "orb":
             O = entry.load_oracle()
             O.build()
             n1 = min(args.cpu_pairs, B)
@@ -1159,8 +1172,8 @@ def main():
         else:
             out["cpu_baseline"] = None
 
-        # ---- e2e: the drop-in binary from image FILES (decode + H2D + tracking + pose file, process start included)
-        if world == 1 and args.e2e_frames >= 3 and not args.config5 and not args.no_secondary:
+        # ---- e2e (--full): the drop-in binary from image FILES (decode + H2D + tracking + pose file, process start included)
+        if args.full and world == 1 and args.e2e_frames >= 3 and not args.config5 and not args.no_secondary:
             n_e2e = min(args.e2e_frames, L.shape[0])
             out["e2e"] = e2e_leg(args, n_e2e, lambda t0, t1: (L[t0:t1, :, :W].cpu().numpy(), R[t0:t1, :, :W].cpu().numpy()), P1, W)
             if args.e2e_full_frames > n_e2e:

@@ -1,6 +1,7 @@
-"""bench.py --dump-outputs and --steps.  CPU: the argument checks and the dump's layout and 64 MB bound on stand-in
-records.  GPU (-m gpu): the timed path's last step is dumped, --steps is the number of timed steps, and two runs with
-the same arguments write the same arrays."""
+"""bench.py --dump-outputs, --steps and --full.  CPU: the argument checks and the dump's layout and 64 MB bound on stand-in
+records.  GPU (-m gpu): the timed path's last step is dumped, --steps is the number of timed steps, two runs with
+the same arguments write the same arrays, and a plain run carries none of --full's extras but dumps what a self-checked
+--full run dumps."""
 import json
 import os
 import subprocess
@@ -31,6 +32,8 @@ def test_steps_below_one_and_dump_with_scaling_table_are_refused():
     assert r.returncode == 2 and "--steps must be >= 1" in r.stderr.decode()
     r = _bench("--gpus", "2", "--scaling-table", "--dump-outputs", "x", timeout=120)
     assert r.returncode == 2 and "--dump-outputs" in r.stderr.decode()
+    r = _bench("--self-check-sabotage", timeout=120)
+    assert r.returncode == 2 and "--self-check-sabotage needs --full" in r.stderr.decode()
 
 
 def test_dump_writes_every_field_as_float64(pkg, tmp_path):
@@ -61,7 +64,7 @@ def test_dump_above_the_limit_is_a_fixed_sample(pkg, tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_dump_outputs_of_the_timed_path_repeat_exactly(tmp_path):
-    flags = ["--steps", "3", "--warmup", "1", "--batch", "12", "--chunks", "2", "--cpu-pairs", "0", "--e2e-frames", "0",
+    flags = ["--full", "--steps", "3", "--warmup", "1", "--batch", "12", "--chunks", "2", "--cpu-pairs", "0", "--e2e-frames", "0",
              "--no-legs", "--no-secondary"]
     outs = []
     for name in ("a", "b"):
@@ -76,3 +79,25 @@ def test_dump_outputs_of_the_timed_path_repeat_exactly(tmp_path):
     assert np.load(tmp_path / "a" / "pose.npy").shape == (12, 16)
     for f in sorted(os.listdir(tmp_path / "a")):
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_a_full_run_dumps(tmp_path):
+    common = ["--steps", "3", "--warmup", "1", "--batch", "12", "--chunks", "2"]
+    r = _bench(*common, "--dump-outputs", str(tmp_path / "plain"))
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    plain = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    r = _bench(*common, "--full", "--cpu-pairs", "0", "--e2e-frames", "0", "--no-legs", "--no-secondary",
+               "--dump-outputs", str(tmp_path / "full"))
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    full = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    assert full["self_check"]["ok"] and full["self_check"]["pairs"] == 12
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["frac"] > 0
+    assert plain["cpu_baseline"] is None
+    for k in ("self_check", "m1", "online", "stream", "lk_accum_sse2", "orb", "hd", "value_x86_order", "e2e", "e2e_full"):
+        assert k not in plain, k
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(os.listdir(tmp_path / "full"))
+    for f in sorted(os.listdir(tmp_path / "plain")):
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f

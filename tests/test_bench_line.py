@@ -1,4 +1,4 @@
-"""bench.py's one-GPU line (-m gpu): the legs the driver's default run carries (lk_accum_sse2 / _simd128 / _sse2_legacy, orb = BASELINE config #3,
+"""bench.py --full's one-GPU line (-m gpu): the legs a --full run carries (lk_accum_sse2 / _simd128 / _sse2_legacy, orb = BASELINE config #3,
 hd = config #4 on exactly 2000 corners) and the oracle self-check, on a small batch; and the self-check's teeth: with the
 oracle deliberately run in the other accumulation order bench.py must exit with 3."""
 import json
@@ -19,8 +19,8 @@ def _bench(*flags, timeout=900):
                           timeout=timeout, env=env)
 
 
-def test_default_line_carries_the_legs_and_a_green_self_check():
-    r = _bench("--steps", "3", "--warmup", "1", "--batch", "12", "--chunks", "2", "--cpu-pairs", "12", "--e2e-frames", "0",
+def test_full_line_carries_the_legs_and_a_green_self_check():
+    r = _bench("--full", "--steps", "3", "--warmup", "1", "--batch", "12", "--chunks", "2", "--cpu-pairs", "12", "--e2e-frames", "0",
                "--hd-batch", "3")
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
@@ -48,7 +48,7 @@ def test_default_line_carries_the_legs_and_a_green_self_check():
 
 
 def test_self_check_mismatch_exits_non_zero():
-    r = _bench("--steps", "1", "--warmup", "0", "--batch", "10", "--chunks", "1", "--cpu-pairs", "0", "--e2e-frames", "0",
+    r = _bench("--full", "--steps", "1", "--warmup", "0", "--batch", "10", "--chunks", "1", "--cpu-pairs", "0", "--e2e-frames", "0",
                "--no-legs", "--no-secondary", "--self-check-sabotage")
     assert r.returncode == 3, (r.returncode, r.stderr.decode()[-2000:])
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])

@@ -288,11 +288,12 @@ def test_bench_rccl_calls_on_a_one_rank_communicator(extra):
     """The `nccl` (= RCCL) branch on the one GPU a test box has: `--dist-single` initialises a process group of ONE
     rank and every collective of the N > 1 path (barrier, gather of poses / relative motions, the ragged gather of
     config #5's full pose lists, the max all-reduce) goes through RCCL on device tensors.  Not a scaling measurement --
-    it is the only execution of that branch this pipeline allows, and it catches API misuse the gloo runs cannot."""
+    it is the only execution of that branch this pipeline allows, and it catches API misuse the gloo runs cannot.
+    --full: outside config #5 the last step is also checked against the oracle."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    r = _bench("--gpus", "1", "--dist-single", "--warmup", "1", "--batch", "64", "--cpu-pairs", "0", "--e2e-frames", "0",
+    r = _bench("--gpus", "1", "--dist-single", "--full", "--warmup", "1", "--batch", "64", "--cpu-pairs", "0", "--e2e-frames", "0",
                "--no-secondary", *extra, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])

@@ -2,7 +2,7 @@
 # ORB-mode bench under different environment settings in one session: ORB_ENV_AB="NAME=VALUE[,NAME=VALUE] ..." (a "-" = none)
 mkdir -p gpurun_out
 CACHE=/tmp/s0_frames_c2.pt
-BARGS="--mode orb --cpu-pairs 0 --no-secondary --no-legs --self-check-pairs 16 --chunks 2 --frames-cache $CACHE"
+BARGS="--full --mode orb --cpu-pairs 0 --no-secondary --no-legs --self-check-pairs 16 --chunks 2 --frames-cache $CACHE"
 python bench.py --steps 2 --warmup 1 $BARGS > gpurun_out/bench_cache.log 2>&1; echo "cache exit=$?"
 i=0
 for V in $ORB_ENV_AB; do
