@@ -323,6 +323,53 @@ int svo_get_last_tracks(svo_ctx *ctx, svo_pt2f *t1_left, svo_pt2f *t1_right, svo
 int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
                          svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out);
 
+/* ---- stream sets: many independent LIVE stereo streams through one launch set (additive; detected by symbol, the ABI
+ * version stays 9) ---------------------------------------------------------------------------------------------------
+ * A live camera has no future frames, so svo_add_frame tracks one pair per call and leaves the chip almost empty.  Every
+ * pair is independent of every other ACROSS cameras as it is along time: a stream set keeps,
+ * for each of n_streams streams, what one lzb_vio::Tracking keeps between AddFrame calls -- last_frame_'s features
+ * (LK mode: both pyramids, the FAST corners; ORB mode: both images' keypoints and descriptors), frame_pose_ and the
+ * INITING / TRACKING status (reference src/tracking.h:105-117) -- in device memory, and one svo_streams_step does for m
+ * of them what m Tracking::AddFrame calls do (src/tracking.cpp:49-77), as ONE set of launches.  All streams share the
+ * context's frame size, rig, mode and every other svo_config field.
+ *   svo_streams_create : allocates the set (once per context; SVO_ERR_ARG on a second call or n_streams < 1).  A context
+ *       that never calls it pays nothing.
+ *   svo_streams_count  : *n_streams = streams of the set, 0 before svo_streams_create.
+ *   svo_streams_step   : frame i (at base + i * frame_stride, rows `pitch` apart, where `mem` says) is the next stereo
+ *       frame of stream stream_ids[i]; results[i] (where `results_mem` says; NULL with SVO_MEM_DEVICE: the records stay
+ *       in the context) is its step record.  The ids are distinct, in any order, any subset: 1 <= m <=
+ *       (max_batch + 1) / 2 -- the step uses 2 m of the context's max_batch + 1 working frame slots, so a caller that
+ *       advances 128 streams a call creates the context with max_batch = 256.  A stream's first frame since its reset
+ *       gives the StereoInit_f2f record (:78-92): ok = 1, n_prev_kps = 0, R = T_rel_inv = I, pose = the stream's pose.
+ *       Later frames track against the stream's previous frame, which the new one replaces on success AND on every
+ *       SVO_FAIL_* outcome (last_frame_ = current_frame_, :59-68); a failed step leaves the stream's pose unchanged.
+ *       Returns SVO_OK or a hard error < 0; soft failures are in results[i].ok / .fail_stage only.  Each record is what
+ *       svo_add_frame returns for the same frames on a context of its own, bit for bit.
+ *       SVO_MEM_HOST frames are copied by the call (one frame: the staging of svo_add_frame; more: frame buffer 0 of
+ *       svo_upload_frames, whose previous contents are lost) and are free again when it returns.  SVO_MEM_HOST results: the
+ *       call returns when they are there.  SVO_MEM_DEVICE results: in stream order on the context's stream, no host
+ *       synchronisation inside the call; the poses live on the device, so a queued step depends on no host memory.
+ *       Overlap mode, the async queue and SVO_CONTINUE_* do not apply to stream steps.
+ *   svo_streams_reset  : that stream (-1: every stream) back to INITING, pose = identity (svo_reset per
+ *       stream); in stream order after the steps queued so far.
+ *   svo_streams_get_pose / svo_streams_set_pose : the stream's frame_pose_ (src/tracking.h:117); set seeds the chain as
+ *       pose0 seeds svo_track_batch.  HOST pointers; get waits for the steps queued so far.
+ *   svo_streams_get_tracks : svo_get_batch_tracks for item `item` of the most recent step (n = 0 for an init item).
+ * The set is separate memory: svo_add_frame, svo_track_batch, the stage API ... keep working on the same context and do not
+ * disturb the streams.  In the other direction a step is one more writer of the working frame slots, exactly like
+ * svo_track_batch: it waits for a pending overlap-mode pose stage, ends a carried frame (SVO_CONTINUE_CARRY_FRAME), and
+ * svo_add_frame's two-frame ring does not survive it -- call svo_reset before svo_add_frame is used again. */
+int svo_streams_create(svo_ctx *ctx, int n_streams);
+int svo_streams_count(const svo_ctx *ctx, int *n_streams);
+int svo_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *left_frames,
+                     const uint8_t *right_frames, int pitch, int64_t frame_stride, int mem,
+                     svo_step_result *results, int results_mem);
+int svo_streams_reset(svo_ctx *ctx, int stream_id);
+int svo_streams_get_pose(svo_ctx *ctx, int stream_id, double pose[16]);
+int svo_streams_set_pose(svo_ctx *ctx, int stream_id, const double pose[16]);
+int svo_streams_get_tracks(svo_ctx *ctx, int item, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
+                           svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

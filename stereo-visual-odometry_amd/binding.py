@@ -109,6 +109,15 @@ def load_library():
     lib.svo_collect_results.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.svo_results_ready.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     lib.svo_set_pose.argtypes = [C.c_void_p, C.c_void_p]
+    # stream sets (additive entry points: a library without them is a stale build, and that is an error, not a fallback)
+    lib.svo_streams_create.argtypes = [C.c_void_p, C.c_int]
+    lib.svo_streams_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.svo_streams_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
+                                     C.c_void_p, C.c_int]
+    lib.svo_streams_reset.argtypes = [C.c_void_p, C.c_int]
+    lib.svo_streams_get_pose.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.svo_streams_set_pose.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.svo_streams_get_tracks.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_int)]
     _LIB = lib
     return lib
 
@@ -565,4 +574,76 @@ class Context:
         n = C.c_int(0)
         self._check(self.lib.svo_get_last_tracks(self.h, *[C.c_void_p(p.ctypes.data) for p in pts], C.c_void_p(inl.ctypes.data),
                                                  cap, C.byref(n)))
+        return [p[:n.value].copy() for p in pts] + [inl[:n.value].copy()]
+
+    # ---- stream sets: many independent live streams through one launch set (svo_streams_*) ------
+    def streams_create(self, n_streams):
+        self._check(self.lib.svo_streams_create(self.h, int(n_streams)))
+
+    def streams_count(self):
+        n = C.c_int(0)
+        self._check(self.lib.svo_streams_count(self.h, C.byref(n)))
+        return n.value
+
+    def _frame_stack(self, frames):
+        """(array, pointer, pitch, frame stride, memory kind) of m equal-size u8 frames: a stacked (m, h, w) numpy array or
+        torch tensor (rows may be padded), or a list of (h, w) images, which is stacked."""
+        if isinstance(frames, (list, tuple)):
+            if isinstance(frames[0], np.ndarray):
+                frames = np.stack([np.ascontiguousarray(f, np.uint8) for f in frames])
+            else:
+                import torch
+                frames = torch.stack(list(frames))
+        assert tuple(frames.shape[1:]) == (self.height, self.width), (tuple(frames.shape), self.height, self.width)
+        if isinstance(frames, np.ndarray):
+            assert frames.dtype == np.uint8 and frames.strides[2] == 1
+            return frames, C.c_void_p(frames.ctypes.data), int(frames.strides[1]), int(frames.strides[0]), MEM_HOST
+        assert frames.element_size() == 1 and frames.stride(2) == 1
+        return (frames, C.c_void_p(frames.data_ptr()), int(frames.stride(1)), int(frames.stride(0)),
+                MEM_DEVICE if frames.is_cuda else MEM_HOST)
+
+    def streams_step(self, ids, lefts, rights, results=None):
+        """Advances the streams `ids` (distinct, any order, any subset) by one stereo frame each: lefts[i] / rights[i] is the
+        next frame of stream ids[i].  Frames: numpy (host) or torch cuda, stacked (m, h, w) or a list of (h, w) images.
+        Returns the m step records in the caller's order as a numpy structured array, or -- results = a cuda uint8 / record
+        tensor of m * STEP_DTYPE.itemsize bytes -- fills that tensor in stream order without a host synchronisation."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        m = int(ids.shape[0])
+        fl, pl, pitch, fstride, mem = self._frame_stack(lefts) if m else (None, None, self.width, 0, MEM_HOST)
+        fr, pr, pitch_r, fstride_r, mem_r = self._frame_stack(rights) if m else (None, None, self.width, 0, MEM_HOST)
+        assert (pitch, fstride, mem) == (pitch_r, fstride_r, mem_r)
+        assert m == 0 or (fl.shape[0] == m and fr.shape[0] == m)
+        if results is None:
+            out = np.zeros(m, dtype=STEP_DTYPE)
+            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
+        else:
+            out = results
+            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
+        ordered = False
+        if mem == MEM_DEVICE:
+            ordered = self._order_in(fl)     # the frames (and a device result buffer) may still be in flight on torch's stream
+        self._check(self.lib.svo_streams_step(self.h, C.c_void_p(ids.ctypes.data), m, pl, pr, pitch, fstride, mem, rp, rmem))
+        if results is not None and ordered:
+            self._order_out(fl)              # frames and records: before whatever torch's stream does next
+        return out
+
+    def streams_reset(self, id=-1):
+        self._check(self.lib.svo_streams_reset(self.h, int(id)))
+
+    def streams_get_pose(self, id):
+        pose = np.zeros(16)
+        self._check(self.lib.svo_streams_get_pose(self.h, int(id), C.c_void_p(pose.ctypes.data)))
+        return pose.reshape(4, 4)
+
+    def streams_set_pose(self, id, pose):
+        pose = np.ascontiguousarray(pose, np.float64).reshape(16)
+        self._check(self.lib.svo_streams_set_pose(self.h, int(id), C.c_void_p(pose.ctypes.data)))
+
+    def streams_tracks(self, item, cap=65536):
+        """(t1_left, t1_right, t2_right, t2_left, inlier) of item `item` of the last streams_step (empty for an init item)."""
+        pts = [np.zeros((cap, 2), np.float32) for _ in range(4)]
+        inl = np.zeros(cap, np.uint8)
+        n = C.c_int(0)
+        self._check(self.lib.svo_streams_get_tracks(self.h, int(item), *[C.c_void_p(p.ctypes.data) for p in pts],
+                                                    C.c_void_p(inl.ctypes.data), cap, C.byref(n)))
         return [p[:n.value].copy() for p in pts] + [inl[:n.value].copy()]

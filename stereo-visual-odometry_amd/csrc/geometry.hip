@@ -932,6 +932,59 @@ __global__ __launch_bounds__(kFinThreads) void finalize_chain_kernel(FinalizeArg
     }
 }
 
+// The pose stage of a stream-set step (svo_streams_step): the pairs of one launch belong to DIFFERENT streams, so nothing is
+// chained along the batch.  finalize_pair decides the gates exactly as for a batch; then pose_s = pose_s * T_rel_inv per stream,
+// read from and written to the stream store on the device (a queued step depends on no host memory), 16 lanes per stream, four
+// streams per wave, one wave per workgroup; the association order is the chain's (k ascending, separate multiply and add).
+// A stream whose first frame this is gets the StereoInit_f2f record (src/tracking.cpp:78-92) instead: detect only, ok = 1.
+constexpr int kFinStreams = 4;                          // streams per workgroup
+__global__ __launch_bounds__(64) void finalize_streams_kernel(FinalizeArgs a, int item0, StreamTable tab, double *pose_store)
+{
+    const int g = threadIdx.x >> 4, e = threadIdx.x & 15, i = e >> 2, j = e & 3;
+    const int t = blockIdx.x * kFinStreams + g;         // entry of this launch's table
+    const int p = item0 + t;                            // item of the step
+    const bool live = t < kStreamChunk && p < a.n_pairs;
+    const bool init = live && tab.init[t] != 0;
+    if (live && e == 0) {
+        if (!init) finalize_pair(a, p);
+        else {
+            svo_step_result r;
+            r.ok = 1; r.fail_stage = 0;
+            r.n_prev_kps = 0; r.n_cur_kps = a.n_cur[p]; r.n_tracked = 0; r.n_inliers = 0; r.ransac_iters = 0; r.lm_iters = 0;
+            for (int k = 0; k < 3; k++) { r.rvec[k] = 0; r.tvec[k] = 0; }
+            for (int k = 0; k < 9; k++) r.R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+            for (int k = 0; k < 16; k++) { r.T_rel_inv[k] = (k % 5 == 0) ? 1.0 : 0.0; r.pose[k] = 0; }
+            a.res[p] = r;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();                                    // the record lane 0 wrote is visible to the 16 lanes of its stream
+    double out = 0;
+    if (live) {
+        const svo_step_result *r = a.res + p;
+        const double *P = pose_store + (size_t)tab.id[t] * 16;
+        out = P[e];
+        if (!init && r->ok) {
+            const double p0 = P[i * 4 + 0], p1 = P[i * 4 + 1], p2 = P[i * 4 + 2], p3 = P[i * 4 + 3];
+            const double *T = r->T_rel_inv + j;
+            double s = 0;
+            s += p0 * T[0]; s += p1 * T[4]; s += p2 * T[8]; s += p3 * T[12];
+            out = s;
+        }
+    }
+    __syncthreads();                                    // every lane has read the old pose before any writes the new one
+    if (live) {
+        a.res[p].pose[e] = out;
+        pose_store[(size_t)tab.id[t] * 16 + e] = out;
+    }
+}
+
+__global__ __launch_bounds__(256) void streams_set_pose_kernel(double *pose_store, int n, Pose16 pose)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n * 16) pose_store[k] = pose.m[k & 15];
+}
+
 // The same product for relative motions gathered from independently tracked chunks (other
 // launches, contexts or GPUs): lanes (i, j) of one wave hold P[i][j]; row elements travel by quad
 // broadcast, the T matrices are staged through LDS 64 pairs at a time.  Same association order
@@ -1155,6 +1208,28 @@ void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const i
     Pose16 p0;
     for (int i = 0; i < 16; i++) p0.m[i] = pose0_host ? pose0_host[i] : ((i % 5 == 0) ? 1.0 : 0.0);
     hipLaunchKernelGGL(finalize_chain_kernel, dim3(1), dim3(kFinThreads), 0, st, f, p0, ctx->seed_dev);
+}
+
+void launch_finalize_streams(svo_ctx *ctx, int item0, int n_items, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
+                             const StreamTable &tab, hipStream_t st)
+{
+    FinalizeArgs f{};
+    f.pnp = (const PnpRecord *)ctx->pnp_ws; f.n_prev = n_prev; f.n_cur = n_cur; f.n_tracked = ctx->m_out; f.ovf = ovf;
+    f.cap = ctx->cfg.max_keypoints;
+    f.n_pairs = item0 + n_items < n_pairs ? item0 + n_items : n_pairs;
+    f.mode = ctx->cfg.track_mode; f.num_features_tracking = ctx->cfg.num_features_tracking;
+    f.inlier_rate = ctx->cfg.inlier_rate; f.min_move2 = ctx->cfg.min_move2; f.max_move2 = ctx->cfg.max_move2;
+    f.res = ctx->d_results;
+    hipLaunchKernelGGL(finalize_streams_kernel, dim3((n_items + kFinStreams - 1) / kFinStreams), dim3(64), 0, st, f, item0, tab,
+                       ctx->streams.pose);
+}
+
+void launch_streams_set_pose(svo_ctx *ctx, int id0, int n, const double *pose_host)
+{
+    Pose16 p;
+    for (int i = 0; i < 16; i++) p.m[i] = pose_host ? pose_host[i] : ((i % 5 == 0) ? 1.0 : 0.0);
+    hipLaunchKernelGGL(streams_set_pose_kernel, dim3((n * 16 + 255) / 256), dim3(256), 0, ctx->stream,
+                       ctx->streams.pose + (size_t)id0 * 16, n, p);
 }
 
 // ---- stage API ------------------------------------------------------------------------------

@@ -67,7 +67,10 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
     return SVO_OK;
 }
 
-static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first = false);
+// A stream-set step: item i of the launch set works for stream ids[i]; init[i]: that stream has no previous frame.
+struct StreamStep { const int32_t *ids; const uint8_t *init; };
+static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first = false,
+                    const StreamStep *ss = nullptr);
 
 // A micro-batch of a stream starts with the frame the previous one ended with: instead of building that frame's
 // pyramids and detecting its features again, what the pair needs of it is carried from frame slot `last` to slot 0
@@ -107,12 +110,88 @@ static void carry_last_frame(svo_ctx *ctx, int last)
     hipLaunchKernelGGL(carry_frame_kernel, dim3(64, c.n), dim3(256), 0, ctx->stream, c);
 }
 
+// The same copy for the streams of a stream set, table-driven: ONE launch moves every carried segment of up to kStreamChunk
+// streams between the stream store (segment k of stream s at store[k] + s * bytes[k]) and the working frame slots (segment k of
+// frame slot f at work[k] + f * bytes[k]).  Item t of the launch is stream tab.id[t] <-> frame slot slot0 + t.
+// Gather (to_store = 0): store -> slot; a stream WITHOUT a previous frame (tab.init[t]) leaves a hole -- its count segments are
+// zeroed (no keypoints: the pair tracks nothing and the pose stage writes the init record), the others are not touched.
+// Scatter (to_store = 1): slot -> store, every item.  16 bytes per lane where both ends are 16-byte aligned, else 4, else 1.
+struct StreamCopyArgs {
+    uint8_t *store[4], *work[4];
+    size_t bytes[4];
+    int is_count[4];
+    int n_seg, n_items, slot0, to_store;
+    StreamTable tab;
+};
+__global__ __launch_bounds__(256) void stream_copy_kernel(StreamCopyArgs a)
+{
+    const int seg = blockIdx.y, t = blockIdx.z;
+    if (seg >= a.n_seg || t >= a.n_items || t >= kStreamChunk) return;
+    const size_t bytes = a.bytes[seg];
+    uint8_t *st = a.store[seg] + (size_t)a.tab.id[t] * bytes;
+    uint8_t *wk = a.work[seg] + (size_t)(a.slot0 + t) * bytes;
+    const bool hole = !a.to_store && a.tab.init[t];
+    if (hole && !a.is_count[seg]) return;
+    uint8_t *d = a.to_store ? st : wk;
+    const uint8_t *s = a.to_store ? wk : st;
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthr = (size_t)gridDim.x * 256;
+    if (hole) {
+        for (size_t i = tid; i < bytes; i += nthr) d[i] = 0;
+        return;
+    }
+    const uintptr_t al = (uintptr_t)d | (uintptr_t)s;
+    size_t done = 0;
+    if ((al & 15) == 0) {
+        const size_t n16 = bytes / 16;
+        for (size_t i = tid; i < n16; i += nthr) ((uint4 *)d)[i] = ((const uint4 *)s)[i];
+        done = n16 * 16;
+    } else if ((al & 3) == 0) {
+        const size_t n4 = bytes / 4;
+        for (size_t i = tid; i < n4; i += nthr) ((uint32_t *)d)[i] = ((const uint32_t *)s)[i];
+        done = n4 * 4;
+    }
+    for (size_t i = done + tid; i < bytes; i += nthr) d[i] = s[i];
+}
+
+// The working arrays behind the segments of the stream store, in the store's order (streams_create sizes the store by them).
+static int stream_segments(svo_ctx *ctx, uint8_t *work[4], size_t bytes[4], int is_count[4])
+{
+    const size_t cap = (size_t)ctx->cfg.max_keypoints;
+    if (ctx->cfg.track_mode == SVO_MODE_ORB) {
+        const size_t kcap = (size_t)ctx->orb_kp_cap;
+        work[0] = (uint8_t *)ctx->orb_kps;      bytes[0] = 2 * kcap * sizeof(svo_keypoint); is_count[0] = 0;
+        work[1] = ctx->orb_desc;                bytes[1] = 2 * kcap * 32;                   is_count[1] = 0;
+        work[2] = (uint8_t *)ctx->orb_n;        bytes[2] = 2 * sizeof(int);                 is_count[2] = 1;
+        work[3] = (uint8_t *)ctx->orb_overflow; bytes[3] = 2 * sizeof(int);                 is_count[3] = 1;
+    } else {
+        work[0] = ctx->bslots;                  bytes[0] = (size_t)2 * ctx->geom.slot_bytes; is_count[0] = 0;
+        work[1] = (uint8_t *)ctx->kp_xy;        bytes[1] = cap * sizeof(float2);            is_count[1] = 0;
+        work[2] = (uint8_t *)ctx->kp_resp;      bytes[2] = cap * sizeof(float);             is_count[2] = 0;
+        work[3] = (uint8_t *)ctx->kp_n;         bytes[3] = sizeof(int);                     is_count[3] = 1;
+    }
+    return 4;
+}
+
+static void launch_stream_copy(svo_ctx *ctx, const StreamTable &tab, int n_items, int slot0, bool to_store)
+{
+    StreamCopyArgs a{};
+    a.n_seg = stream_segments(ctx, a.work, a.bytes, a.is_count);
+    for (int k = 0; k < a.n_seg; k++) a.store[k] = ctx->streams.seg[k];
+    a.n_items = n_items; a.slot0 = slot0; a.to_store = to_store ? 1 : 0;
+    a.tab = tab;
+    // the largest segment (two pyramid slots, ~1.2 MB at KITTI size) in 4 KB workgroup trips: 64 workgroups for a lone stream,
+    // fewer per stream as the launch widens (the grid is items x segments x this)
+    int gx = 2048 / n_items;
+    gx = gx > 64 ? 64 : (gx < 8 ? 8 : gx);
+    hipLaunchKernelGGL(stream_copy_kernel, dim3(gx, a.n_seg, n_items), dim3(256), 0, ctx->stream, a);
+}
+
 // Tracks `n_pairs` pairs; pair p = (frame slot fp0 + p*fstep, frame slot fc0 + p*fstep).
 // Front half on the context's stream: circular LK, compaction, triangulation.  Back half (pose
 // solver, gates, chain, optional copy of the records to `results_dev`) on `back_stream`, which is
 // the context's stream, or -- overlap mode -- the side stream, ordered after the front by an event.
 static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, const double *pose0_host,
-                     svo_step_result *results_dev)
+                     svo_step_result *results_dev, const StreamStep *ss = nullptr)
 {
     const PyrGeom &g = ctx->geom;
     const int cap = ctx->cfg.max_keypoints;
@@ -129,7 +208,7 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
         const SnapSpec snap{(const int *)ctx->orb_n, (const int *)ctx->orb_overflow, fp0, fc0, fstep, 2};
         launch_triangulate_batch(ctx, n_pairs, cap, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, &snap);
         mark(ctx, kTTri);
-        return run_back(ctx, n_pairs, pose0_host, results_dev);
+        return run_back(ctx, n_pairs, pose0_host, results_dev, false, ss);
     }
     auto S = [&](int slot) { return ctx->bslots + (size_t)slot * g.slot_bytes; };
     LkArgs a{};
@@ -172,22 +251,23 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
     // side stream with it -- 0.14 ms per 256 pairs, 50 us of a micro-batch's front-end chain --; only the count snapshot stays in
     // front-end order (SVO_TRI_SIDE=0: the round-5 order, for A/B runs)
     static const bool tri_side = !(getenv("SVO_TRI_SIDE") && getenv("SVO_TRI_SIDE")[0] == '0');
-    if (tri_side && ctx->overlap && results_dev != nullptr) {
+    if (tri_side && ctx->overlap && results_dev != nullptr && !ss) {
         launch_snap_counts(ctx, n_pairs, snap, ctx->stream);
         mark(ctx, kTTri);
         return run_back(ctx, n_pairs, pose0_host, results_dev, /*triangulate_first*/ true);
     }
     launch_triangulate_batch(ctx, n_pairs, cap, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, &snap);
     mark(ctx, kTTri);
-    return run_back(ctx, n_pairs, pose0_host, results_dev);
+    return run_back(ctx, n_pairs, pose0_host, results_dev, false, ss);
 }
 
 // Pose stage: solvePnPRansac(X, t2_left) (:299 / :200), gates, frame_pose_ chain, optional copy of the
 // records; on the side stream in overlap mode.
-static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first)
+static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first,
+                    const StreamStep *ss)
 {
     hipStream_t bs = ctx->stream;
-    const bool side = ctx->overlap && results_dev != nullptr;
+    const bool side = ctx->overlap && results_dev != nullptr && !ss;      // a stream-set step is ordered on the context's stream
     if (side) {
         SVO_HIP(hipEventRecord(ctx->ev_front, ctx->stream));
         SVO_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->ev_front, 0));
@@ -197,8 +277,18 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
         launch_triangulate_batch(ctx, n_pairs, ctx->cfg.max_keypoints, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, nullptr, bs);
     launch_pnp_batch(ctx, n_pairs, ctx->cmp[3], ctx->m_out, 0, bs);
     if (!side) mark(ctx, kTPnp);
-    launch_finalize_chain(ctx, n_pairs, ctx->kp_n_snap, ctx->kp_n_snap + n_pairs,
-                          ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->kp_n_snap + 2 * n_pairs : nullptr, pose0_host, bs);
+    const int *ovf = ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->kp_n_snap + 2 * n_pairs : nullptr;
+    if (ss) {
+        // gates per pair, pose_s = pose_s * T_rel_inv per stream (no chain along the launch), init records
+        for (int i0 = 0; i0 < n_pairs; i0 += kStreamChunk) {
+            const int n = n_pairs - i0 < kStreamChunk ? n_pairs - i0 : kStreamChunk;
+            StreamTable tab{};
+            for (int t = 0; t < n; t++) { tab.id[t] = ss->ids[i0 + t]; tab.init[t] = ss->init[i0 + t]; }
+            launch_finalize_streams(ctx, i0, n, n_pairs, ctx->kp_n_snap, ctx->kp_n_snap + n_pairs, ovf, tab, bs);
+        }
+    } else {
+        launch_finalize_chain(ctx, n_pairs, ctx->kp_n_snap, ctx->kp_n_snap + n_pairs, ovf, pose0_host, bs);
+    }
     if (results_dev)
         SVO_HIP(hipMemcpyAsync(results_dev, ctx->d_results, sizeof(svo_step_result) * (size_t)n_pairs,
                                hipMemcpyDeviceToDevice, bs));
@@ -317,6 +407,134 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     memcpy(ctx->pose, res->pose, sizeof(ctx->pose));
     ctx->online_frames++; ctx->online_cur = cur;       // last_frame_ = current_frame_ on both outcomes (:59-68)
     return res->ok ? SVO_OK : res->fail_stage;
+}
+
+// ---- stream sets: many independent live streams through one launch set -----------------------------------------------
+static const char *kTGather = "stream_gather", *kTScatter = "stream_scatter";
+
+int pipeline_streams_create(svo_ctx *ctx, int n_streams)
+{
+    StreamSet &ss = ctx->streams;
+    SVO_ARG(ss.n == 0, "the context already has a stream set");
+    SVO_ARG(n_streams >= 1 && n_streams <= (1 << 20), "n_streams must be >= 1");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (ctx->cfg.track_mode == SVO_MODE_ORB) { const int rc = orb_alloc(ctx); if (rc) return rc; }
+    uint8_t *work[4]; int is_count[4];
+    ss.n_seg = stream_segments(ctx, work, ss.seg_bytes, is_count);
+    for (int k = 0; k < ss.n_seg; k++) {
+        // + 16: a segment whose size is not a multiple of 16 still ends inside its allocation for every access width
+        if (dev_alloc(ctx, &ss.seg[k], ss.seg_bytes[k] * (size_t)n_streams + 16) != SVO_OK) return SVO_ERR_HIP;
+        SVO_HIP(hipMemsetAsync(ss.seg[k], 0, ss.seg_bytes[k] * (size_t)n_streams + 16, ctx->stream));
+    }
+    if (dev_alloc(ctx, &ss.pose, sizeof(double) * 16 * (size_t)n_streams) != SVO_OK) return SVO_ERR_HIP;
+    ss.n_frames.assign((size_t)n_streams, 0);
+    ss.seen.assign((size_t)n_streams, 0);
+    ss.call = 0;
+    ss.n = n_streams;                                  // the set exists from here on
+    launch_streams_set_pose(ctx, 0, n_streams, nullptr);
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
+}
+
+int pipeline_streams_reset(svo_ctx *ctx, int id)
+{
+    StreamSet &ss = ctx->streams;
+    SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(id >= -1 && id < ss.n, "stream id out of range");
+    SVO_HIP(hipSetDevice(ctx->device));
+    const int id0 = id < 0 ? 0 : id, n = id < 0 ? ss.n : 1;
+    for (int s = id0; s < id0 + n; s++) ss.n_frames[(size_t)s] = 0;
+    launch_streams_set_pose(ctx, id0, n, nullptr);     // in stream order: steps queued before it keep their poses
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
+}
+
+int pipeline_streams_set_pose(svo_ctx *ctx, int id, const double *pose)
+{
+    StreamSet &ss = ctx->streams;
+    SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(id >= 0 && id < ss.n && pose, "stream id out of range / null pose");
+    SVO_HIP(hipSetDevice(ctx->device));
+    launch_streams_set_pose(ctx, id, 1, pose);         // the pose travels by value in the argument block
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
+}
+
+int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose)
+{
+    StreamSet &ss = ctx->streams;
+    SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(id >= 0 && id < ss.n && pose, "stream id out of range / null pose");
+    SVO_HIP(hipSetDevice(ctx->device));
+    double *h = (double *)((char *)ctx->h_pinned + 256);
+    SVO_HIP(hipMemcpyAsync(h, ss.pose + (size_t)id * 16, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(pose, h, sizeof(double) * 16);
+    return SVO_OK;
+}
+
+// L / R: DEVICE frames (frame i at base + i * frame_stride), already ordered before the context's stream.
+int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
+                          int64_t frame_stride, svo_step_result *results, int results_mem)
+{
+    StreamSet &ss = ctx->streams;
+    // working frame slots 0 .. m-1 hold the streams' previous frames, m .. 2m-1 the new ones: 2m of the context's max_batch + 1
+    const int m_cap = (ctx->cfg.max_batch + 1) / 2;
+    SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(ids && L && R && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
+    SVO_ARG(m >= 1 && m <= m_cap, "m must be in [1, (max_batch + 1) / 2]");
+    SVO_ARG(pitch >= ctx->cfg.width && (m == 1 || frame_stride >= (int64_t)pitch * ctx->cfg.height), "bad pitch / frame_stride");
+    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
+    for (int i = 0; i < m; i++) SVO_ARG(ids[i] >= 0 && ids[i] < ss.n, "stream id out of range");
+    ss.call++;
+    for (int i = 0; i < m; i++) {
+        SVO_ARG(ss.seen[(size_t)ids[i]] != ss.call, "the same stream id twice in one step");
+        ss.seen[(size_t)ids[i]] = ss.call;
+    }
+    SVO_HIP(hipSetDevice(ctx->device));
+    // one more writer of the working frame slots and the pair buffers, like svo_track_batch: a pending side-stream pose stage
+    // still reads them, and neither a carried frame nor the online ring survives
+    if (ctx->back_pending) {
+        SVO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_back, 0));
+        ctx->back_pending = false;
+    }
+    ctx->carry_slot = -1;
+    ctx->last_batch_pairs = m;
+    std::vector<uint8_t> init((size_t)m);
+    for (int i = 0; i < m; i++) init[(size_t)i] = ss.n_frames[(size_t)ids[i]] == 0;
+    mark(ctx, kT0);
+    for (int i0 = 0; i0 < m; i0 += kStreamChunk) {
+        const int n = m - i0 < kStreamChunk ? m - i0 : kStreamChunk;
+        StreamTable tab{};
+        for (int t = 0; t < n; t++) { tab.id[t] = ids[i0 + t]; tab.init[t] = init[(size_t)(i0 + t)]; }
+        launch_stream_copy(ctx, tab, n, i0, /*to_store*/ false);
+    }
+    mark(ctx, kTGather);
+    int rc = ingest_frames(ctx, L, R, pitch, m == 1 ? 0 : frame_stride, m, m);
+    if (rc) return rc;
+    for (int i0 = 0; i0 < m; i0 += kStreamChunk) {
+        const int n = m - i0 < kStreamChunk ? m - i0 : kStreamChunk;
+        StreamTable tab{};
+        for (int t = 0; t < n; t++) tab.id[t] = ids[i0 + t];
+        launch_stream_copy(ctx, tab, n, m + i0, /*to_store*/ true);
+    }
+    mark(ctx, kTScatter);
+    // last_frame_ = current_frame_ on every outcome (src/tracking.cpp:59-68): the store already holds the new frames
+    for (int i = 0; i < m; i++) ss.n_frames[(size_t)ids[i]]++;
+    const StreamStep step{ids, init.data()};
+    rc = run_pairs(ctx, m, 0, m, 1, nullptr, nullptr, &step);
+    if (rc) return rc;
+    SVO_HIP(hipGetLastError());
+    if (results_mem == SVO_MEM_DEVICE) {
+        if (results)
+            SVO_HIP(hipMemcpyAsync(results, ctx->d_results, sizeof(svo_step_result) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+        return SVO_OK;
+    }
+    svo_step_result *h = (svo_step_result *)((char *)ctx->h_pinned + 4096);
+    SVO_HIP(hipMemcpyAsync(h, ctx->d_results, sizeof(svo_step_result) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(results, h, sizeof(svo_step_result) * (size_t)m);
+    return SVO_OK;
 }
 
 }  // namespace svo

@@ -25,6 +25,12 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
 int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch,
                          int64_t frame_stride, int n_frames, const double *pose0,
                          svo_step_result *results, int results_mem, int carry_first = 0);
+int pipeline_streams_create(svo_ctx *ctx, int n_streams);
+int pipeline_streams_reset(svo_ctx *ctx, int id);
+int pipeline_streams_set_pose(svo_ctx *ctx, int id, const double *pose);
+int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose);
+int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
+                          int64_t frame_stride, svo_step_result *results, int results_mem);
 }  // namespace svo
 
 static int align_up(int v, int a) { return (v + a - 1) / a * a; }
@@ -983,6 +989,87 @@ extern "C" int svo_collect_results(svo_ctx *ctx, svo_step_result *results, int n
     ctx->async_n[r] = 0;
     ctx->async_head++;
     return SVO_OK;
+}
+
+// ---- stream sets: N independent live streams of one context, any subset advanced by one frame each per call --------
+extern "C" int svo_streams_create(svo_ctx *ctx, int n_streams)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return pipeline_streams_create(ctx, n_streams);
+}
+
+extern "C" int svo_streams_count(const svo_ctx *ctx, int *n_streams)
+{
+    if (!ctx || !n_streams) return SVO_ERR_ARG;
+    *n_streams = ctx->streams.n;
+    return SVO_OK;
+}
+
+extern "C" int svo_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *left_frames,
+                                const uint8_t *right_frames, int pitch, int64_t frame_stride, int mem,
+                                svo_step_result *results, int results_mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
+    if (mem == SVO_MEM_DEVICE)
+        return pipeline_streams_step(ctx, stream_ids, m, left_frames, right_frames, pitch, frame_stride, results, results_mem);
+    // host frames: checked here as far as the staging needs it, the rest by the step itself
+    SVO_ARG(stream_ids && left_frames && right_frames, "null pointer");
+    SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
+    SVO_ARG(pitch >= ctx->cfg.width && (m == 1 || frame_stride >= (int64_t)pitch * ctx->cfg.height), "bad pitch / frame_stride");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (m == 1) {
+        // one frame: the pinned staging of svo_add_frame
+        const uint8_t *dL, *dR;
+        int dp = 0;
+        int rc = svo::stage_host_image(ctx, left_frames, pitch, 0, &dL, &dp);
+        if (rc) return rc;
+        rc = svo::stage_host_image(ctx, right_frames, pitch, 1, &dR, &dp);
+        if (rc) return rc;
+        return pipeline_streams_step(ctx, stream_ids, 1, dL, dR, dp, 0, results, results_mem);
+    }
+    // several: frame buffer 0 of svo_upload_frames; the caller's memory is free again when the call returns
+    int rc = svo_upload_frames(ctx, 0, left_frames, right_frames, pitch, frame_stride, m);
+    if (rc) return rc;
+    SVO_HIP(hipEventSynchronize(ctx->ev_up[0]));
+    ctx->fb_frames[0] = 0;                              // (not a batch a later svo_track_uploaded may claim)
+    const size_t fbytes = (size_t)ctx->stage_pitch * ctx->cfg.height, per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
+    rc = pipeline_streams_step(ctx, stream_ids, m, ctx->fb[0], ctx->fb[0] + per_cam, ctx->stage_pitch, (int64_t)fbytes, results,
+                               results_mem);
+    if (rc < 0 && rc != SVO_ERR_HIP) return rc;         // refused before anything was launched
+    SVO_HIP(hipEventRecord(ctx->ev_fb_free[0], ctx->stream));
+    ctx->fb_used[0] = true;
+    return rc;
+}
+
+extern "C" int svo_streams_reset(svo_ctx *ctx, int stream_id)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return pipeline_streams_reset(ctx, stream_id);
+}
+
+extern "C" int svo_streams_get_pose(svo_ctx *ctx, int stream_id, double pose[16])
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return pipeline_streams_get_pose(ctx, stream_id, pose);
+}
+
+extern "C" int svo_streams_set_pose(svo_ctx *ctx, int stream_id, const double pose[16])
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return pipeline_streams_set_pose(ctx, stream_id, pose);
+}
+
+extern "C" int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
+                                    svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out);
+extern "C" int svo_streams_get_tracks(svo_ctx *ctx, int item, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
+                                      svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
+    // item i of a step is pair i of its launch set (an init item has no tracks: n = 0)
+    return svo_get_batch_tracks(ctx, item, t1_left, t1_right, t2_right, t2_left, inlier, cap, n_out);
 }
 
 extern "C" int svo_chain_relative(svo_ctx *ctx, const double *T_rel_inv, const int32_t *ok, int n, const double *pose0,

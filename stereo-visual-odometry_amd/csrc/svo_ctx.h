@@ -22,6 +22,20 @@ struct DevArena {
     std::vector<void *> extra;
 };
 
+// A stream set (svo_streams_create): n independent live stereo streams of one context.  What a stream keeps in HBM between
+// steps is what carry_last_frame moves -- seg[k] + id * seg_bytes[k], k < n_seg -- and its frame_pose_ (pose + 16 * id); the
+// INITING / TRACKING state is host-side (steps are issued in host order).
+struct StreamSet {
+    int n = 0;
+    int n_seg = 0;
+    uint8_t *seg[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t seg_bytes[4] = {0, 0, 0, 0};
+    double *pose = nullptr;
+    std::vector<int> n_frames;        // frames fed since the stream's reset (0: INITING)
+    std::vector<int> seen;            // call number a stream id was last named in (duplicate check)
+    int call = 0;
+};
+
 struct svo_ctx {
     svo_config cfg;
     DevArena arena;
@@ -107,6 +121,8 @@ struct svo_ctx {
     hipEvent_t ev_order = nullptr;    // svo_wait_stream / svo_signal_stream (made on first use)
     bool back_pending = false;
     int *kp_n_snap = nullptr;         // n_prev / n_cur (/ ORB capacity flags) of the batch the pose stage works on: 3 x max_batch
+    // ---- stream set (svo_streams_create; empty until then)
+    StreamSet streams;
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -156,6 +172,12 @@ int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int
                       int n_img, hipStream_t st, bool in_place = false);
 int orb_match_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hipStream_t st);
 void orb_launch_match_fixed(svo_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, hipStream_t st);
+// One step of a stream set: item i of a launch works for stream id[i]; init[i]: the stream's first frame (no previous one).
+constexpr int kStreamChunk = 128;                       // items per gather / scatter / finalize launch (the table is a kernel argument)
+struct StreamTable { int32_t id[kStreamChunk]; uint8_t init[kStreamChunk]; };
+void launch_finalize_streams(svo_ctx *ctx, int item0, int n_items, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
+                             const StreamTable &tab, hipStream_t st);
+void launch_streams_set_pose(svo_ctx *ctx, int id0, int n, const double *pose_host);    // null: identity
 void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
                            const double *pose0_host, hipStream_t st);      // ctx->seed_dev != null: seed read on the device
 }  // namespace svo

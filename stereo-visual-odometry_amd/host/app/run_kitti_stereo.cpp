@@ -9,7 +9,12 @@
 // Additive: run_kitti_stereo cfg.yaml [poses.txt] --split-pairs N [--devices D]
 //   ONE sequence cut into N contiguous chunks of frame pairs (one-frame halo), a context per chunk on device chunk % D, the
 //   relative motions chained once (lzb_vio::RunSplitPairs; SURVEY.md 8e granularity 2): same pose file, no length imbalance.
+// Additive: run_kitti_stereo a.yaml b.yaml ... --poses-dir DIR --interleave
+//   the sequences become the streams of ONE context (lzb_vio::Fleet, svo_streams_step) on device 0 and are
+//   stepped in lockstep, frame t of every sequence that still has one: what N live cameras look like to the library.  The
+//   YAMLs must agree in camera, rig, mode and tracking parameters (exit code 2 names the key that differs); same pose files.
 #include "lzb_vio/System.h"
+#include "lzb_vio/fleet.h"
 #include <unistd.h>
 
 // Orderly teardown is the default: the System is destroyed (pose / tracks files closed, context freed), the HIP runtime's
@@ -41,11 +46,13 @@ int main(int argc, char **argv)
     std::vector<std::string> yamls, rest;
     std::string poses_dir;
     int devices = 0, split = 0;
+    bool interleave = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--poses-dir" && i + 1 < argc) poses_dir = argv[++i];
         else if (a == "--devices" && i + 1 < argc) devices = atoi(argv[++i]);
         else if (a == "--split-pairs" && i + 1 < argc) split = atoi(argv[++i]);
+        else if (a == "--interleave") interleave = true;
         else if (is_yaml(a)) yamls.push_back(a);
         else rest.push_back(a);
     }
@@ -60,6 +67,12 @@ int main(int argc, char **argv)
             pose_files.push_back(f);
         }
         std::vector<lzb_vio::SequenceReport> rep;
+        if (interleave) {
+            const int rc = lzb_vio::RunInterleaved(yamls, pose_files, /*device*/ 0, &rep);
+            for (const auto &r : rep)
+                fprintf(stderr, "%s: stream of device %d, %d frames%s\n", r.yaml.c_str(), r.device, r.frames, r.ok ? "" : "  [FAILED]");
+            return finish(nullptr, rc);
+        }
         const int failed = lzb_vio::RunSequences(yamls, pose_files, devices, &rep);
         for (const auto &r : rep)
             fprintf(stderr, "%s: device %d, %d frames, %.3f s%s\n", r.yaml.c_str(), r.device, r.frames, r.seconds, r.ok ? "" : "  [FAILED]");
@@ -70,8 +83,8 @@ int main(int argc, char **argv)
         const int failed = lzb_vio::RunSplitPairs(yamls[0], rest.empty() ? std::string() : rest[0], split, devices, &rep);
         return finish(nullptr, failed ? 1 : 0);
     }
-    if (argc < 2 || argc > 3 || yamls.size() > 1 || !poses_dir.empty() || devices || split) {
-        fprintf(stderr, "usage: %s config.yaml [poses.txt]\n       %s a.yaml b.yaml ... [--poses-dir DIR] [--devices N]\n"
+    if (argc < 2 || argc > 3 || yamls.size() > 1 || !poses_dir.empty() || devices || split || interleave) {
+        fprintf(stderr, "usage: %s config.yaml [poses.txt]\n       %s a.yaml b.yaml ... [--poses-dir DIR] [--devices N] [--interleave]\n"
                         "       %s config.yaml [poses.txt] --split-pairs N [--devices D]\n", argv[0], argv[0], argv[0]);
         return 2;
     }

@@ -21,6 +21,8 @@ public:
     ~Config() {}
     static bool SetParameterFile(const std::string &filename);
     static bool Has(const std::string &key);
+    // additive: every key / value of the file last loaded (what a runner compares two configurations by)
+    static std::map<std::string, std::string> All() { return config_ ? config_->kv_ : std::map<std::string, std::string>(); }
     template <typename T>
     static T Get(const std::string &key)
     {
