@@ -370,6 +370,72 @@ int svo_streams_set_pose(svo_ctx *ctx, int stream_id, const double pose[16]);
 int svo_streams_get_tracks(svo_ctx *ctx, int item, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
                            svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out);
 
+/* ---- cv::resize and the ingest stage: full-size camera frames downscaled on the GPU before tracking (additive; detected by
+ * symbol, the ABI version stays 9 and svo_config is unchanged) -----------------------------------------------------------
+ * The reference resizes both images before Tracking::AddFrame -- cv::resize(img, img, cv::Size(), 0.5, 0.5, cv::INTER_NEAREST)
+ * at src/System.cpp:94-97, the same with 0.6 at app/ros/robust-vslam/src/robust_vslam_ros.cpp:86-89 -- and every other entry
+ * point of this library takes frames of exactly the context's width x height.  The calls below take frames of ANOTHER
+ * (larger or equal) size and make working-size frames of them on the device.
+ *
+ * Semantics, bit for bit (restated from OpenCV 3's resize.cpp; "parity unpinned": no OpenCV binary exists in the build
+ * environment).  Source sw x sh, destination dw x dh, 8-bit gray, both with a row pitch.  The scale is given
+ *   - in FACTOR form, fx > 0 and fy > 0 (cv::resize(src, dst, Size(), fx, fy)): inv_x = fx, and dw must equal
+ *     cvRound(sw * fx) (rint, ties to even), likewise dh, else SVO_ERR_ARG; or
+ *   - in SIZE form, fx = fy = 0 (cv::resize(src, dst, Size(dw, dh))): inv_x = (double)dw / sw, likewise y.
+ * scale_x = 1.0 / inv_x in double, likewise y.  Only 0 < inv <= 1 on both axes (downscale or identity) and sw, sh <= 8192;
+ * anything else is SVO_ERR_ARG.
+ *   SVO_INTERP_NEAREST: dst[dy][dx] = src[min((int)floor(dy * scale_y), sh - 1)][min((int)floor(dx * scale_x), sw - 1)].
+ *   SVO_INTERP_LINEAR : scale_x == 2.0 && scale_y == 2.0 exactly: upstream reroutes INTER_LINEAR to its integer-area path,
+ *       dst[y][x] = (s[2y][2x] + s[2y][2x+1] + s[2y+1][2x] + s[2y+1][2x+1] + 2) >> 2; needs 2 dw <= sw and 2 dh <= sh
+ *       (SVO_ERR_ARG otherwise: upstream's partial-window tail is not restated).  Any other scale: the 11-bit fixed-point
+ *       bilinear of the ORB pyramid (orc_resize_linear_u8 in oracle/orb.c), with scale_x / scale_y as defined above.
+ *
+ * svo_scale_projection (no context, no device): the projection matrix of the resized image, P_out = S * P with
+ *   S = [[inv_x, 0, ox], [0, inv_y, oy], [0, 0, 1]]; nearest: ox = oy = 0 (destination pixel dx shows source pixel
+ *   dx * scale_x); linear, both branches: ox = 0.5 (inv_x - 1), oy = 0.5 (inv_y - 1) (pixel centres: x_dst =
+ *   (x_src + 0.5) inv_x - 0.5).  A context that tracks resized frames is created with its P1 / P2 passed through it.
+ *   Thresholds in pixels (feature_match_error, reproj_err, the FAST thresholds) are the caller's configuration AT THE
+ *   WORKING SIZE and are not touched.
+ * svo_resize (stage API): n_frames images, frame f at base + f * stride (strides ignored for n_frames = 1), any sizes within
+ *   the limits above, independent of the context's frame size.  `mem` says where BOTH images live; SVO_MEM_DEVICE: one launch
+ *   in stream order on the context's stream, no host synchronisation; SVO_MEM_HOST: copied through device scratch that
+ *   grows on demand, returns when dst is complete.  Bytes of a destination row beyond dw are not written.  The tap tables
+ *   of a geometry (sizes, interp, factors) are built on the host on first use and cached in the context (at most 64
+ *   distinct geometries per context; 8 bytes per destination column + 16 per row on the device).
+ * svo_ingest_create : the ingest stage of a context, source size -> the context's width x height.  Once per context (a
+ *   second call: SVO_ERR_ARG); a context that never calls it allocates and pays nothing.  It allocates the working-size
+ *   device frames the ingest calls resize into: 2 x (max_batch + 1) frames of align256(width) x height bytes (960 x 540,
+ *   max_batch = 256: 284 MB).  Source-size staging for HOST frames comes on first use: svo_ingest_add_frame /
+ *   svo_ingest_streams_step 2 x m frames of align16(src_width) x src_height bytes, svo_ingest_upload_frames_at
+ *   2 x (max_batch + 1) such frames per upload buffer (1920 x 1080, max_batch = 256: 1.07 GB per buffer, 2.1 GB for both).
+ *   The other svo_ingest_* calls before it: SVO_ERR_STATE.
+ * svo_ingest_info   : what the stage was created with, and inv_x / inv_y to hand to svo_scale_projection.
+ * svo_ingest_X (add_frame, track_batch, streams_step, upload_frames_at): svo_X on source-size frames.  `pitch` and
+ *   `frame_stride` describe the SOURCE frames.  The contract is one sentence: its records and every later read-back
+ *   (svo_get_last_tracks, svo_get_batch_tracks, svo_streams_get_tracks, svo_get_frame_keypoints, poses) are byte for byte
+ *   what svo_X gives when it is fed the frames svo_resize makes of the same sources.  Same argument rules, same return
+ *   codes, same stream order as svo_X: the resize runs on the stream svo_X reads its frames on (svo_ingest_upload_frames_at:
+ *   the copy stream, so svo_wait_upload, svo_track_uploaded(_async), SVO_CONTINUE_CARRY_FRAME and svo_collect_results work
+ *   unchanged behind it), device frames are read in stream order (they may be overwritten once svo_signal_stream_inputs /
+ *   svo_sync says so), and with device frames and device results nothing synchronises with the host.  The working-size
+ *   frames of call k are not overwritten before call k's front end has read them (stream order).
+ * The plain entry points keep working on a context with an ingest stage, on working-size frames, undisturbed. */
+#define SVO_INTERP_NEAREST 0
+#define SVO_INTERP_LINEAR  1
+int svo_scale_projection(const double P[12], double inv_x, double inv_y, int interp, double P_out[12]);
+int svo_resize(svo_ctx *ctx, const uint8_t *src, int sw, int sh, int spitch, int64_t sstride,
+               uint8_t *dst, int dw, int dh, int dpitch, int64_t dstride, int n_frames,
+               int interp, double fx, double fy, int mem);
+int svo_ingest_create(svo_ctx *ctx, int src_width, int src_height, int interp, double fx, double fy);
+int svo_ingest_info(const svo_ctx *ctx, int *src_width, int *src_height, int *interp, double *inv_x, double *inv_y);
+int svo_ingest_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem, svo_step_result *res);
+int svo_ingest_track_batch(svo_ctx *ctx, const uint8_t *lefts, const uint8_t *rights, int pitch, int64_t frame_stride,
+                           int n_frames, const double *pose0, svo_step_result *results, int results_mem);
+int svo_ingest_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *lefts, const uint8_t *rights,
+                            int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem);
+int svo_ingest_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *lefts, const uint8_t *rights,
+                                int pitch, int64_t frame_stride, int n_frames);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

@@ -32,6 +32,7 @@ class Config(C.Structure):
 
 
 MODE_LK, MODE_ORB = 0, 1
+INTERP_NEAREST, INTERP_LINEAR = 0, 1                                                        # svo_resize / svo_ingest_create
 LK_ACCUM_EXACT, LK_ACCUM_SSE2, LK_ACCUM_SIMD128, LK_ACCUM_SSE2_LEGACY = 0, 1, 2, 3          # svo_config.lk_accum
 
 
@@ -118,8 +119,40 @@ def load_library():
     lib.svo_streams_get_pose.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.svo_streams_set_pose.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.svo_streams_get_tracks.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_int)]
+    # cv::resize and the ingest stage (additive entry points, like the stream sets)
+    lib.svo_scale_projection.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
+    lib.svo_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
+                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
+    lib.svo_ingest_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
+    lib.svo_ingest_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.svo_ingest_add_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.svo_ingest_track_batch.argtypes = lib.svo_track_batch.argtypes
+    lib.svo_ingest_streams_step.argtypes = lib.svo_streams_step.argtypes
+    lib.svo_ingest_upload_frames_at.argtypes = lib.svo_upload_frames_at.argtypes
     _LIB = lib
     return lib
+
+
+def _interp(interp):
+    """SVO_INTERP_* of "nearest" / "linear" (or the constant itself)."""
+    if isinstance(interp, str):
+        if interp not in ("nearest", "linear"):
+            raise ValueError(f"interp must be 'nearest' or 'linear', not {interp!r}")
+        return INTERP_LINEAR if interp == "linear" else INTERP_NEAREST
+    return int(interp)
+
+
+def scale_projection(P, inv_x, inv_y, interp="nearest"):
+    """svo_scale_projection: the 3 x 4 projection matrix of an image resized by (inv_x, inv_y) -- what a context that tracks
+    resized frames is created with.  Host arithmetic only (no device, no context)."""
+    P = np.ascontiguousarray(P, np.float64).reshape(12)
+    out = np.zeros(12)
+    rc = load_library().svo_scale_projection(C.c_void_p(P.ctypes.data), float(inv_x), float(inv_y), _interp(interp),
+                                             C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise SvoError(f"svo_scale_projection failed ({rc}): inv must be in (0, 1], interp nearest or linear")
+    return out.reshape(3, 4)
 
 
 def device_count():
@@ -403,6 +436,137 @@ class Context:
             self._order_out(dist)
         return idx[:len(query)], dist[:len(query)]
 
+    # ---- cv::resize and the ingest stage (svo_resize / svo_ingest_*) -------------------------------
+    def resize(self, src, dw, dh, interp="nearest", fx=0, fy=0, out=None):
+        """cv::resize of one (h, w) image or a stack (n, h, w) of them, numpy (host) or torch cuda, rows may be padded:
+        factor form (fx, fy > 0; dw x dh must be cvRound(size * f)) or size form (fx = fy = 0).  Returns an array of the
+        same kind, or fills `out` (same kind; rows may be padded, the padding is not written)."""
+        single = src.ndim == 2
+        s3 = src[None] if single else src
+        n, sh, sw = (int(v) for v in s3.shape)
+        is_np = isinstance(s3, np.ndarray)
+        if out is None:
+            if is_np:
+                o3 = np.zeros((n, int(dh), int(dw)), np.uint8)
+            else:
+                import torch
+                o3 = torch.zeros((n, int(dh), int(dw)), dtype=torch.uint8, device=s3.device)
+        else:
+            o3 = out[None] if single else out
+            assert isinstance(o3, np.ndarray) == is_np and tuple(o3.shape) == (n, int(dh), int(dw))
+        if is_np:
+            assert s3.dtype == np.uint8 and o3.dtype == np.uint8 and s3.strides[2] == 1 and o3.strides[2] == 1
+            ps, pd, mem = C.c_void_p(s3.ctypes.data), C.c_void_p(o3.ctypes.data), MEM_HOST
+            sp, ss, dp, ds = s3.strides[1], s3.strides[0], o3.strides[1], o3.strides[0]
+        else:
+            assert s3.element_size() == 1 and o3.element_size() == 1 and s3.stride(2) == 1 and o3.stride(2) == 1
+            assert s3.is_cuda == o3.is_cuda
+            ps, pd = C.c_void_p(s3.data_ptr()), C.c_void_p(o3.data_ptr())
+            mem = MEM_DEVICE if s3.is_cuda else MEM_HOST
+            sp, ss, dp, ds = s3.stride(1), s3.stride(0), o3.stride(1), o3.stride(0)
+        ordered = self._order_in(s3) if mem == MEM_DEVICE else False
+        self._check(self.lib.svo_resize(self.h, ps, sw, sh, int(sp), int(ss), pd, int(dw), int(dh), int(dp), int(ds), n,
+                                        _interp(interp), float(fx), float(fy), mem))
+        if ordered:
+            self._order_out(o3)
+        res = o3 if out is None else out
+        return res[0] if (single and out is None) else res
+
+    def ingest_create(self, src_width, src_height, interp="nearest", fx=0, fy=0):
+        """The ingest stage: frames of src_width x src_height are resized on the device to the context's size (factor form,
+        or fx = fy = 0 for the size form).  Once per context."""
+        self._check(self.lib.svo_ingest_create(self.h, int(src_width), int(src_height), _interp(interp), float(fx), float(fy)))
+        self.src_width, self.src_height = int(src_width), int(src_height)
+
+    def ingest_info(self):
+        """(src_width, src_height, interp, inv_x, inv_y) of the ingest stage; inv_x / inv_y go to scale_projection."""
+        sw, sh, it = C.c_int(0), C.c_int(0), C.c_int(0)
+        ix, iy = C.c_double(0), C.c_double(0)
+        self._check(self.lib.svo_ingest_info(self.h, C.byref(sw), C.byref(sh), C.byref(it), C.byref(ix), C.byref(iy)))
+        return sw.value, sh.value, it.value, ix.value, iy.value
+
+    def _src_shape(self):
+        """The frame shape the ingest calls assert against (before ingest_create: the library answers SVO_ERR_STATE)."""
+        return (getattr(self, "src_height", self.height), getattr(self, "src_width", self.width))
+
+    def _src_img(self, img):
+        assert tuple(img.shape) == self._src_shape(), (tuple(img.shape), self._src_shape())
+        if isinstance(img, np.ndarray):
+            assert img.dtype == np.uint8 and img.strides[1] == 1
+            return C.c_void_p(img.ctypes.data), int(img.strides[0]), MEM_HOST
+        assert img.element_size() == 1 and img.stride(1) == 1
+        return C.c_void_p(img.data_ptr()), int(img.stride(0)), (MEM_DEVICE if img.is_cuda else MEM_HOST)
+
+    def ingest_add_frame(self, left, right):
+        """add_frame on source-size frames (svo_ingest_add_frame)."""
+        pl, pitch, mem = self._src_img(left)
+        pr, pitch_r, mem_r = self._src_img(right)
+        assert pitch == pitch_r and mem == mem_r
+        res = StepResult()
+        if mem == MEM_DEVICE:
+            self._order_in(left)           # as add_frame: the call returns after everything that reads the frames
+        rc = self._check(self.lib.svo_ingest_add_frame(self.h, pl, pr, pitch, mem, C.byref(res)), allow_soft=True)
+        return rc, np.frombuffer(bytes(res), dtype=STEP_DTYPE)[0].copy()
+
+    def ingest_track_batch(self, left_frames, right_frames, pose0=None, results=None):
+        """track_batch on source-size frames: torch cuda uint8 tensors (F, src_height, src_width), rows may be padded."""
+        F = left_frames.shape[0]
+        assert left_frames.is_cuda and right_frames.is_cuda
+        assert tuple(left_frames.shape[1:]) == self._src_shape() and left_frames.shape == right_frames.shape
+        assert left_frames.stride(2) == 1 and left_frames.stride() == right_frames.stride()
+        pitch, fstride = left_frames.stride(1), left_frames.stride(0)
+        p0 = None
+        if pose0 is not None:
+            pose0 = np.ascontiguousarray(pose0, np.float64).reshape(16)
+            p0 = C.c_void_p(pose0.ctypes.data)
+        if results is None:
+            out = np.zeros(F - 1, dtype=STEP_DTYPE)
+            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
+        else:
+            out = results
+            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
+        # stream ordering as track_batch: the source frames are read by the resize kernel on the context's stream
+        ordered = self._order_in(left_frames)
+        self._check(self.lib.svo_ingest_track_batch(self.h, C.c_void_p(left_frames.data_ptr()),
+                                                    C.c_void_p(right_frames.data_ptr()), int(pitch), int(fstride),
+                                                    int(F), p0, rp, rmem))
+        if results is not None and ordered:
+            import torch
+            self.signal_stream_inputs(torch.cuda.current_stream(left_frames.device).cuda_stream)
+        return out
+
+    def ingest_streams_step(self, ids, lefts, rights, results=None):
+        """streams_step on source-size frames (svo_ingest_streams_step)."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        m = int(ids.shape[0])
+        shape = self._src_shape()
+        fl, pl, pitch, fstride, mem = self._frame_stack(lefts, shape) if m else (None, None, shape[1], 0, MEM_HOST)
+        fr, pr, pitch_r, fstride_r, mem_r = self._frame_stack(rights, shape) if m else (None, None, shape[1], 0, MEM_HOST)
+        assert (pitch, fstride, mem) == (pitch_r, fstride_r, mem_r)
+        assert m == 0 or (fl.shape[0] == m and fr.shape[0] == m)
+        if results is None:
+            out = np.zeros(m, dtype=STEP_DTYPE)
+            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
+        else:
+            out = results
+            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
+        ordered = False
+        if mem == MEM_DEVICE:
+            ordered = self._order_in(fl)
+        self._check(self.lib.svo_ingest_streams_step(self.h, C.c_void_p(ids.ctypes.data), m, pl, pr, pitch, fstride, mem, rp, rmem))
+        if results is not None and ordered:
+            self._order_out(fl)
+        return out
+
+    def ingest_upload_frames(self, buf, left, right, first_slot=0):
+        """upload_frames on source-size host frames (F, src_height, pitch): copied and resized into device frame buffer
+        `buf` on the copy stream (svo_ingest_upload_frames_at); wait_upload / track_uploaded(_async) follow as usual."""
+        assert left.shape == right.shape and left.strides == right.strides and left.strides[2] == 1
+        assert tuple(left.shape[1:]) == self._src_shape(), (tuple(left.shape), self._src_shape())
+        self._check(self.lib.svo_ingest_upload_frames_at(self.h, int(buf), int(first_slot), C.c_void_p(left.ctypes.data),
+                                                         C.c_void_p(right.ctypes.data), int(left.strides[1]), int(left.strides[0]),
+                                                         int(left.shape[0])))
+
     # ---- fused API --------------------------------------------------------------------------
     def add_frame(self, left, right):
         pl, pitch, mem = self._img(left)
@@ -460,15 +624,16 @@ class Context:
         return out
 
     # ---- host-resident frame batches (svo_upload_frames / svo_track_uploaded) -----------------
-    def host_frames(self, n_frames, pitch=None):
+    def host_frames(self, n_frames, pitch=None, source_size=False):
         """(n_frames, height, pitch) uint8 numpy view over page-locked host memory (svo_host_alloc);
-        release it with host_free(view)."""
-        pitch = pitch or self.width
-        nbytes = int(n_frames) * self.height * int(pitch)
+        release it with host_free(view).  source_size: frames of the ingest stage's source size (ingest_upload_frames)."""
+        height, width = self._src_shape() if source_size else (self.height, self.width)
+        pitch = pitch or width
+        nbytes = int(n_frames) * height * int(pitch)
         p = C.c_void_p()
         self._check(self.lib.svo_host_alloc(self.h, nbytes, C.byref(p)))
         buf = (C.c_uint8 * nbytes).from_address(p.value)
-        view = np.frombuffer(buf, dtype=np.uint8).reshape(int(n_frames), self.height, int(pitch))
+        view = np.frombuffer(buf, dtype=np.uint8).reshape(int(n_frames), height, int(pitch))
         self._pinned = getattr(self, "_pinned", {})
         self._pinned[view.ctypes.data] = p
         return view
@@ -585,7 +750,7 @@ class Context:
         self._check(self.lib.svo_streams_count(self.h, C.byref(n)))
         return n.value
 
-    def _frame_stack(self, frames):
+    def _frame_stack(self, frames, shape=None):
         """(array, pointer, pitch, frame stride, memory kind) of m equal-size u8 frames: a stacked (m, h, w) numpy array or
         torch tensor (rows may be padded), or a list of (h, w) images, which is stacked."""
         if isinstance(frames, (list, tuple)):
@@ -594,7 +759,8 @@ class Context:
             else:
                 import torch
                 frames = torch.stack(list(frames))
-        assert tuple(frames.shape[1:]) == (self.height, self.width), (tuple(frames.shape), self.height, self.width)
+        shape = shape or (self.height, self.width)
+        assert tuple(frames.shape[1:]) == tuple(shape), (tuple(frames.shape), shape)
         if isinstance(frames, np.ndarray):
             assert frames.dtype == np.uint8 and frames.strides[2] == 1
             return frames, C.c_void_p(frames.ctypes.data), int(frames.strides[1]), int(frames.strides[0]), MEM_HOST

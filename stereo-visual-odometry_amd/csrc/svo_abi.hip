@@ -149,6 +149,8 @@ extern "C" void svo_default_config(svo_config *cfg, int width, int height)
 static void free_all(svo_ctx *c)
 {
     dev_release(c);                                   // every device buffer: the arena + the lazy extras
+    for (int k = 0; k < 2; k++) if (c->resize_scratch[k]) (void)hipFree(c->resize_scratch[k]);
+    if (c->ingest.src_stage) (void)hipFree(c->ingest.src_stage);
     if (c->ev_front) (void)hipEventDestroy(c->ev_front);
     if (c->ev_back) (void)hipEventDestroy(c->ev_back);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -1070,6 +1072,194 @@ extern "C" int svo_streams_get_tracks(svo_ctx *ctx, int item, svo_pt2f *t1_left,
     SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
     // item i of a step is pair i of its launch set (an init item has no tracks: n = 0)
     return svo_get_batch_tracks(ctx, item, t1_left, t1_right, t2_right, t2_left, inlier, cap, n_out);
+}
+
+// ---- ingest stage: source-size frames resized on the device into working-size frames the existing entry points read --------
+// (the kernel, the tap tables, svo_resize and svo_scale_projection: resize.hip)
+#define SVO_INGEST_ON() do { if (!ctx->ingest.on) { ctx->err = "no ingest stage (svo_ingest_create)"; return SVO_ERR_STATE; } } while (0)
+
+static size_t ingest_work_frame(const svo_ctx *ctx) { return (size_t)ctx->stage_pitch * ctx->cfg.height; }
+static size_t ingest_src_frame(const svo_ctx *ctx) { return (size_t)ctx->ingest.spitch * ctx->ingest.sh; }
+
+extern "C" int svo_ingest_create(svo_ctx *ctx, int src_width, int src_height, int interp, double fx, double fy)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    Ingest &g = ctx->ingest;
+    SVO_ARG(!g.on, "the context already has an ingest stage");
+    SVO_HIP(hipSetDevice(ctx->device));
+    int tab = -1;
+    int rc = resize_plan(ctx, src_width, src_height, ctx->cfg.width, ctx->cfg.height, interp, fx, fy, &tab);
+    if (rc) return rc;
+    if (!g.work && dev_alloc(ctx, &g.work, 2 * ingest_work_frame(ctx) * (size_t)(ctx->cfg.max_batch + 1)) != SVO_OK) return SVO_ERR_HIP;
+    g.sw = src_width; g.sh = src_height; g.tab = tab;
+    g.spitch = (src_width + 15) & ~15;
+    g.on = true;
+    return SVO_OK;
+}
+
+extern "C" int svo_ingest_info(const svo_ctx *ctx, int *src_width, int *src_height, int *interp, double *inv_x, double *inv_y)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (!ctx->ingest.on) return SVO_ERR_STATE;
+    const ResizeTab &t = ctx->resize_tabs[(size_t)ctx->ingest.tab];
+    if (src_width) *src_width = t.sw;
+    if (src_height) *src_height = t.sh;
+    if (interp) *interp = t.interp;
+    if (inv_x) *inv_x = t.inv_x;
+    if (inv_y) *inv_y = t.inv_y;
+    return SVO_OK;
+}
+
+// Left / right working-size frames of slot `slot`.
+static uint8_t *ingest_work(svo_ctx *ctx, int eye, int slot)
+{
+    return ctx->ingest.work + ((size_t)eye * (size_t)(ctx->cfg.max_batch + 1) + (size_t)slot) * ingest_work_frame(ctx);
+}
+
+// n source-size HOST frames per eye -> the stage's device staging, on the context's stream; the caller's memory is free again
+// when this returns.
+static int ingest_stage_host(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int64_t frame_stride, int n,
+                             const uint8_t **dL, const uint8_t **dR)
+{
+    Ingest &g = ctx->ingest;
+    const size_t fbytes = ingest_src_frame(ctx);
+    if (g.src_stage_frames < n) {
+        if (g.src_stage) {
+            SVO_HIP(hipStreamSynchronize(ctx->stream));
+            SVO_HIP(hipFree(g.src_stage));
+            g.src_stage = nullptr; g.src_stage_frames = 0;
+        }
+        SVO_HIP(hipMalloc((void **)&g.src_stage, 2 * fbytes * (size_t)n));
+        g.src_stage_frames = n;
+    }
+    const uint8_t *src[2] = {left, right};
+    for (int eye = 0; eye < 2; eye++) {
+        uint8_t *dst = g.src_stage + (size_t)eye * fbytes * (size_t)n;
+        if (pitch == g.spitch && (n == 1 || frame_stride == (int64_t)fbytes)) {
+            SVO_HIP(hipMemcpyAsync(dst, src[eye], fbytes * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        } else {
+            for (int f = 0; f < n; f++)
+                SVO_HIP(hipMemcpy2DAsync(dst + f * fbytes, (size_t)g.spitch, src[eye] + (n > 1 ? f * frame_stride : 0), (size_t)pitch,
+                                         (size_t)g.sw, (size_t)g.sh, hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    *dL = g.src_stage; *dR = g.src_stage + fbytes * (size_t)n;
+    return SVO_OK;
+}
+
+extern "C" int svo_ingest_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem, svo_step_result *res)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    SVO_ARG(left && right && res, "null pointer");
+    SVO_ARG(pitch >= ctx->ingest.sw, "pitch < source width");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
+    SVO_HIP(hipSetDevice(ctx->device));
+    const uint8_t *sL = left, *sR = right;
+    int sp = pitch;
+    if (mem == SVO_MEM_HOST) {
+        int rc = ingest_stage_host(ctx, left, right, pitch, 0, 1, &sL, &sR);
+        if (rc) return rc;
+        sp = ctx->ingest.spitch;
+    }
+    uint8_t *wL = ingest_work(ctx, 0, 0), *wR = ingest_work(ctx, 1, 0);
+    int rc = resize_launch(ctx, ctx->ingest.tab, sL, sR, sp, 0, wL, wR, ctx->stage_pitch, 0, 1, ctx->stream);
+    if (rc) return rc;
+    return pipeline_add_frame(ctx, wL, wR, ctx->stage_pitch, SVO_MEM_DEVICE, res);
+}
+
+extern "C" int svo_ingest_track_batch(svo_ctx *ctx, const uint8_t *lefts, const uint8_t *rights, int pitch, int64_t frame_stride,
+                                      int n_frames, const double *pose0, svo_step_result *results, int results_mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    // svo_track_batch's rules, against the source size: nothing is launched for a call it would refuse
+    SVO_ARG(lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
+    SVO_ARG(n_frames >= 2 && n_frames - 1 <= ctx->cfg.max_batch, "n_frames - 1 must be in [1, max_batch]");
+    SVO_ARG(pitch >= ctx->ingest.sw && frame_stride >= (int64_t)pitch * ctx->ingest.sh, "bad pitch / frame_stride");
+    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
+    SVO_HIP(hipSetDevice(ctx->device));
+    uint8_t *wL = ingest_work(ctx, 0, 0), *wR = ingest_work(ctx, 1, 0);
+    const int64_t wstride = (int64_t)ingest_work_frame(ctx);
+    int rc = resize_launch(ctx, ctx->ingest.tab, lefts, rights, pitch, frame_stride, wL, wR, ctx->stage_pitch, wstride, n_frames, ctx->stream);
+    if (rc) return rc;
+    return pipeline_track_batch(ctx, wL, wR, ctx->stage_pitch, wstride, n_frames, pose0, results, results_mem);
+}
+
+extern "C" int svo_ingest_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *lefts, const uint8_t *rights,
+                                       int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
+    SVO_ARG(stream_ids && lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
+    SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
+    SVO_ARG(pitch >= ctx->ingest.sw && (m == 1 || frame_stride >= (int64_t)pitch * ctx->ingest.sh), "bad pitch / frame_stride");
+    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
+    // ids: checked before anything is launched, as svo_streams_step does (the step itself checks them again and counts the call)
+    for (int i = 0; i < m; i++) {
+        SVO_ARG(stream_ids[i] >= 0 && stream_ids[i] < ctx->streams.n, "stream id out of range");
+        for (int j = 0; j < i; j++) SVO_ARG(stream_ids[j] != stream_ids[i], "the same stream id twice in one step");
+    }
+    SVO_HIP(hipSetDevice(ctx->device));
+    const uint8_t *sL = lefts, *sR = rights;
+    int sp = pitch;
+    int64_t sstride = frame_stride;
+    if (mem == SVO_MEM_HOST) {
+        int rc = ingest_stage_host(ctx, lefts, rights, pitch, frame_stride, m, &sL, &sR);
+        if (rc) return rc;
+        sp = ctx->ingest.spitch; sstride = (int64_t)ingest_src_frame(ctx);
+    }
+    uint8_t *wL = ingest_work(ctx, 0, 0), *wR = ingest_work(ctx, 1, 0);
+    const int64_t wstride = (int64_t)ingest_work_frame(ctx);
+    int rc = resize_launch(ctx, ctx->ingest.tab, sL, sR, sp, sstride, wL, wR, ctx->stage_pitch, wstride, m, ctx->stream);
+    if (rc) return rc;
+    return pipeline_streams_step(ctx, stream_ids, m, wL, wR, ctx->stage_pitch, wstride, results, results_mem);
+}
+
+// svo_upload_frames_at with the resize between the copy and the frame buffer: host -> source-size staging -> fb[buf], all on
+// the copy stream, so everything behind ev_up[buf] works unchanged.
+extern "C" int svo_ingest_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *lefts, const uint8_t *rights,
+                                           int pitch, int64_t frame_stride, int n_frames)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    Ingest &g = ctx->ingest;
+    SVO_ARG(buf == 0 || buf == 1, "buf must be 0 or 1");
+    SVO_ARG(lefts && rights, "null frames");
+    SVO_ARG(first_slot >= 0 && n_frames >= 1 && first_slot + n_frames <= ctx->cfg.max_batch + 1, "first_slot + n_frames must be in [1, max_batch + 1]");
+    SVO_ARG(first_slot <= 1, "first_slot must be 0 (a whole batch) or 1 (frame 0 is carried on the device)");
+    SVO_ARG(pitch >= g.sw && frame_stride >= (int64_t)pitch * g.sh, "bad pitch / frame_stride");
+    SVO_HIP(hipSetDevice(ctx->device));
+    int rc = frame_buffers(ctx);
+    if (rc) return rc;
+    const size_t sbytes = ingest_src_frame(ctx), s_per_cam = sbytes * (size_t)(ctx->cfg.max_batch + 1);
+    if (!g.up_stage[buf] && dev_alloc(ctx, &g.up_stage[buf], 2 * s_per_cam) != SVO_OK) return SVO_ERR_HIP;
+    const size_t fbytes = ingest_work_frame(ctx), per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
+    // the batch that last read this buffer must have been ingested (the staging behind it is reused in copy-stream order)
+    if (ctx->fb_used[buf]) SVO_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_fb_free[buf], 0));
+    const uint8_t *src[2] = {lefts, rights};
+    uint8_t *stg[2];
+    for (int cam = 0; cam < 2; cam++) {
+        stg[cam] = g.up_stage[buf] + cam * s_per_cam + (size_t)first_slot * sbytes;
+        if (pitch == g.spitch && frame_stride == (int64_t)sbytes) {
+            SVO_HIP(hipMemcpyAsync(stg[cam], src[cam], sbytes * (size_t)n_frames, hipMemcpyHostToDevice, ctx->copy_stream));
+        } else {
+            for (int f = 0; f < n_frames; f++)
+                SVO_HIP(hipMemcpy2DAsync(stg[cam] + f * sbytes, (size_t)g.spitch, src[cam] + f * frame_stride, (size_t)pitch, (size_t)g.sw,
+                                         (size_t)g.sh, hipMemcpyHostToDevice, ctx->copy_stream));
+        }
+    }
+    uint8_t *dL = ctx->fb[buf] + (size_t)first_slot * fbytes;
+    rc = resize_launch(ctx, g.tab, stg[0], stg[1], g.spitch, (int64_t)sbytes, dL, dL + per_cam, ctx->stage_pitch, (int64_t)fbytes, n_frames,
+                       ctx->copy_stream);
+    if (rc) return rc;
+    SVO_HIP(hipEventRecord(ctx->ev_up[buf], ctx->copy_stream));
+    ctx->fb_frames[buf] = first_slot + n_frames;
+    ctx->fb_first[buf] = first_slot;
+    return SVO_OK;
 }
 
 extern "C" int svo_chain_relative(svo_ctx *ctx, const double *T_rel_inv, const int32_t *ok, int n, const double *pose0,

@@ -36,6 +36,29 @@ struct StreamSet {
     int call = 0;
 };
 
+// One cv::resize geometry (resize.hip): the tap tables of (source size, destination size, interpolation, factors), built on
+// the host in double exactly as include/svo_abi.h states them and uploaded once, and the launch shape derived from them.
+struct ResizeTab {
+    int sw = 0, sh = 0, dw = 0, dh = 0, interp = 0;
+    double fx = 0, fy = 0;            // the key: factor form (fx, fy > 0) or size form (0, 0)
+    double inv_x = 1, inv_y = 1;
+    bool box = false;                 // INTER_LINEAR at exactly 2x: the 2x2 mean, no tables
+    void *xt = nullptr, *yt = nullptr;   // int2 per destination column (sx | sx1 << 16, a0 | a1 << 16), int4 per row (y0, y1, b0, b1)
+    int bx_shift = 8, rpt = 8;        // workgroup = 2^bx_shift lanes along x (4 pixels each) x 256 >> bx_shift lane rows x rpt rows per lane
+    int lds_pitch = 0, lds_rows = 0;  // staged source rows: bytes per row (multiple of 16), rows; 0 rows: gathered from global memory
+};
+
+// The ingest stage of a context (svo_ingest_create): source-size frames -> the context's width x height.
+struct Ingest {
+    bool on = false;
+    int sw = 0, sh = 0, tab = -1;
+    int spitch = 0;                   // row pitch of the source-size staging (16-byte aligned)
+    uint8_t *work = nullptr;          // working-size frames: 2 eyes x (max_batch + 1) slots, stage_pitch rows
+    uint8_t *src_stage = nullptr;     // source-size staging of HOST frames (svo_ingest_add_frame / _streams_step), grown on demand
+    int src_stage_frames = 0;
+    uint8_t *up_stage[2] = {nullptr, nullptr};   // source-size staging behind fb[0] / fb[1] (svo_ingest_upload_frames_at), first use
+};
+
 struct svo_ctx {
     svo_config cfg;
     DevArena arena;
@@ -123,6 +146,11 @@ struct svo_ctx {
     int *kp_n_snap = nullptr;         // n_prev / n_cur (/ ORB capacity flags) of the batch the pose stage works on: 3 x max_batch
     // ---- stream set (svo_streams_create; empty until then)
     StreamSet streams;
+    // ---- cv::resize (svo_resize) and the ingest stage (svo_ingest_*); nothing is allocated until they are used
+    std::vector<ResizeTab> resize_tabs;
+    uint8_t *resize_scratch[2] = {nullptr, nullptr};     // device copies of svo_resize's HOST source / destination
+    size_t resize_scratch_bytes[2] = {0, 0};
+    Ingest ingest;
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -172,6 +200,11 @@ int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int
                       int n_img, hipStream_t st, bool in_place = false);
 int orb_match_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hipStream_t st);
 void orb_launch_match_fixed(svo_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, hipStream_t st);
+// resize.hip
+int resize_plan(svo_ctx *ctx, int sw, int sh, int dw, int dh, int interp, double fx, double fy, int *tab);
+// n_frames images per eye (eye 1 may be null), frame f at base + f * stride; one launch
+int resize_launch(svo_ctx *ctx, int tab, const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
+                  uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st);
 // One step of a stream set: item i of a launch works for stream id[i]; init[i]: the stream's first frame (no previous one).
 constexpr int kStreamChunk = 128;                       // items per gather / scatter / finalize launch (the table is a kernel argument)
 struct StreamTable { int32_t id[kStreamChunk]; uint8_t init[kStreamChunk]; };

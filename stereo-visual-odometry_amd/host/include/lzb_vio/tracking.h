@@ -41,6 +41,21 @@ public:
     bool GetLastTracks(std::vector<cv::Point2f> &t1_left, std::vector<cv::Point2f> &t1_right,
                        std::vector<cv::Point2f> &t2_left, std::vector<unsigned char> &inlier);
 
+    // additive YAML keys image_scale / image_interp (reference src/System.cpp:93-97: cv::resize(img, img, Size(), f, f,
+    // INTER_NEAREST) in front of AddFrame).  image_scale: f in (0, 1]; absent or 1: the frames are tracked as they come and no
+    // ingest stage exists.  image_interp: nearest (default, the reference's choice) | linear.  With f < 1 the context is
+    // created at the WORKING size cvRound(file size * f) with P1 / P2 passed through svo_scale_projection, and the frames
+    // travel through the svo_ingest_* twins of the entry points (include/svo_abi.h); thresholds in pixels are the YAML's
+    // values AT THE WORKING SIZE.  ReadImageScale reads and checks the two keys of the loaded YAML (false + a message that
+    // names the key); ConfigError() is that message for this object's YAML (empty: fine).
+    static bool ReadImageScale(double *scale, int *interp, std::string *err);
+    const std::string &ConfigError() const { return config_error_; }
+    bool Ingest() const { return image_scale_ < 1.0; }
+    double ImageScale() const { return image_scale_; }
+    int ImageInterp() const { return image_interp_; }
+    int WorkWidth() const { return work_w_; }               // the context's frame size (0 before the first frame)
+    int WorkHeight() const { return work_h_; }
+
     // additive: batched tracking of host-resident frames.  The context is
     // (re)created for `max_batch` frame pairs per launch; frames travel with svo_upload_frames and
     // TrackUploaded runs svo_track_uploaded on device buffer `buf`, appends the n_frames - 1 step
@@ -82,7 +97,11 @@ private:
     long max_keypoints_key_ = 0;                             // additive YAML key max_keypoints, read once (0 = absent)
     int fast_keep_strongest_ = 0;                            // additive YAML key fast_keep_strongest (0 = every corner)
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128
-    int ctx_w_ = 0, ctx_h_ = 0, ctx_batch_ = 0;
+    double image_scale_ = 1.0;                               // additive YAML key image_scale (1 = no ingest stage)
+    int image_interp_ = SVO_INTERP_NEAREST;                  // additive YAML key image_interp: nearest (default) | linear
+    std::string config_error_;
+    int ctx_w_ = 0, ctx_h_ = 0, ctx_batch_ = 0;              // the size the context was built FOR: the frames' (source) size
+    int work_w_ = 0, work_h_ = 0;                            // the context's own size: cvRound(source * image_scale)
     int async_pairs_[2] = {0, 0};
     unsigned async_head_ = 0, async_tail_ = 0;
     svo_step_result last_;

@@ -342,6 +342,10 @@ System::System(std::string &config_path) : config_file_path_(config_path)
     init_parameter_ = Parameter::Ptr(new Parameter);
     sensors_ = Sensors::Ptr(new Sensors(init_parameter_));
     tracking_ = Tracking::Ptr(new Tracking(this, init_parameter_, sensors_));
+    if (!tracking_->ConfigError().empty()) {               // refused on the host, before a device is opened
+        fprintf(stderr, "%s: %s\n", config_file_path_.c_str(), tracking_->ConfigError().c_str());
+        exit(2);
+    }
     dataset_path_ = init_parameter_->dataset_path_;
     // additive keys pose_file / tracks_file (the headless stand-in for Tracking::displayTracking, src/tracking.cpp:345-382).
     // A System that only probes the sequence or hands its records to a sink (RunSplitPairs) must not open -- and truncate --
@@ -598,7 +602,9 @@ void System::RunBatched(int B, int decode_threads)
     };
     auto upload = [&](int k, int n) {
         svo_ctx *c = tracking_->Context();
-        int rc = svo_upload_frames(c, k, pin[k][0], pin[k][1], pitch, (int64_t)fbytes, n);
+        // (image_scale: the page-locked buffers hold source-size frames, the resize runs behind the copy on the copy stream)
+        int rc = tracking_->Ingest() ? svo_ingest_upload_frames_at(c, k, 0, pin[k][0], pin[k][1], pitch, (int64_t)fbytes, n)
+                                     : svo_upload_frames(c, k, pin[k][0], pin[k][1], pitch, (int64_t)fbytes, n);
         if (rc != SVO_OK) LZB_LOG("ERROR", "svo_upload_frames: %s", svo_last_error(c));
         return rc == SVO_OK;
     };
@@ -719,8 +725,9 @@ bool System::StreamSubmit()
     // after the first micro-batch the halo frame (slot 0) is carried ON THE DEVICE (Tracking::TrackUploadedAsync asks for
     // SVO_CONTINUE_CARRY_FRAME with the chain): it is neither copied on the host nor uploaded again
     const int s0 = s.chunk > 0 ? 1 : 0;
-    if (svo_upload_frames_at(ctx, s.buf, s0, s.pin[s.buf][0] + (size_t)s0 * s.fbytes, s.pin[s.buf][1] + (size_t)s0 * s.fbytes, s.pitch,
-                             (int64_t)s.fbytes, s.n - s0) != SVO_OK) {
+    if ((tracking_->Ingest() ? svo_ingest_upload_frames_at : svo_upload_frames_at)(
+            ctx, s.buf, s0, s.pin[s.buf][0] + (size_t)s0 * s.fbytes, s.pin[s.buf][1] + (size_t)s0 * s.fbytes, s.pitch,
+            (int64_t)s.fbytes, s.n - s0) != SVO_OK) {
         LZB_LOG("ERROR", "svo_upload_frames_at: %s", svo_last_error(ctx));
         return false;
     }

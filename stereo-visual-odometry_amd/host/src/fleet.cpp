@@ -15,6 +15,10 @@ Fleet::Fleet(const std::string &config_path, int n_streams, int max_step)
     parameter_ = Parameter::Ptr(new Parameter);
     sensors_ = Sensors::Ptr(new Sensors(parameter_));
     tracking_ = Tracking::Ptr(new Tracking(nullptr, parameter_, sensors_));
+    if (!tracking_->ConfigError().empty()) {               // refused on the host, before a device is opened
+        fprintf(stderr, "%s: %s\n", config_path.c_str(), tracking_->ConfigError().c_str());
+        exit(2);
+    }
     n_streams_ = n_streams < 1 ? 1 : n_streams;
     max_step_ = max_step < 1 || max_step > n_streams_ ? n_streams_ : max_step;
     poses_.assign((size_t)n_streams_, Pose4x4());
@@ -63,7 +67,8 @@ std::vector<bool> Fleet::Step(const std::vector<std::pair<int, Frame::Ptr>> &fra
                 memcpy(pin_[cam] + (size_t)i * fbytes + (size_t)y * pitch_, img[cam]->data + (size_t)y * img[cam]->step, (size_t)w_);
     }
     std::vector<svo_step_result> res((size_t)m);
-    const int rc = svo_streams_step(ctx, ids.data(), m, pin_[0], pin_[1], pitch_, (int64_t)fbytes, SVO_MEM_HOST, res.data(), SVO_MEM_HOST);
+    const int rc = (tracking_->Ingest() ? svo_ingest_streams_step : svo_streams_step)(ctx, ids.data(), m, pin_[0], pin_[1], pitch_, (int64_t)fbytes,
+                                                                                      SVO_MEM_HOST, res.data(), SVO_MEM_HOST);
     if (rc != SVO_OK) return fail(svo_last_error(ctx));
     for (int i = 0; i < m; i++) {
         const svo_step_result &r = res[(size_t)i];
@@ -142,6 +147,11 @@ int RunInterleaved(const std::vector<std::string> &yamls, const std::vector<std:
                     return 2;
                 }
         }
+    }
+    {
+        // image_scale / image_interp are shared keys like every other (compared above); their values are checked here
+        double scale; int interp; std::string err;
+        if (!Tracking::ReadImageScale(&scale, &interp, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
     }
     for (int s = 0; s < n; s++) {
         cv::Mat l, r;

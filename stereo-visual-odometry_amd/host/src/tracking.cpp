@@ -3,8 +3,29 @@
 // everything below it is ONE svo_add_frame call: FAST -> 4x LK -> filter -> triangulate ->
 // solvePnPRansac -> gates -> frame_pose_ update all happen on the GPU.
 #include "lzb_vio/tracking.h"
+#include <cmath>
 
 namespace lzb_vio {
+
+bool Tracking::ReadImageScale(double *scale, int *interp, std::string *err)
+{
+    *scale = 1.0; *interp = SVO_INTERP_NEAREST;
+    if (Config::Has("image_interp")) {
+        const std::string v = Config::Get<std::string>("image_interp");
+        if (v == "linear") *interp = SVO_INTERP_LINEAR;
+        else if (v != "nearest") LZB_LOG("WARNING", "image_interp: '%s' is neither 'nearest' nor 'linear'; using 'nearest'", v.c_str());
+    }
+    if (!Config::Has("image_scale")) return true;
+    const double f = Config::Get<double>("image_scale");
+    if (!(f > 0.0 && f <= 1.0)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "image_scale: %g is outside (0, 1] (frames are downscaled before tracking, never enlarged)", f);
+        if (err) *err = msg;
+        return false;
+    }
+    *scale = f;
+    return true;
+}
 
 Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensors)
 {
@@ -28,6 +49,7 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
         else if (v == "sse2_legacy") lk_accum_ = SVO_LK_ACCUM_SSE2_LEGACY;
         else if (v != "exact") LZB_LOG("WARNING", "lk_accum: '%s' is none of 'exact', 'sse2', 'simd128', 'sse2_legacy'; using 'exact'", v.c_str());
     }
+    if (!ReadImageScale(&image_scale_, &image_interp_, &config_error_)) image_scale_ = 1.0;     // the owner refuses to run (ConfigError)
 }
 
 Tracking::~Tracking()
@@ -81,6 +103,10 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
                 "re-initialises the tracker (no motion is estimated for it), the pose chain continues from frame_pose_",
                 ctx_w_, ctx_h_, width, height);
     if (ctx_) { svo_destroy(ctx_); ctx_ = nullptr; }
+    // image_scale: width x height is the SOURCE size the ingest stage takes; the context itself (and the default
+    // max_keypoints below) has the working size, as cv::resize(..., Size(), f, f) makes it: cvRound(size * f)
+    const int src_w = width, src_h = height;
+    if (Ingest()) { width = (int)std::nearbyint(src_w * image_scale_); height = (int)std::nearbyint(src_h * image_scale_); }
     svo_config cfg;
     svo_default_config(&cfg, width, height);
     cfg.max_batch = max_batch;
@@ -121,13 +147,26 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
     }
     memcpy(cfg.P1, sensors_->projMatr1_, sizeof(cfg.P1));
     memcpy(cfg.P2, sensors_->projMatr2_, sizeof(cfg.P2));
+    if (Ingest() && (svo_scale_projection(sensors_->projMatr1_, image_scale_, image_scale_, image_interp_, cfg.P1) != SVO_OK ||
+                     svo_scale_projection(sensors_->projMatr2_, image_scale_, image_scale_, image_interp_, cfg.P2) != SVO_OK)) {
+        LZB_LOG("ERROR", "svo_scale_projection refused image_scale = %g", image_scale_);
+        return false;
+    }
     int rc = svo_create(&cfg, device_, &ctx_);
     if (rc != SVO_OK) {
         LZB_LOG("ERROR", "svo_create failed (%d): a HIP device is required, there is no CPU path", rc);
         ctx_ = nullptr;
         return false;
     }
-    ctx_w_ = width; ctx_h_ = height; ctx_batch_ = max_batch;
+    if (Ingest() && (rc = svo_ingest_create(ctx_, src_w, src_h, image_interp_, image_scale_, image_scale_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_ingest_create (image_scale %g, %dx%d -> %dx%d) failed (%d): %s", image_scale_, src_w, src_h, width, height,
+                rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    ctx_w_ = src_w; ctx_h_ = src_h; ctx_batch_ = max_batch;
+    work_w_ = width; work_h_ = height;
     if (resized) svo_set_pose(ctx_, frame_pose_.m);          // the new context's first frame only initialises; the chain goes on
     return true;
 }
@@ -150,7 +189,7 @@ bool Tracking::AddFrame(Frame::Ptr frame)
     return true;
 }
 
-static bool feed(svo_ctx *ctx, Frame::Ptr f, svo_step_result *res, int *rc_out)
+static bool feed(svo_ctx *ctx, bool ingest, Frame::Ptr f, svo_step_result *res, int *rc_out)
 {
     const cv::Mat &L = f->left_img_, &R = f->right_img_;
     if (L.empty() || R.empty() || L.rows != R.rows || L.cols != R.cols || L.step != R.step) {
@@ -158,7 +197,8 @@ static bool feed(svo_ctx *ctx, Frame::Ptr f, svo_step_result *res, int *rc_out)
         *rc_out = SVO_ERR_ARG;
         return false;
     }
-    *rc_out = svo_add_frame(ctx, L.data, R.data, (int)L.step, SVO_MEM_HOST, res);
+    *rc_out = ingest ? svo_ingest_add_frame(ctx, L.data, R.data, (int)L.step, SVO_MEM_HOST, res)
+                     : svo_add_frame(ctx, L.data, R.data, (int)L.step, SVO_MEM_HOST, res);
     if (*rc_out < 0) LZB_LOG("ERROR", "svo_add_frame: %s", svo_last_error(ctx));
     if (*rc_out == SVO_FAIL_CAPACITY)
         LZB_LOG("ERROR", "frame %lu: more keypoints than the context's capacity (YAML key max_keypoints); "
@@ -227,7 +267,7 @@ bool Tracking::StereoInit_f2f()
     if (!EnsureContext(current_frame_->left_img_.cols, current_frame_->left_img_.rows)) return false;
     svo_reset(ctx_);
     int rc;
-    feed(ctx_, current_frame_, &last_, &rc);
+    feed(ctx_, Ingest(), current_frame_, &last_, &rc);
     FillFeatures();
     last_frame_ = current_frame_;
     status_ = TrackingStatus::TRACKING_GOOD;
@@ -249,7 +289,7 @@ bool Tracking::TrackOnGpu()
 {
     if (!EnsureContext(current_frame_->left_img_.cols, current_frame_->left_img_.rows)) return false;
     int rc;
-    bool ok = feed(ctx_, current_frame_, &last_, &rc);
+    bool ok = feed(ctx_, Ingest(), current_frame_, &last_, &rc);
     if (rc < 0) return false;
     FillFeatures();
     if (ok) {

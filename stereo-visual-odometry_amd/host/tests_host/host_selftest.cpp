@@ -183,6 +183,14 @@ int main(int argc, char **argv)
     printf("nFeatures=%d fScaleFactor=%.2f nLevels=%d fIniThFAST=%d fMinThFAST=%d\n", p.nFeatures_,
            p.fScaleFactor_, p.nLevels_, p.fIniThFAST_, p.fMinThFAST_);
     printf("missing=%d\n", lzb_vio::Config::Get<int>("no_such_key"));
+    {
+        // additive keys image_scale / image_interp as Tracking reads them: ingest=1 means an ingest stage will be created
+        double scale; int interp; std::string err;
+        const bool ok = lzb_vio::Tracking::ReadImageScale(&scale, &interp, &err);
+        printf("image_scale_ok=%d\nimage_scale=%.17g\nimage_interp=%s\ningest=%d\n", ok ? 1 : 0, scale,
+               interp == SVO_INTERP_LINEAR ? "linear" : "nearest", ok && scale < 1.0 ? 1 : 0);
+        if (!ok) printf("image_scale_error=%s\n", err.c_str());
+    }
     for (int i = 2; i < argc; i++) {
         cv::Mat m;
         bool ok = lzb_vio::ReadImageGray(argv[i], m);
