@@ -436,6 +436,41 @@ int svo_ingest_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, cons
 int svo_ingest_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *lefts, const uint8_t *rights,
                                 int pitch, int64_t frame_stride, int n_frames);
 
+/* ---- FAST corner buckets: the strongest corners per grid cell before LK tracking (additive; detected by symbol, the ABI
+ * version stays 9 and svo_config is unchanged) ---------------------------------------------------------------------------
+ * The LK step's cost is proportional to the corners it is handed, and cv::FAST is uncapped (src/tracking.cpp:94-113).
+ * svo_config.fast_keep_strongest bounds the count but not where the corners lie; the reference's author asked for spacing
+ * too (cv::GFTTDetector::create(n, 0.01, 20) at src/tracking.cpp:18, never called).  Bucketing keeps coverage of the image:
+ *
+ * Semantics.  A grid of cell_w x cell_h pixel cells anchored at (0, 0): ceil(w / cell_w) x ceil(h / cell_h) cells, edge
+ * cells may be partial; a corner at integer (x, y) belongs to cell (y / cell_h) * cols + x / cell_w.  Per image and per cell
+ * the per_cell corners of highest response stay (ties: raster order first); the survivors stay in raster order with their
+ * responses intact -- np.argsort(-response, kind="stable")[:per_cell] per cell, then a sort of the kept indices.  At most
+ * 16384 cells per image.
+ *   svo_set_fast_buckets : LK mode, fused entry points only (svo_add_frame, svo_track_batch, svo_track_uploaded(_async),
+ *       svo_streams_step and their svo_ingest_* twins).  per_cell = 0 (the default): off, the sizes are ignored.  May be
+ *       called at any time between calls on the context and applies to frames whose corners are detected by LATER calls: a
+ *       frame already detected (svo_add_frame's previous frame, a stream's stored frame, a carried frame) keeps its corners.
+ *       svo_config.fast_keep_strongest = N > 0 runs AFTER the buckets, on their survivors.  n_prev_kps / n_cur_kps, the
+ *       < 30 gate, svo_get_frame_keypoints and the tracks read-backs see the kept set, as with fast_keep_strongest; a frame
+ *       whose RAW corner count exceeds max_keypoints is left alone and still ends in SVO_FAIL_CAPACITY.  SVO_ERR_ARG:
+ *       cell_w < 1, cell_h < 1, per_cell < 0, more than 16384 cells at the context's size, an ORB-mode context (ORB mode
+ *       spreads its keypoints with the quadtree).  Grids of more than 3072 cells keep their per-cell words in device memory
+ *       (16 bytes x cells x (max_batch + 1)), allocated by the call that first asks for such a grid (that call waits for the
+ *       device); a context that never enables buckets allocates and pays nothing.
+ *   svo_get_fast_buckets : what is set (0, 0, 0 while off).  Any pointer may be NULL.
+ *   svo_bucket_corners (stage API): the same kernel on a caller's list -- any raster-ordered list of n records with integer
+ *       coordinates inside width x height and responses in 1..255 --, independent of the context's frame size and mode.
+ *       out receives the survivors as the records cv::FAST makes (x, y, response of the input; size 7, angle -1, octave 0,
+ *       class_id -1), *n_out their count.  `mem` says where in, out AND n_out live; SVO_MEM_DEVICE: in stream order on the
+ *       context's stream, no host synchronisation (device scratch of 12 bytes per corner grows on demand; a call that grows
+ *       it waits for the device); SVO_MEM_HOST: returns when out is complete.  in == out is allowed.  SVO_ERR_ARG: n > cap,
+ *       per_cell < 1, a size < 1 or > 16384, more than 16384 cells. */
+int svo_set_fast_buckets(svo_ctx *ctx, int cell_w, int cell_h, int per_cell);
+int svo_get_fast_buckets(const svo_ctx *ctx, int *cell_w, int *cell_h, int *per_cell);
+int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, int width, int height,
+                       int cell_w, int cell_h, int per_cell, svo_keypoint *out, int cap, int *n_out, int mem);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

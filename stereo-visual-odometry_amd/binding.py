@@ -130,6 +130,11 @@ def load_library():
     lib.svo_ingest_track_batch.argtypes = lib.svo_track_batch.argtypes
     lib.svo_ingest_streams_step.argtypes = lib.svo_streams_step.argtypes
     lib.svo_ingest_upload_frames_at.argtypes = lib.svo_upload_frames_at.argtypes
+    # FAST corner buckets (additive entry points, like the stream sets)
+    lib.svo_set_fast_buckets.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.svo_get_fast_buckets.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.svo_bucket_corners.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     _LIB = lib
     return lib
 
@@ -435,6 +440,46 @@ class Context:
         if mem == MEM_DEVICE:
             self._order_out(dist)
         return idx[:len(query)], dist[:len(query)]
+
+    # ---- FAST corner buckets (svo_set_fast_buckets / svo_bucket_corners) ---------------------------
+    def set_fast_buckets(self, cell_w, cell_h, per_cell):
+        """LK mode: keep the per_cell strongest FAST corners of every cell_w x cell_h pixel cell of the frames detected by
+        later calls (per_cell = 0: off, the default).  fast_keep_strongest, if set, runs on the survivors."""
+        self._check(self.lib.svo_set_fast_buckets(self.h, int(cell_w), int(cell_h), int(per_cell)))
+
+    def fast_buckets(self):
+        """(cell_w, cell_h, per_cell) as set; (0, 0, 0) while off."""
+        cw, ch, k = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.svo_get_fast_buckets(self.h, C.byref(cw), C.byref(ch), C.byref(k)))
+        return cw.value, ch.value, k.value
+
+    def bucket_corners(self, kps, width, height, cell_w, cell_h, per_cell, cap=None):
+        """svo_bucket_corners on a raster-ordered corner list: a numpy KP_DTYPE array (returns the kept records), or a cuda
+        uint8 tensor of n * KP_DTYPE.itemsize bytes (returns (records tensor of the same size, int32 count tensor), both
+        filled in stream order without a host synchronisation)."""
+        if isinstance(kps, np.ndarray):
+            kps = np.ascontiguousarray(kps, KP_DTYPE)
+            n = int(kps.shape[0])
+            cap = n if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=KP_DTYPE)
+            m = C.c_int(0)
+            self._check(self.lib.svo_bucket_corners(self.h, C.c_void_p(kps.ctypes.data), n, int(width), int(height), int(cell_w),
+                                                    int(cell_h), int(per_cell), C.c_void_p(out.ctypes.data), cap,
+                                                    C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+            return out[:m.value].copy()
+        import torch
+        assert kps.is_cuda and kps.is_contiguous() and kps.element_size() == 1 and kps.numel() % KP_DTYPE.itemsize == 0
+        n = kps.numel() // KP_DTYPE.itemsize
+        cap = n if cap is None else int(cap)
+        out = torch.zeros(max(cap, 1) * KP_DTYPE.itemsize, dtype=torch.uint8, device=kps.device)
+        m = torch.zeros(1, dtype=torch.int32, device=kps.device)
+        ordered = self._order_in(out)
+        self._check(self.lib.svo_bucket_corners(self.h, C.c_void_p(kps.data_ptr()), n, int(width), int(height), int(cell_w),
+                                                int(cell_h), int(per_cell), C.c_void_p(out.data_ptr()), cap,
+                                                C.c_void_p(m.data_ptr()), MEM_DEVICE))
+        if ordered:
+            self._order_out(out)
+        return out, m
 
     # ---- cv::resize and the ingest stage (svo_resize / svo_ingest_*) -------------------------------
     def resize(self, src, dw, dh, interp="nearest", fx=0, fy=0, out=None):

@@ -336,6 +336,167 @@ void launch_fast_keep_strongest(const FastArgs &a, int batch, int keep, hipStrea
     hipLaunchKernelGGL(fast_keep_strongest_kernel, dim3(batch), dim3(1024), 0, st, a, keep);
 }
 
+// svo_set_fast_buckets / svo_bucket_corners: keeps, in every cell of a grid of cw x ch pixel cells anchored at (0, 0), the
+// `per_cell` highest-response corners -- ties by raster order, i.e. np.argsort(-response, kind="stable")[:per_cell] per cell --
+// IN PLACE and in raster order.  One workgroup per image; every pass walks the list in chunks of 1024 and costs O(n):
+//   A  8 passes : the cut-off response t of every cell, built bit by bit from the top: t | bit stays when the cell has at
+//                 least per_cell corners with response >= t | bit.  t = the largest value with #(response >= t) >= per_cell,
+//                 0 for a cell that holds fewer than per_cell corners (every corner of it is above 0);
+//   B  1 pass   : need = per_cell - #(response > t): how many of the corners AT t the cell still takes;
+//   C  ceil(log2(n + 1)) passes : the list index `cut` below which a corner AT t is taken, built bit by bit like t:
+//                 cut | bit stays when at most `need` of the cell's corners at t lie below it.  A corner at t with index i has
+//                 #(same cell, at t, before i) < need  <=>  i < cut, so which corner survives is decided by integer COUNTS
+//                 only -- no rank ever depends on the order in which atomics land;
+//   D  1 pass   : keep = response > t || (response == t && i < cut), decided for a whole chunk from the untouched per-cell
+//                 words before the chunk is written; write positions never overtake the reads (fast_keep_strongest_kernel).
+// Per-cell state: 4 ints (count, t, need, cut), in LDS up to kBucketLdsCells cells, else in device memory (a.cells).
+// The lists are raster ordered, so the corners of one cell in one image row are neighbours in the list: a wave adds a run
+// of equal cells with ONE atomic (heads found with a shuffle and two ballots).
+constexpr int kBucketLdsCells = 3072;                    // 48 KB of LDS
+
+__device__ __forceinline__ void bucket_count(int *cnt, int cell, bool flag)
+{
+    const int lane = threadIdx.x & 63;
+    const int prev = __shfl_up(cell, 1);
+    const bool head = lane == 0 || prev != cell;
+    const unsigned long long H = __ballot(head), F = __ballot(flag);
+    if (head && cell >= 0) {
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long after = lane == 63 ? 0ull : H & ~(below | (1ull << lane));
+        const unsigned long long upto = after ? (1ull << (__ffsll((long long)after) - 1)) - 1ull : ~0ull;   // lanes before the next head
+        const int c = __popcll(F & upto & ~below);
+        if (c) atomicAdd(&cnt[4 * cell], c);
+    }
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(1024) void fast_bucket_kernel(BucketArgs a)
+{
+    __shared__ int lds_cells[kLds ? 4 * kBucketLdsCells : 4];
+    __shared__ int wave_kp[16];
+    __shared__ int s_out_base;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = a.n_out[b];
+    if (n <= a.per_cell || n > a.cap) return;    // no cell can lose a corner / over capacity: the list is left alone (SVO_FAIL_CAPACITY)
+    float2 *xy = a.kp_xy + (int64_t)b * a.kp_stride;
+    float *resp = a.kp_resp + (int64_t)b * a.kp_stride;
+    int *cs = kLds ? lds_cells : a.cells + (int64_t)b * a.cells_stride;       // [cell][count, t, need, cut]
+    const int ncells = a.ncells;
+    for (int c = tid; c < 4 * ncells; c += 1024) cs[c] = 0;
+    __syncthreads();
+    // a cell's count after a pass (device memory: the adds were made in L2, so the read goes there too)
+    auto count_of = [&](int c) -> int { return kLds ? cs[4 * c] : __hip_atomic_load(&cs[4 * c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    // (cell, response) of list entry i; -1 beyond the list.  Coordinates are clamped into the image: a caller's list that
+    // breaks the contract lands in an edge cell, never outside the per-cell words.
+    auto entry = [&](int i, int *r) -> int {
+        if (i >= n) { *r = 0; return -1; }
+        const float2 p = xy[i];
+        *r = min(255, max(0, (int)resp[i]));
+        const unsigned x = (unsigned)min(a.w - 1, max(0, (int)p.x)), y = (unsigned)min(a.h - 1, max(0, (int)p.y));
+        return (int)((y / (unsigned)a.ch) * (unsigned)a.cols + x / (unsigned)a.cw);
+    };
+    // A: cut-off response per cell
+    for (int bit = 128; bit > 0; bit >>= 1) {
+        for (int start = 0; start < n; start += 1024) {
+            int r;
+            const int cell = entry(start + tid, &r);
+            bucket_count(cs, cell, cell >= 0 && r >= (cs[4 * cell + 1] | bit));
+        }
+        __syncthreads();
+        for (int c = tid; c < ncells; c += 1024) {
+            if (count_of(c) >= a.per_cell) cs[4 * c + 1] |= bit;
+            cs[4 * c] = 0;
+        }
+        __syncthreads();
+    }
+    // B: corners strictly above the cut-off
+    for (int start = 0; start < n; start += 1024) {
+        int r;
+        const int cell = entry(start + tid, &r);
+        bucket_count(cs, cell, cell >= 0 && r > cs[4 * cell + 1]);
+    }
+    __syncthreads();
+    for (int c = tid; c < ncells; c += 1024) {
+        cs[4 * c + 2] = a.per_cell - count_of(c);
+        cs[4 * c] = 0;
+    }
+    __syncthreads();
+    // C: list index below which a corner AT the cut-off is taken
+    for (int bit = 1 << (31 - __clz(n)); bit > 0; bit >>= 1) {
+        for (int start = 0; start < n; start += 1024) {
+            int r;
+            const int i = start + tid;
+            const int cell = entry(i, &r);
+            bucket_count(cs, cell, cell >= 0 && r == cs[4 * cell + 1] && i < (cs[4 * cell + 3] | bit));
+        }
+        __syncthreads();
+        for (int c = tid; c < ncells; c += 1024) {
+            if (count_of(c) <= cs[4 * c + 2]) cs[4 * c + 3] |= bit;
+            cs[4 * c] = 0;
+        }
+        __syncthreads();
+    }
+    // D: stable compaction
+    if (tid == 0) s_out_base = 0;
+    __syncthreads();
+    for (int start = 0; start < n; start += 1024) {
+        const int i = start + tid;
+        const bool in = i < n;
+        const float2 p = in ? xy[i] : make_float2(0.f, 0.f);
+        const float rf = in ? resp[i] : 0.f;
+        int r;
+        const int cell = entry(i, &r);
+        const bool kp = in && (r > cs[4 * cell + 1] || (r == cs[4 * cell + 1] && i < cs[4 * cell + 3]));
+        const unsigned long long mk = __ballot(kp);
+        if (lane == 0) wave_kp[wv] = __popcll(mk);
+        __syncthreads();
+        int kp_pre = s_out_base, kp_tot = 0;
+        for (int q = 0; q < 16; q++) { const int c = wave_kp[q]; if (q < wv) kp_pre += c; kp_tot += c; }
+        if (kp) {
+            const int dst = kp_pre + __popcll(mk & ((1ull << lane) - 1ull));
+            xy[dst] = p; resp[dst] = rf;
+        }
+        __syncthreads();
+        if (tid == 0) s_out_base += kp_tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.n_out[b] = s_out_base;
+}
+
+void launch_fast_buckets(const BucketArgs &a, int batch, hipStream_t st)
+{
+    if (a.per_cell <= 0 || batch <= 0) return;
+    if (a.ncells <= kBucketLdsCells) hipLaunchKernelGGL(fast_bucket_kernel<true>, dim3(batch), dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL(fast_bucket_kernel<false>, dim3(batch), dim3(1024), 0, st, a);
+}
+int fast_bucket_lds_cells() { return kBucketLdsCells; }
+
+// svo_bucket_corners: cv::KeyPoint records <-> the structure-of-arrays lists the selection works on
+__global__ __launch_bounds__(256) void bucket_unpack_kernel(const svo_keypoint *in, int n, float2 *xy, float *resp, int *n_dev)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *n_dev = n;
+    if (i < n) { xy[i] = make_float2(in[i].x, in[i].y); resp[i] = in[i].response; }
+}
+__global__ __launch_bounds__(256) void bucket_pack_kernel(const float2 *xy, const float *resp, const int *n_dev, svo_keypoint *out, int *n_out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, n = *n_dev;
+    if (i == 0) *n_out = n;
+    if (i < n) {                               // the cv::KeyPoint cv::FAST produces
+        svo_keypoint k;
+        k.x = xy[i].x; k.y = xy[i].y; k.size = 7.f; k.angle = -1.f; k.response = resp[i]; k.octave = 0; k.class_id = -1;
+        out[i] = k;
+    }
+}
+void launch_bucket_unpack(const svo_keypoint *in, int n, float2 *xy, float *resp, int *n_dev, hipStream_t st)
+{
+    hipLaunchKernelGGL(bucket_unpack_kernel, dim3(n / 256 + 1), dim3(256), 0, st, in, n, xy, resp, n_dev);
+}
+void launch_bucket_pack(const float2 *xy, const float *resp, const int *n_dev, int n_max, svo_keypoint *out, int *n_out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bucket_pack_kernel, dim3(n_max / 256 + 1), dim3(256), 0, st, xy, resp, n_dev, out, n_out);
+}
+
 void launch_fast(const FastArgs &a, int batch, hipStream_t st)
 {
     (void)hipMemsetAsync(a.rowcount, 0, sizeof(int) * (size_t)a.rowcount_stride * batch, st);

@@ -62,6 +62,16 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
     a.kp_stride = ctx->cfg.max_keypoints;
     a.n_out = ctx->kp_n + f0; a.cap = ctx->cfg.max_keypoints;
     launch_fast(a, n_new, ctx->stream);
+    if (ctx->bucket_keep > 0) {
+        // svo_set_fast_buckets: the strongest corners per grid cell, before the global top-N
+        BucketArgs k{};
+        k.kp_xy = a.kp_xy; k.kp_resp = a.kp_resp; k.kp_stride = a.kp_stride; k.n_out = a.n_out; k.cap = a.cap;
+        k.w = a.w; k.h = a.h; k.cw = ctx->bucket_w; k.ch = ctx->bucket_h; k.per_cell = ctx->bucket_keep;
+        k.cols = (a.w + k.cw - 1) / k.cw; k.ncells = k.cols * ((a.h + k.ch - 1) / k.ch);
+        k.cells_stride = (int64_t)4 * k.ncells;
+        k.cells = ctx->bucket_cells ? ctx->bucket_cells + (size_t)f0 * k.cells_stride : nullptr;
+        launch_fast_buckets(k, n_new, ctx->stream);
+    }
     launch_fast_keep_strongest(a, n_new, ctx->cfg.fast_keep_strongest, ctx->stream);
     mark(ctx, kTFast);
     return SVO_OK;

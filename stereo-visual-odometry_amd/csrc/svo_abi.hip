@@ -151,6 +151,8 @@ static void free_all(svo_ctx *c)
     dev_release(c);                                   // every device buffer: the arena + the lazy extras
     for (int k = 0; k < 2; k++) if (c->resize_scratch[k]) (void)hipFree(c->resize_scratch[k]);
     if (c->ingest.src_stage) (void)hipFree(c->ingest.src_stage);
+    if (c->bucket_cells) (void)hipFree(c->bucket_cells);
+    if (c->bucket_stage) (void)hipFree(c->bucket_stage);
     if (c->ev_front) (void)hipEventDestroy(c->ev_front);
     if (c->ev_back) (void)hipEventDestroy(c->ev_back);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -1371,5 +1373,100 @@ extern "C" int svo_get_last_tracks(svo_ctx *ctx, svo_pt2f *t1_left, svo_pt2f *t1
     }
     if (inlier) SVO_HIP(hipMemcpyAsync(inlier, pnp_inlier_mask(ctx), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SVO_HIP(hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
+// ---- FAST corner buckets: the strongest corners per grid cell (fast.hip: fast_bucket_kernel) -------------------------
+static const int kMaxBucketCells = 16384;
+
+static int64_t bucket_cell_count(int w, int h, int cw, int ch)
+{
+    return (int64_t)((w + cw - 1) / cw) * ((h + ch - 1) / ch);
+}
+
+extern "C" int svo_set_fast_buckets(svo_ctx *ctx, int cell_w, int cell_h, int per_cell)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(per_cell >= 0, "per_cell < 0");
+    if (per_cell == 0) { ctx->bucket_keep = 0; return SVO_OK; }      // off: the sizes are ignored
+    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "FAST buckets are an LK-mode option (ORB mode spreads its keypoints with the quadtree)");
+    SVO_ARG(cell_w >= 1 && cell_h >= 1, "cell_w / cell_h < 1");
+    const int64_t ncells = bucket_cell_count(ctx->cfg.width, ctx->cfg.height, cell_w, cell_h);
+    SVO_ARG(ncells <= kMaxBucketCells, "more than 16384 cells per image");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (ncells > fast_bucket_lds_cells()) {
+        // the per-cell words of such a grid live in device memory: every image slot of the context its own
+        const size_t bytes = sizeof(int) * 4 * (size_t)ncells * (size_t)ctx->n_img;
+        if (bytes > ctx->bucket_cells_bytes) {
+            if (ctx->bucket_cells) SVO_HIP(hipFree(ctx->bucket_cells));      // (waits for the launches that still use it)
+            ctx->bucket_cells = nullptr; ctx->bucket_cells_bytes = 0;
+            ctx->bucket_keep = 0;
+            SVO_HIP(hipMalloc((void **)&ctx->bucket_cells, bytes));
+            ctx->bucket_cells_bytes = bytes;
+        }
+    }
+    ctx->bucket_w = cell_w; ctx->bucket_h = cell_h; ctx->bucket_keep = per_cell;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_fast_buckets(const svo_ctx *ctx, int *cell_w, int *cell_h, int *per_cell)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (cell_w) *cell_w = ctx->bucket_keep > 0 ? ctx->bucket_w : 0;
+    if (cell_h) *cell_h = ctx->bucket_keep > 0 ? ctx->bucket_h : 0;
+    if (per_cell) *per_cell = ctx->bucket_keep;
+    return SVO_OK;
+}
+
+extern "C" int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, int width, int height, int cell_w, int cell_h,
+                                  int per_cell, svo_keypoint *out, int cap, int *n_out, int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(n >= 0 && n <= (1 << 24) && (in || n == 0) && (out || n == 0) && n_out, "null pointer / bad n");
+    SVO_ARG(n <= cap, "n > cap");
+    SVO_ARG(width >= 1 && height >= 1 && width <= 16384 && height <= 16384, "width / height out of range");
+    SVO_ARG(cell_w >= 1 && cell_h >= 1 && per_cell >= 1, "cell_w / cell_h / per_cell < 1");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "mem must be SVO_MEM_HOST or SVO_MEM_DEVICE");
+    const int64_t ncells = bucket_cell_count(width, height, cell_w, cell_h);
+    SVO_ARG(ncells <= kMaxBucketCells, "more than 16384 cells");
+    SVO_HIP(hipSetDevice(ctx->device));
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const bool host = mem == SVO_MEM_HOST, dev_cells = ncells > fast_bucket_lds_cells();
+    const size_t o_xy = 256, o_resp = o_xy + up(sizeof(float2) * (size_t)n), o_cells = o_resp + up(sizeof(float) * (size_t)n),
+                 o_in = o_cells + (dev_cells ? up(sizeof(int) * 4 * (size_t)ncells) : 0),
+                 o_out = o_in + (host ? up(sizeof(svo_keypoint) * (size_t)n) : 0),
+                 bytes = o_out + (host ? up(sizeof(svo_keypoint) * (size_t)n) : 0);
+    if (bytes > ctx->bucket_stage_bytes) {
+        if (ctx->bucket_stage) SVO_HIP(hipFree(ctx->bucket_stage));
+        ctx->bucket_stage = nullptr; ctx->bucket_stage_bytes = 0;
+        SVO_HIP(hipMalloc((void **)&ctx->bucket_stage, bytes));
+        ctx->bucket_stage_bytes = bytes;
+    }
+    uint8_t *s = ctx->bucket_stage;
+    int *d_n = (int *)s, *d_nout = host ? (int *)s + 1 : n_out;
+    float2 *xy = (float2 *)(s + o_xy);
+    float *resp = (float *)(s + o_resp);
+    const svo_keypoint *d_in = host ? (const svo_keypoint *)(s + o_in) : in;
+    svo_keypoint *d_out = host ? (svo_keypoint *)(s + o_out) : out;
+    if (host && n > 0) SVO_HIP(hipMemcpyAsync((void *)d_in, in, sizeof(svo_keypoint) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    launch_bucket_unpack(d_in, n, xy, resp, d_n, ctx->stream);
+    BucketArgs k{};
+    k.kp_xy = xy; k.kp_resp = resp; k.kp_stride = 0; k.n_out = d_n; k.cap = n;
+    k.w = width; k.h = height; k.cw = cell_w; k.ch = cell_h; k.per_cell = per_cell;
+    k.cols = (width + cell_w - 1) / cell_w; k.ncells = (int)ncells;
+    k.cells = dev_cells ? (int *)(s + o_cells) : nullptr; k.cells_stride = 0;
+    launch_fast_buckets(k, 1, ctx->stream);
+    launch_bucket_pack(xy, resp, d_n, n, d_out, d_nout, ctx->stream);
+    SVO_HIP(hipGetLastError());
+    if (!host) return SVO_OK;
+    int *h_n = (int *)ctx->h_pinned;
+    SVO_HIP(hipMemcpyAsync(h_n, d_nout, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    const int m = *h_n;
+    *n_out = m;
+    if (m > 0) {
+        SVO_HIP(hipMemcpyAsync(out, d_out, sizeof(svo_keypoint) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        SVO_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return SVO_OK;
 }

@@ -151,6 +151,12 @@ struct svo_ctx {
     uint8_t *resize_scratch[2] = {nullptr, nullptr};     // device copies of svo_resize's HOST source / destination
     size_t resize_scratch_bytes[2] = {0, 0};
     Ingest ingest;
+    // ---- FAST corner buckets (svo_set_fast_buckets; off and nothing allocated until then)
+    int bucket_w = 0, bucket_h = 0, bucket_keep = 0;     // cell size in pixels, corners kept per cell (0: off)
+    int *bucket_cells = nullptr;                         // per-cell words of grids too large for LDS: 4 ints x cells x n_img
+    size_t bucket_cells_bytes = 0;
+    uint8_t *bucket_stage = nullptr;                     // svo_bucket_corners: the caller's list as structure of arrays (+ its cells)
+    size_t bucket_stage_bytes = 0;
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing

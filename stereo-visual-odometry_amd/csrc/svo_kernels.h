@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svo_device.h"
+#include "../../include/svo_abi.h"
 
 namespace svo {
 
@@ -19,6 +20,18 @@ struct FastArgs {
 void launch_fast(const FastArgs &a, int batch, hipStream_t st);
 // svo_config.fast_keep_strongest: in-place selection of the `keep` highest-response corners per image, raster order kept
 void launch_fast_keep_strongest(const FastArgs &a, int batch, int keep, hipStream_t st);
+// svo_set_fast_buckets / svo_bucket_corners: in-place selection of the `per_cell` highest-response corners of every cell of a
+// grid of cw x ch pixel cells (cols per row, ncells in all), raster order kept; one launch for the batch
+struct BucketArgs {
+    float2 *kp_xy; float *kp_resp; int64_t kp_stride;      // the lists fast_emit_kernel writes, `cap` entries per image
+    int *n_out; int cap;                                   // corners per image; a list longer than cap is left alone
+    int w, h, cw, ch, cols, ncells, per_cell;
+    int *cells; int64_t cells_stride;                      // 4 ints per cell and image; only read when ncells > fast_bucket_lds_cells()
+};
+void launch_fast_buckets(const BucketArgs &a, int batch, hipStream_t st);
+int fast_bucket_lds_cells();
+void launch_bucket_unpack(const svo_keypoint *in, int n, float2 *xy, float *resp, int *n_dev, hipStream_t st);
+void launch_bucket_pack(const float2 *xy, const float *resp, const int *n_dev, int n_max, svo_keypoint *out, int *n_out, hipStream_t st);
 
 // ---- LK pyramid (pyramid.hip) ---------------------------------------------------------------
 struct PyrArgs {

@@ -50,6 +50,11 @@ public:
     // names the key); ConfigError() is that message for this object's YAML (empty: fine).
     static bool ReadImageScale(double *scale, int *interp, std::string *err);
     const std::string &ConfigError() const { return config_error_; }
+    // additive YAML keys fast_bucket_width / fast_bucket_height / fast_bucket_keep (svo_set_fast_buckets, include/svo_abi.h): LK
+    // mode keeps the fast_bucket_keep strongest FAST corners of every width x height pixel cell.  All absent (or keep 0): off.
+    // ReadFastBuckets reads and checks them for the loaded YAML: a keep value without both sizes, a size < 1, a negative keep
+    // or ORB mode with keep > 0 is refused (false + a message that names the key).  The keys are applied right after svo_create.
+    static bool ReadFastBuckets(int *cell_w, int *cell_h, int *keep, std::string *err);
     bool Ingest() const { return image_scale_ < 1.0; }
     double ImageScale() const { return image_scale_; }
     int ImageInterp() const { return image_interp_; }
@@ -96,6 +101,7 @@ private:
     int device_ = 0;
     long max_keypoints_key_ = 0;                             // additive YAML key max_keypoints, read once (0 = absent)
     int fast_keep_strongest_ = 0;                            // additive YAML key fast_keep_strongest (0 = every corner)
+    int bucket_w_ = 0, bucket_h_ = 0, bucket_keep_ = 0;      // additive YAML keys fast_bucket_width / _height / _keep (keep 0 = off)
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128
     double image_scale_ = 1.0;                               // additive YAML key image_scale (1 = no ingest stage)
     int image_interp_ = SVO_INTERP_NEAREST;                  // additive YAML key image_interp: nearest (default) | linear

@@ -152,6 +152,9 @@ int RunInterleaved(const std::vector<std::string> &yamls, const std::vector<std:
         // image_scale / image_interp are shared keys like every other (compared above); their values are checked here
         double scale; int interp; std::string err;
         if (!Tracking::ReadImageScale(&scale, &interp, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
+        // ... and so are fast_bucket_width / fast_bucket_height / fast_bucket_keep
+        int cw, ch, keep;
+        if (!Tracking::ReadFastBuckets(&cw, &ch, &keep, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
     }
     for (int s = 0; s < n; s++) {
         cv::Mat l, r;

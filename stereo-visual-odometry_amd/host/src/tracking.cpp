@@ -27,6 +27,26 @@ bool Tracking::ReadImageScale(double *scale, int *interp, std::string *err)
     return true;
 }
 
+bool Tracking::ReadFastBuckets(int *cell_w, int *cell_h, int *keep, std::string *err)
+{
+    *cell_w = *cell_h = *keep = 0;
+    const bool has_w = Config::Has("fast_bucket_width"), has_h = Config::Has("fast_bucket_height");
+    const int w = has_w ? Config::Get<int>("fast_bucket_width") : 0, h = has_h ? Config::Get<int>("fast_bucket_height") : 0;
+    const int k = Config::Has("fast_bucket_keep") ? Config::Get<int>("fast_bucket_keep") : 0;
+    char msg[200] = "";
+    if (has_w && w < 1) snprintf(msg, sizeof(msg), "fast_bucket_width: %d is < 1 (the cell width in pixels)", w);
+    else if (has_h && h < 1) snprintf(msg, sizeof(msg), "fast_bucket_height: %d is < 1 (the cell height in pixels)", h);
+    else if (k < 0) snprintf(msg, sizeof(msg), "fast_bucket_keep: %d is < 0 (corners kept per cell; 0 = off)", k);
+    else if (k > 0 && !(has_w && has_h))
+        snprintf(msg, sizeof(msg), "fast_bucket_keep: %d needs the cell size: %s is absent", k, has_w ? "fast_bucket_height" : "fast_bucket_width");
+    else if (k > 0 && Config::Has("track_mode") && Config::Get<std::string>("track_mode") == "ORB_stereof2f_pnp")
+        snprintf(msg, sizeof(msg), "fast_bucket_keep: %d with track_mode ORB_stereof2f_pnp (buckets are an LK-mode option; ORB mode "
+                                   "spreads its keypoints with the quadtree)", k);
+    if (msg[0]) { if (err) *err = msg; return false; }
+    if (k > 0) { *cell_w = w; *cell_h = h; *keep = k; }
+    return true;
+}
+
 Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensors)
 {
     sensors_ = sensors;
@@ -50,6 +70,8 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
         else if (v != "exact") LZB_LOG("WARNING", "lk_accum: '%s' is none of 'exact', 'sse2', 'simd128', 'sse2_legacy'; using 'exact'", v.c_str());
     }
     if (!ReadImageScale(&image_scale_, &image_interp_, &config_error_)) image_scale_ = 1.0;     // the owner refuses to run (ConfigError)
+    std::string bucket_error;
+    if (!ReadFastBuckets(&bucket_w_, &bucket_h_, &bucket_keep_, &bucket_error) && config_error_.empty()) config_error_ = bucket_error;
 }
 
 Tracking::~Tracking()
@@ -161,6 +183,13 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
     if (Ingest() && (rc = svo_ingest_create(ctx_, src_w, src_h, image_interp_, image_scale_, image_scale_)) != SVO_OK) {
         LZB_LOG("ERROR", "svo_ingest_create (image_scale %g, %dx%d -> %dx%d) failed (%d): %s", image_scale_, src_w, src_h, width, height,
                 rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    if (bucket_keep_ > 0 && (rc = svo_set_fast_buckets(ctx_, bucket_w_, bucket_h_, bucket_keep_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_fast_buckets (fast_bucket_width %d, fast_bucket_height %d, fast_bucket_keep %d at %dx%d) failed (%d): %s",
+                bucket_w_, bucket_h_, bucket_keep_, width, height, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;
