@@ -192,6 +192,21 @@ def _ptr(a):
     return C.c_void_p(a.data_ptr()), (MEM_DEVICE if a.is_cuda else MEM_HOST)
 
 
+def _pose_ptr(pose0):
+    """Pointer to the 16 doubles of a pose (it keeps its array alive), or None."""
+    if pose0 is None:
+        return None
+    return np.ascontiguousarray(pose0, np.float64).reshape(16).ctypes.data_as(C.c_void_p)
+
+
+def _records(n, results):
+    """(out object, pointer, memory kind) of n step records: a fresh host array, or the caller's cuda tensor."""
+    if results is None:
+        out = np.zeros(n, dtype=STEP_DTYPE)
+        return out, C.c_void_p(out.ctypes.data), MEM_HOST
+    return results, C.c_void_p(results.data_ptr()), MEM_DEVICE
+
+
 class Context:
     """One svo_ctx: owns every device buffer of the hot path on one GPU."""
 
@@ -284,9 +299,11 @@ class Context:
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
 
     # ---- stage API --------------------------------------------------------------------------
-    def _img(self, img):
-        """(pointer, row pitch in bytes, memory kind) of a u8 image; rows may be padded (pitch >= width)."""
-        assert tuple(img.shape) == (self.height, self.width), (img.shape, self.height, self.width)
+    def _img(self, img, shape=None):
+        """(pointer, row pitch in bytes, memory kind) of a u8 image of the context's size (or of `shape`); rows may be padded
+        (pitch >= width)."""
+        shape = shape or (self.height, self.width)
+        assert tuple(img.shape) == tuple(shape), (tuple(img.shape), shape)
         if isinstance(img, np.ndarray):
             assert img.dtype == np.uint8 and img.strides[1] == 1
             return C.c_void_p(img.ctypes.data), int(img.strides[0]), MEM_HOST
@@ -534,96 +551,40 @@ class Context:
         """The frame shape the ingest calls assert against (before ingest_create: the library answers SVO_ERR_STATE)."""
         return (getattr(self, "src_height", self.height), getattr(self, "src_width", self.width))
 
-    def _src_img(self, img):
-        assert tuple(img.shape) == self._src_shape(), (tuple(img.shape), self._src_shape())
-        if isinstance(img, np.ndarray):
-            assert img.dtype == np.uint8 and img.strides[1] == 1
-            return C.c_void_p(img.ctypes.data), int(img.strides[0]), MEM_HOST
-        assert img.element_size() == 1 and img.stride(1) == 1
-        return C.c_void_p(img.data_ptr()), int(img.stride(0)), (MEM_DEVICE if img.is_cuda else MEM_HOST)
-
     def ingest_add_frame(self, left, right):
         """add_frame on source-size frames (svo_ingest_add_frame)."""
-        pl, pitch, mem = self._src_img(left)
-        pr, pitch_r, mem_r = self._src_img(right)
-        assert pitch == pitch_r and mem == mem_r
-        res = StepResult()
-        if mem == MEM_DEVICE:
-            self._order_in(left)           # as add_frame: the call returns after everything that reads the frames
-        rc = self._check(self.lib.svo_ingest_add_frame(self.h, pl, pr, pitch, mem, C.byref(res)), allow_soft=True)
-        return rc, np.frombuffer(bytes(res), dtype=STEP_DTYPE)[0].copy()
+        return self._add_frame(self.lib.svo_ingest_add_frame, self._src_shape(), left, right)
 
     def ingest_track_batch(self, left_frames, right_frames, pose0=None, results=None):
-        """track_batch on source-size frames: torch cuda uint8 tensors (F, src_height, src_width), rows may be padded."""
-        F = left_frames.shape[0]
-        assert left_frames.is_cuda and right_frames.is_cuda
-        assert tuple(left_frames.shape[1:]) == self._src_shape() and left_frames.shape == right_frames.shape
-        assert left_frames.stride(2) == 1 and left_frames.stride() == right_frames.stride()
-        pitch, fstride = left_frames.stride(1), left_frames.stride(0)
-        p0 = None
-        if pose0 is not None:
-            pose0 = np.ascontiguousarray(pose0, np.float64).reshape(16)
-            p0 = C.c_void_p(pose0.ctypes.data)
-        if results is None:
-            out = np.zeros(F - 1, dtype=STEP_DTYPE)
-            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
-        else:
-            out = results
-            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
-        # stream ordering as track_batch: the source frames are read by the resize kernel on the context's stream
-        ordered = self._order_in(left_frames)
-        self._check(self.lib.svo_ingest_track_batch(self.h, C.c_void_p(left_frames.data_ptr()),
-                                                    C.c_void_p(right_frames.data_ptr()), int(pitch), int(fstride),
-                                                    int(F), p0, rp, rmem))
-        if results is not None and ordered:
-            import torch
-            self.signal_stream_inputs(torch.cuda.current_stream(left_frames.device).cuda_stream)
-        return out
+        """track_batch on source-size frames: torch cuda uint8 tensors (F, src_height, src_width), rows may be padded; they are
+        read by the resize kernel on the context's stream."""
+        return self._track_batch(self.lib.svo_ingest_track_batch, self._src_shape(), left_frames, right_frames, pose0, results)
 
     def ingest_streams_step(self, ids, lefts, rights, results=None):
         """streams_step on source-size frames (svo_ingest_streams_step)."""
-        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
-        m = int(ids.shape[0])
-        shape = self._src_shape()
-        fl, pl, pitch, fstride, mem = self._frame_stack(lefts, shape) if m else (None, None, shape[1], 0, MEM_HOST)
-        fr, pr, pitch_r, fstride_r, mem_r = self._frame_stack(rights, shape) if m else (None, None, shape[1], 0, MEM_HOST)
-        assert (pitch, fstride, mem) == (pitch_r, fstride_r, mem_r)
-        assert m == 0 or (fl.shape[0] == m and fr.shape[0] == m)
-        if results is None:
-            out = np.zeros(m, dtype=STEP_DTYPE)
-            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
-        else:
-            out = results
-            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
-        ordered = False
-        if mem == MEM_DEVICE:
-            ordered = self._order_in(fl)
-        self._check(self.lib.svo_ingest_streams_step(self.h, C.c_void_p(ids.ctypes.data), m, pl, pr, pitch, fstride, mem, rp, rmem))
-        if results is not None and ordered:
-            self._order_out(fl)
-        return out
+        return self._streams_step(self.lib.svo_ingest_streams_step, self._src_shape(), ids, lefts, rights, results)
 
     def ingest_upload_frames(self, buf, left, right, first_slot=0):
         """upload_frames on source-size host frames (F, src_height, pitch): copied and resized into device frame buffer
         `buf` on the copy stream (svo_ingest_upload_frames_at); wait_upload / track_uploaded(_async) follow as usual."""
-        assert left.shape == right.shape and left.strides == right.strides and left.strides[2] == 1
-        assert tuple(left.shape[1:]) == self._src_shape(), (tuple(left.shape), self._src_shape())
-        self._check(self.lib.svo_ingest_upload_frames_at(self.h, int(buf), int(first_slot), C.c_void_p(left.ctypes.data),
-                                                         C.c_void_p(right.ctypes.data), int(left.strides[1]), int(left.strides[0]),
-                                                         int(left.shape[0])))
+        self._upload_frames(self.lib.svo_ingest_upload_frames_at, self._src_shape(), buf, left, right, first_slot)
 
     # ---- fused API --------------------------------------------------------------------------
     def add_frame(self, left, right):
-        pl, pitch, mem = self._img(left)
-        pr, pitch_r, mem_r = self._img(right)
+        return self._add_frame(self.lib.svo_add_frame, (self.height, self.width), left, right)
+
+    def _add_frame(self, fn, shape, left, right):
+        """svo_add_frame / svo_ingest_add_frame on one frame pair of `shape`."""
+        pl, pitch, mem = self._img(left, shape)
+        pr, pitch_r, mem_r = self._img(right, shape)
         assert pitch == pitch_r and mem == mem_r
         res = StepResult()
         if mem == MEM_DEVICE:
             # ORB mode reads level 0 IN PLACE until the end of the front end, and the frames may still be being written on
-            # torch's stream: order them before the library's kernels.  svo_add_frame returns with the record on the host,
+            # torch's stream: order them before the library's kernels.  The call returns with the record on the host,
             # i.e. after everything that reads the frames, so nothing is left to order afterwards.
             self._order_in(left)
-        rc = self._check(self.lib.svo_add_frame(self.h, pl, pr, pitch, mem, C.byref(res)), allow_soft=True)
+        rc = self._check(fn(self.h, pl, pr, pitch, mem, C.byref(res)), allow_soft=True)
         return rc, np.frombuffer(bytes(res), dtype=STEP_DTYPE)[0].copy()
 
     def reset(self):
@@ -637,20 +598,16 @@ class Context:
     def track_batch(self, left_frames, right_frames, pose0=None, results=None):
         """left/right_frames: torch cuda uint8 tensors (F, h, pitch>=w) viewed as (F, h, w).
         Returns a numpy structured array of F-1 step results (or fills the given cuda tensor)."""
+        return self._track_batch(self.lib.svo_track_batch, None, left_frames, right_frames, pose0, results)
+
+    def _track_batch(self, fn, shape, left_frames, right_frames, pose0, results):
+        """svo_track_batch / svo_ingest_track_batch on F frames per eye (of `shape`, where one is given)."""
         F = left_frames.shape[0]
         assert left_frames.is_cuda and right_frames.is_cuda
+        assert shape is None or (tuple(left_frames.shape[1:]) == tuple(shape) and left_frames.shape == right_frames.shape)
         assert left_frames.stride(2) == 1 and left_frames.stride() == right_frames.stride()
         pitch, fstride = left_frames.stride(1), left_frames.stride(0)
-        p0 = None
-        if pose0 is not None:
-            pose0 = np.ascontiguousarray(pose0, np.float64).reshape(16)
-            p0 = C.c_void_p(pose0.ctypes.data)
-        if results is None:
-            out = np.zeros(F - 1, dtype=STEP_DTYPE)
-            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
-        else:
-            out = results
-            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
+        out, rp, rmem = _records(F - 1, results)
         # The frames (read in place until the end of the front end in ORB mode) and a device result buffer (its zero fill) may
         # still be in flight on torch's current stream, and with device results the call returns while the kernels run:
         # torch's stream is ordered before the launch, and the kernels that READ THE FRAMES before whatever torch's stream
@@ -660,9 +617,8 @@ class Context:
         # signal_stream(consumer) / sync(), as before.  Two event operations each, no host synchronisation; skipped when
         # the context runs ON torch's current stream (set_stream).
         ordered = self._order_in(left_frames)
-        self._check(self.lib.svo_track_batch(self.h, C.c_void_p(left_frames.data_ptr()),
-                                             C.c_void_p(right_frames.data_ptr()), int(pitch), int(fstride),
-                                             int(F), p0, rp, rmem))
+        self._check(fn(self.h, C.c_void_p(left_frames.data_ptr()), C.c_void_p(right_frames.data_ptr()), int(pitch), int(fstride),
+                       int(F), _pose_ptr(pose0), rp, rmem))
         if results is not None and ordered:
             import torch
             self.signal_stream_inputs(torch.cuda.current_stream(left_frames.device).cuda_stream)
@@ -691,33 +647,29 @@ class Context:
         """left/right: (F, height, pitch) uint8 host arrays (ideally from host_frames); asynchronous.  first_slot: the frame
         slot of the device buffer the first of them goes to (svo_upload_frames_at: a stream whose halo frame is carried on
         the device uploads its new frames into slots 1..)."""
+        self._upload_frames(self.lib.svo_upload_frames_at, None, buf, left, right, first_slot)
+
+    def _upload_frames(self, fn, shape, buf, left, right, first_slot):
+        """svo_upload_frames_at / svo_ingest_upload_frames_at on F host frames per eye (of `shape`, where one is given)."""
         assert left.shape == right.shape and left.strides == right.strides and left.strides[2] == 1
-        self._check(self.lib.svo_upload_frames_at(self.h, int(buf), int(first_slot), C.c_void_p(left.ctypes.data),
-                                                  C.c_void_p(right.ctypes.data), int(left.strides[1]), int(left.strides[0]),
-                                                  int(left.shape[0])))
+        assert shape is None or tuple(left.shape[1:]) == tuple(shape), (tuple(left.shape), shape)
+        self._check(fn(self.h, int(buf), int(first_slot), C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data),
+                       int(left.strides[1]), int(left.strides[0]), int(left.shape[0])))
 
     def wait_upload(self, buf):
         self._check(self.lib.svo_wait_upload(self.h, int(buf)))
 
     def track_uploaded(self, buf, n_frames, pose0=None):
-        p0 = None
-        if pose0 is not None:
-            pose0 = np.ascontiguousarray(pose0, np.float64).reshape(16)
-            p0 = C.c_void_p(pose0.ctypes.data)
         out = np.zeros(int(n_frames) - 1, dtype=STEP_DTYPE)
-        self._check(self.lib.svo_track_uploaded(self.h, int(buf), int(n_frames), p0, C.c_void_p(out.ctypes.data), MEM_HOST))
+        self._check(self.lib.svo_track_uploaded(self.h, int(buf), int(n_frames), _pose_ptr(pose0), C.c_void_p(out.ctypes.data), MEM_HOST))
         return out
 
     def track_uploaded_async(self, buf, n_frames, pose0=None, continue_chain=False, carry_frame=False):
         """svo_track_uploaded without waiting for the GPU; the records are fetched by collect_results()
         (up to two batches outstanding, collected in launch order).  carry_frame (with continue_chain): frame 0 of this
         batch is the previous batch's last frame -- its features are carried over on the device, not computed again."""
-        p0 = None
-        if pose0 is not None:
-            pose0 = np.ascontiguousarray(pose0, np.float64).reshape(16)
-            p0 = C.c_void_p(pose0.ctypes.data)
         flags = (1 if continue_chain else 0) | (2 if continue_chain and carry_frame else 0)
-        self._check(self.lib.svo_track_uploaded_async(self.h, int(buf), int(n_frames), p0, flags))
+        self._check(self.lib.svo_track_uploaded_async(self.h, int(buf), int(n_frames), _pose_ptr(pose0), flags))
 
     def collect_results(self, n_pairs):
         out = np.zeros(int(n_pairs), dtype=STEP_DTYPE)
@@ -737,10 +689,6 @@ class Context:
     def chain_relative(self, T_rel_inv, ok, pose0=None):
         """poses[p] = pose0 * prod_{q<=p, ok[q]} T[q] (svo_chain_relative).  numpy arrays or torch cuda
         tensors: T (n, 16) float64, ok (n,) int32.  Returns (n, 16) of the same kind."""
-        p0 = None
-        if pose0 is not None:
-            pose0 = np.ascontiguousarray(pose0, np.float64).reshape(16)
-            p0 = C.c_void_p(pose0.ctypes.data)
         if isinstance(T_rel_inv, np.ndarray):
             T = np.ascontiguousarray(T_rel_inv, np.float64).reshape(-1, 16)
             okc = np.ascontiguousarray(ok, np.int32)
@@ -754,7 +702,7 @@ class Context:
             out = torch.zeros_like(T)
             self._order_in(out)
             tp, op_, up, mem = C.c_void_p(T.data_ptr()), C.c_void_p(okc.data_ptr()), C.c_void_p(out.data_ptr()), MEM_DEVICE
-        self._check(self.lib.svo_chain_relative(self.h, tp, op_, int(T.shape[0]), p0, up, mem))
+        self._check(self.lib.svo_chain_relative(self.h, tp, op_, int(T.shape[0]), _pose_ptr(pose0), up, mem))
         if mem == MEM_DEVICE:
             self._order_out(out)        # device tensors: complete in stream order, for torch's current stream too
         return out
@@ -795,8 +743,8 @@ class Context:
         self._check(self.lib.svo_streams_count(self.h, C.byref(n)))
         return n.value
 
-    def _frame_stack(self, frames, shape=None):
-        """(array, pointer, pitch, frame stride, memory kind) of m equal-size u8 frames: a stacked (m, h, w) numpy array or
+    def _frame_stack(self, frames, shape):
+        """(array, pointer, pitch, frame stride, memory kind) of m equal-size u8 frames of `shape`: a stacked (m, h, w) numpy array or
         torch tensor (rows may be padded), or a list of (h, w) images, which is stacked."""
         if isinstance(frames, (list, tuple)):
             if isinstance(frames[0], np.ndarray):
@@ -804,7 +752,6 @@ class Context:
             else:
                 import torch
                 frames = torch.stack(list(frames))
-        shape = shape or (self.height, self.width)
         assert tuple(frames.shape[1:]) == tuple(shape), (tuple(frames.shape), shape)
         if isinstance(frames, np.ndarray):
             assert frames.dtype == np.uint8 and frames.strides[2] == 1
@@ -818,22 +765,21 @@ class Context:
         next frame of stream ids[i].  Frames: numpy (host) or torch cuda, stacked (m, h, w) or a list of (h, w) images.
         Returns the m step records in the caller's order as a numpy structured array, or -- results = a cuda uint8 / record
         tensor of m * STEP_DTYPE.itemsize bytes -- fills that tensor in stream order without a host synchronisation."""
+        return self._streams_step(self.lib.svo_streams_step, (self.height, self.width), ids, lefts, rights, results)
+
+    def _streams_step(self, fn, shape, ids, lefts, rights, results):
+        """svo_streams_step / svo_ingest_streams_step on one frame of `shape` per named stream."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         m = int(ids.shape[0])
-        fl, pl, pitch, fstride, mem = self._frame_stack(lefts) if m else (None, None, self.width, 0, MEM_HOST)
-        fr, pr, pitch_r, fstride_r, mem_r = self._frame_stack(rights) if m else (None, None, self.width, 0, MEM_HOST)
+        fl, pl, pitch, fstride, mem = self._frame_stack(lefts, shape) if m else (None, None, shape[1], 0, MEM_HOST)
+        fr, pr, pitch_r, fstride_r, mem_r = self._frame_stack(rights, shape) if m else (None, None, shape[1], 0, MEM_HOST)
         assert (pitch, fstride, mem) == (pitch_r, fstride_r, mem_r)
         assert m == 0 or (fl.shape[0] == m and fr.shape[0] == m)
-        if results is None:
-            out = np.zeros(m, dtype=STEP_DTYPE)
-            rp, rmem = C.c_void_p(out.ctypes.data), MEM_HOST
-        else:
-            out = results
-            rp, rmem = C.c_void_p(results.data_ptr()), MEM_DEVICE
+        out, rp, rmem = _records(m, results)
         ordered = False
         if mem == MEM_DEVICE:
             ordered = self._order_in(fl)     # the frames (and a device result buffer) may still be in flight on torch's stream
-        self._check(self.lib.svo_streams_step(self.h, C.c_void_p(ids.ctypes.data), m, pl, pr, pitch, fstride, mem, rp, rmem))
+        self._check(fn(self.h, C.c_void_p(ids.ctypes.data), m, pl, pr, pitch, fstride, mem, rp, rmem))
         if results is not None and ordered:
             self._order_out(fl)              # frames and records: before whatever torch's stream does next
         return out

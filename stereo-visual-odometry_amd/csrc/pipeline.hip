@@ -82,6 +82,27 @@ struct StreamStep { const int32_t *ids; const uint8_t *init; };
 static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first = false,
                     const StreamStep *ss = nullptr);
 
+// What a frame carries from one step to the next -- the list exists here only.  work[k]: the working array behind segment k (frame
+// slot f at work[k] + f * bytes[k]); is_count[k]: a count segment.  carry_last_frame moves them between frame slots, a stream
+// set keeps them per stream, in this order (streams_create sizes the store by them).
+static int stream_segments(svo_ctx *ctx, uint8_t *work[4], size_t bytes[4], int is_count[4])
+{
+    const size_t cap = (size_t)ctx->cfg.max_keypoints;
+    if (ctx->cfg.track_mode == SVO_MODE_ORB) {
+        const size_t kcap = (size_t)ctx->orb_kp_cap;
+        work[0] = (uint8_t *)ctx->orb_kps;      bytes[0] = 2 * kcap * sizeof(svo_keypoint); is_count[0] = 0;
+        work[1] = ctx->orb_desc;                bytes[1] = 2 * kcap * 32;                   is_count[1] = 0;
+        work[2] = (uint8_t *)ctx->orb_n;        bytes[2] = 2 * sizeof(int);                 is_count[2] = 1;
+        work[3] = (uint8_t *)ctx->orb_overflow; bytes[3] = 2 * sizeof(int);                 is_count[3] = 1;
+    } else {
+        work[0] = ctx->bslots;                  bytes[0] = (size_t)2 * ctx->geom.slot_bytes; is_count[0] = 0;
+        work[1] = (uint8_t *)ctx->kp_xy;        bytes[1] = cap * sizeof(float2);            is_count[1] = 0;
+        work[2] = (uint8_t *)ctx->kp_resp;      bytes[2] = cap * sizeof(float);             is_count[2] = 0;
+        work[3] = (uint8_t *)ctx->kp_n;         bytes[3] = sizeof(int);                     is_count[3] = 1;
+    }
+    return 4;
+}
+
 // A micro-batch of a stream starts with the frame the previous one ended with: instead of building that frame's
 // pyramids and detecting its features again, what the pair needs of it is carried from frame slot `last` to slot 0
 // (LK mode: the two pyramid slots, the FAST keypoints + responses + count; ORB mode: both images' keypoints, descriptors,
@@ -101,22 +122,10 @@ __global__ __launch_bounds__(256) void carry_frame_kernel(CarryArgs a)
 static void carry_last_frame(svo_ctx *ctx, int last)
 {
     CarryArgs c{};
-    const size_t cap = (size_t)ctx->cfg.max_keypoints;
-    auto seg = [&](void *dst, const void *src, size_t bytes) {
-        c.dst[c.n] = (uint8_t *)dst; c.src[c.n] = (const uint8_t *)src; c.bytes[c.n] = bytes; c.n++;
-    };
-    if (ctx->cfg.track_mode == SVO_MODE_ORB) {
-        const size_t kcap = (size_t)ctx->orb_kp_cap;
-        seg(ctx->orb_kps, (const svo_keypoint *)ctx->orb_kps + 2 * (size_t)last * kcap, 2 * kcap * sizeof(svo_keypoint));
-        seg(ctx->orb_desc, ctx->orb_desc + 2 * (size_t)last * kcap * 32, 2 * kcap * 32);
-        seg(ctx->orb_n, ctx->orb_n + 2 * last, 2 * sizeof(int));
-        seg(ctx->orb_overflow, ctx->orb_overflow + 2 * last, 2 * sizeof(int));
-    } else {
-        seg(ctx->bslots, ctx->bslots + (size_t)(2 * last) * ctx->geom.slot_bytes, (size_t)2 * ctx->geom.slot_bytes);
-        seg(ctx->kp_xy, ctx->kp_xy + (size_t)last * cap, cap * sizeof(float2));
-        seg(ctx->kp_resp, ctx->kp_resp + (size_t)last * cap, cap * sizeof(float));
-        seg(ctx->kp_n, ctx->kp_n + last, sizeof(int));
-    }
+    uint8_t *work[4];
+    int is_count[4];
+    c.n = stream_segments(ctx, work, c.bytes, is_count);
+    for (int k = 0; k < c.n; k++) { c.dst[k] = work[k]; c.src[k] = work[k] + (size_t)last * c.bytes[k]; }
     hipLaunchKernelGGL(carry_frame_kernel, dim3(64, c.n), dim3(256), 0, ctx->stream, c);
 }
 
@@ -163,25 +172,6 @@ __global__ __launch_bounds__(256) void stream_copy_kernel(StreamCopyArgs a)
     for (size_t i = done + tid; i < bytes; i += nthr) d[i] = s[i];
 }
 
-// The working arrays behind the segments of the stream store, in the store's order (streams_create sizes the store by them).
-static int stream_segments(svo_ctx *ctx, uint8_t *work[4], size_t bytes[4], int is_count[4])
-{
-    const size_t cap = (size_t)ctx->cfg.max_keypoints;
-    if (ctx->cfg.track_mode == SVO_MODE_ORB) {
-        const size_t kcap = (size_t)ctx->orb_kp_cap;
-        work[0] = (uint8_t *)ctx->orb_kps;      bytes[0] = 2 * kcap * sizeof(svo_keypoint); is_count[0] = 0;
-        work[1] = ctx->orb_desc;                bytes[1] = 2 * kcap * 32;                   is_count[1] = 0;
-        work[2] = (uint8_t *)ctx->orb_n;        bytes[2] = 2 * sizeof(int);                 is_count[2] = 1;
-        work[3] = (uint8_t *)ctx->orb_overflow; bytes[3] = 2 * sizeof(int);                 is_count[3] = 1;
-    } else {
-        work[0] = ctx->bslots;                  bytes[0] = (size_t)2 * ctx->geom.slot_bytes; is_count[0] = 0;
-        work[1] = (uint8_t *)ctx->kp_xy;        bytes[1] = cap * sizeof(float2);            is_count[1] = 0;
-        work[2] = (uint8_t *)ctx->kp_resp;      bytes[2] = cap * sizeof(float);             is_count[2] = 0;
-        work[3] = (uint8_t *)ctx->kp_n;         bytes[3] = sizeof(int);                     is_count[3] = 1;
-    }
-    return 4;
-}
-
 static void launch_stream_copy(svo_ctx *ctx, const StreamTable &tab, int n_items, int slot0, bool to_store)
 {
     StreamCopyArgs a{};
@@ -194,6 +184,19 @@ static void launch_stream_copy(svo_ctx *ctx, const StreamTable &tab, int n_items
     int gx = 2048 / n_items;
     gx = gx > 64 ? 64 : (gx < 8 ? 8 : gx);
     hipLaunchKernelGGL(stream_copy_kernel, dim3(gx, a.n_seg, n_items), dim3(256), 0, ctx->stream, a);
+}
+
+// launch(tab, i0, n) for every chunk of up to kStreamChunk items of a step: tab.id[t] / tab.init[t] are those of item i0 + t
+// (init null: none is an init item).
+template <class F>
+static void for_stream_chunks(const int32_t *ids, const uint8_t *init, int m, F launch)
+{
+    for (int i0 = 0; i0 < m; i0 += kStreamChunk) {
+        const int n = m - i0 < kStreamChunk ? m - i0 : kStreamChunk;
+        StreamTable tab{};
+        for (int t = 0; t < n; t++) { tab.id[t] = ids[i0 + t]; tab.init[t] = init ? init[i0 + t] : 0; }
+        launch(tab, i0, n);
+    }
 }
 
 // Tracks `n_pairs` pairs; pair p = (frame slot fp0 + p*fstep, frame slot fc0 + p*fstep).
@@ -290,18 +293,14 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
     const int *ovf = ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->kp_n_snap + 2 * n_pairs : nullptr;
     if (ss) {
         // gates per pair, pose_s = pose_s * T_rel_inv per stream (no chain along the launch), init records
-        for (int i0 = 0; i0 < n_pairs; i0 += kStreamChunk) {
-            const int n = n_pairs - i0 < kStreamChunk ? n_pairs - i0 : kStreamChunk;
-            StreamTable tab{};
-            for (int t = 0; t < n; t++) { tab.id[t] = ss->ids[i0 + t]; tab.init[t] = ss->init[i0 + t]; }
+        for_stream_chunks(ss->ids, ss->init, n_pairs, [&](const StreamTable &tab, int i0, int n) {
             launch_finalize_streams(ctx, i0, n, n_pairs, ctx->kp_n_snap, ctx->kp_n_snap + n_pairs, ovf, tab, bs);
-        }
+        });
     } else {
         launch_finalize_chain(ctx, n_pairs, ctx->kp_n_snap, ctx->kp_n_snap + n_pairs, ovf, pose0_host, bs);
     }
-    if (results_dev)
-        SVO_HIP(hipMemcpyAsync(results_dev, ctx->d_results, sizeof(svo_step_result) * (size_t)n_pairs,
-                               hipMemcpyDeviceToDevice, bs));
+    const int rc = deliver_records(ctx, ctx->d_results, n_pairs, results_dev, SVO_MEM_DEVICE, bs);
+    if (rc) return rc;
     if (side) {
         SVO_HIP(hipEventRecord(ctx->ev_back, ctx->side_stream));
         ctx->back_pending = true;
@@ -311,16 +310,24 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
     return SVO_OK;
 }
 
+int deliver_records(svo_ctx *ctx, const svo_step_result *d_src, int n, svo_step_result *out, int mem, hipStream_t st)
+{
+    const size_t bytes = sizeof(svo_step_result) * (size_t)n;
+    if (mem == SVO_MEM_DEVICE) {
+        if (out) SVO_HIP(hipMemcpyAsync(out, d_src, bytes, hipMemcpyDeviceToDevice, st));
+        return SVO_OK;
+    }
+    void *h = (char *)ctx->h_pinned + kPinnedRecords;
+    SVO_HIP(hipMemcpyAsync(h, d_src, bytes, hipMemcpyDeviceToHost, st));
+    SVO_HIP(hipStreamSynchronize(st));
+    memcpy(out, h, bytes);
+    return SVO_OK;
+}
+
 int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch,
                          int64_t frame_stride, int n_frames, const double *pose0,
                          svo_step_result *results, int results_mem, int carry_first)
 {
-    // results == NULL with SVO_MEM_DEVICE: the records stay in the context (svo_collect_results)
-    SVO_ARG(left_frames && right_frames && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
-    SVO_ARG(n_frames >= 2 && n_frames - 1 <= ctx->cfg.max_batch, "n_frames - 1 must be in [1, max_batch]");
-    SVO_ARG(pitch >= ctx->cfg.width && frame_stride >= (int64_t)pitch * ctx->cfg.height, "bad pitch / frame_stride");
-    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
-    SVO_HIP(hipSetDevice(ctx->device));
     const int n_pairs = n_frames - 1;
     // carry_first: frame 0 of this batch IS the last frame of the previous batch on this context (a stream's halo frame):
     // its features are carried over instead of being computed again
@@ -339,15 +346,12 @@ int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t
     }
     if (rc) return rc;
     // the LK outputs use the keypoint stride (cap) per item: frame slots are consecutive (fstep 1)
+    // (device records -- results null: they stay in the context for svo_collect_results -- are the pose stage's last copy, on its stream)
     rc = run_pairs(ctx, n_pairs, 0, 1, 1, pose0, results_mem == SVO_MEM_DEVICE ? results : nullptr);
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
     if (results_mem == SVO_MEM_DEVICE) return SVO_OK;
-    svo_step_result *h = (svo_step_result *)((char *)ctx->h_pinned + 4096);
-    SVO_HIP(hipMemcpyAsync(h, ctx->d_results, sizeof(svo_step_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(results, h, sizeof(svo_step_result) * (size_t)n_pairs);
-    return SVO_OK;
+    return deliver_records(ctx, ctx->d_results, n_pairs, results, SVO_MEM_HOST, ctx->stream);
 }
 
 // Host image -> device staging: the rows are gathered into a pinned mirror with the staging pitch
@@ -371,27 +375,14 @@ int stage_host_image(svo_ctx *ctx, const uint8_t *img, int pitch, int stage_idx,
     return SVO_OK;
 }
 
-int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem,
-                       svo_step_result *res)
+int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, svo_step_result *res)
 {
-    SVO_ARG(left && right && res, "null pointer");
-    SVO_ARG(pitch >= ctx->cfg.width, "pitch < width");
-    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
-    SVO_HIP(hipSetDevice(ctx->device));
     ctx->carry_slot = -1;                        // the online ring lives in frame slots 0 / 1
-    const uint8_t *dL = left, *dR = right;
-    int dp = pitch;
-    if (mem == SVO_MEM_HOST) {
-        int rcs = stage_host_image(ctx, left, pitch, 0, &dL, &dp);
-        if (rcs) return rcs;
-        rcs = stage_host_image(ctx, right, pitch, 1, &dR, &dp);
-        if (rcs) return rcs;
-    }
     // two-frame ring in frame slots 0 / 1
     const int cur = ctx->online_frames == 0 ? 0 : (ctx->online_cur ^ 1);
     const int prev = cur ^ 1;
     mark(ctx, kT0);
-    int rc = ingest_frames(ctx, dL, dR, dp, 0, cur, 1);
+    int rc = ingest_frames(ctx, left, right, pitch, 0, cur, 1);
     if (rc) return rc;
     memset(res, 0, sizeof(*res));
     if (ctx->online_frames == 0) {
@@ -409,10 +400,8 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     rc = run_pairs(ctx, 1, prev, cur, 0, ctx->pose, nullptr);
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
-    svo_step_result *h = (svo_step_result *)((char *)ctx->h_pinned + 4096);
-    SVO_HIP(hipMemcpyAsync(h, ctx->d_results, sizeof(svo_step_result), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    *res = *h;
+    rc = deliver_records(ctx, ctx->d_results, 1, res, SVO_MEM_HOST, ctx->stream);
+    if (rc) return rc;
     ctx->online_tracked = res->n_tracked;
     memcpy(ctx->pose, res->pose, sizeof(ctx->pose));
     ctx->online_frames++; ctx->online_cur = cur;       // last_frame_ = current_frame_ on both outcomes (:59-68)
@@ -483,25 +472,25 @@ int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose)
     return SVO_OK;
 }
 
-// L / R: DEVICE frames (frame i at base + i * frame_stride), already ordered before the context's stream.
-int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
-                          int64_t frame_stride, svo_step_result *results, int results_mem)
+// The m ids of one step: each names a stream of the set, none twice (a stream remembers the last call that named it).
+int pipeline_streams_check_ids(svo_ctx *ctx, const int32_t *ids, int m)
 {
     StreamSet &ss = ctx->streams;
-    // working frame slots 0 .. m-1 hold the streams' previous frames, m .. 2m-1 the new ones: 2m of the context's max_batch + 1
-    const int m_cap = (ctx->cfg.max_batch + 1) / 2;
-    SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
-    SVO_ARG(ids && L && R && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
-    SVO_ARG(m >= 1 && m <= m_cap, "m must be in [1, (max_batch + 1) / 2]");
-    SVO_ARG(pitch >= ctx->cfg.width && (m == 1 || frame_stride >= (int64_t)pitch * ctx->cfg.height), "bad pitch / frame_stride");
-    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
     for (int i = 0; i < m; i++) SVO_ARG(ids[i] >= 0 && ids[i] < ss.n, "stream id out of range");
     ss.call++;
     for (int i = 0; i < m; i++) {
         SVO_ARG(ss.seen[(size_t)ids[i]] != ss.call, "the same stream id twice in one step");
         ss.seen[(size_t)ids[i]] = ss.call;
     }
-    SVO_HIP(hipSetDevice(ctx->device));
+    return SVO_OK;
+}
+
+// Frame i at base + i * frame_stride.  Working frame slots 0 .. m-1 hold the streams' previous frames, m .. 2m-1 the new ones:
+// 2m of the context's max_batch + 1.
+int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
+                          int64_t frame_stride, svo_step_result *results, int results_mem)
+{
+    StreamSet &ss = ctx->streams;
     // one more writer of the working frame slots and the pair buffers, like svo_track_batch: a pending side-stream pose stage
     // still reads them, and neither a carried frame nor the online ring survives
     if (ctx->back_pending) {
@@ -513,21 +502,11 @@ int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t
     std::vector<uint8_t> init((size_t)m);
     for (int i = 0; i < m; i++) init[(size_t)i] = ss.n_frames[(size_t)ids[i]] == 0;
     mark(ctx, kT0);
-    for (int i0 = 0; i0 < m; i0 += kStreamChunk) {
-        const int n = m - i0 < kStreamChunk ? m - i0 : kStreamChunk;
-        StreamTable tab{};
-        for (int t = 0; t < n; t++) { tab.id[t] = ids[i0 + t]; tab.init[t] = init[(size_t)(i0 + t)]; }
-        launch_stream_copy(ctx, tab, n, i0, /*to_store*/ false);
-    }
+    for_stream_chunks(ids, init.data(), m, [&](const StreamTable &tab, int i0, int n) { launch_stream_copy(ctx, tab, n, i0, /*to_store*/ false); });
     mark(ctx, kTGather);
     int rc = ingest_frames(ctx, L, R, pitch, m == 1 ? 0 : frame_stride, m, m);
     if (rc) return rc;
-    for (int i0 = 0; i0 < m; i0 += kStreamChunk) {
-        const int n = m - i0 < kStreamChunk ? m - i0 : kStreamChunk;
-        StreamTable tab{};
-        for (int t = 0; t < n; t++) tab.id[t] = ids[i0 + t];
-        launch_stream_copy(ctx, tab, n, m + i0, /*to_store*/ true);
-    }
+    for_stream_chunks(ids, nullptr, m, [&](const StreamTable &tab, int i0, int n) { launch_stream_copy(ctx, tab, n, m + i0, /*to_store*/ true); });
     mark(ctx, kTScatter);
     // last_frame_ = current_frame_ on every outcome (src/tracking.cpp:59-68): the store already holds the new frames
     for (int i = 0; i < m; i++) ss.n_frames[(size_t)ids[i]]++;
@@ -535,16 +514,7 @@ int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t
     rc = run_pairs(ctx, m, 0, m, 1, nullptr, nullptr, &step);
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
-    if (results_mem == SVO_MEM_DEVICE) {
-        if (results)
-            SVO_HIP(hipMemcpyAsync(results, ctx->d_results, sizeof(svo_step_result) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
-        return SVO_OK;
-    }
-    svo_step_result *h = (svo_step_result *)((char *)ctx->h_pinned + 4096);
-    SVO_HIP(hipMemcpyAsync(h, ctx->d_results, sizeof(svo_step_result) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(results, h, sizeof(svo_step_result) * (size_t)m);
-    return SVO_OK;
+    return deliver_records(ctx, ctx->d_results, m, results, results_mem, ctx->stream);
 }
 
 }  // namespace svo

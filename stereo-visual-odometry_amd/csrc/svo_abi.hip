@@ -11,28 +11,6 @@
 
 using namespace svo;
 
-namespace svo {
-// geometry.hip / pipeline.hip
-int geom_workspace_bytes(const svo_config &cfg, int n_items, size_t *bytes);
-int geom_workspace_init(svo_ctx *ctx);
-int stage_triangulate(svo_ctx *ctx, const double P1[12], const double P2[12], const svo_pt2f *x1,
-                      const svo_pt2f *x2, int n, svo_pt3f *out, int mem);
-int stage_pnp_ransac(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img, int n, const double K[9],
-                     int iterations, float reproj_err, double confidence, svo_pnp_result *res,
-                     uint8_t *inlier_mask, int mem);
-int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem,
-                       svo_step_result *res);
-int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch,
-                         int64_t frame_stride, int n_frames, const double *pose0,
-                         svo_step_result *results, int results_mem, int carry_first = 0);
-int pipeline_streams_create(svo_ctx *ctx, int n_streams);
-int pipeline_streams_reset(svo_ctx *ctx, int id);
-int pipeline_streams_set_pose(svo_ctx *ctx, int id, const double *pose);
-int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose);
-int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
-                          int64_t frame_stride, svo_step_result *results, int results_mem);
-}  // namespace svo
-
 static int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 namespace svo {
@@ -101,7 +79,6 @@ static void make_geom(int w, int h, PyrGeom *g)
     g->slot_bytes = off;
 }
 
-extern "C" int svo_wait_results(svo_ctx *ctx);
 extern "C" int svo_abi_version(void) { return SVO_ABI_VERSION; }
 extern "C" int svo_config_bytes(void) { return (int)sizeof(svo_config); }
 
@@ -296,7 +273,7 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
         CK(hipStreamCreateWithFlags(&ctx->fetch_stream, hipStreamNonBlocking));
         ctx->async_ready = true;
     }
-    ctx->h_pinned_bytes = sizeof(svo_step_result) * (size_t)B + 4096 +
+    ctx->h_pinned_bytes = kPinnedRecords + sizeof(svo_step_result) * (size_t)B +
                           (size_t)cap * (sizeof(svo_keypoint) + 32) + sizeof(int) * 64;
     CK(hipHostMalloc(&ctx->h_pinned, ctx->h_pinned_bytes, hipHostMallocDefault));
     PHASE("events, streams, page-locked scratch");
@@ -768,13 +745,6 @@ extern "C" int svo_pnp_ransac(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f 
     return stage_pnp_ransac(ctx, obj, img, n, K, iterations, reproj_err, confidence, res, inlier_mask, mem);
 }
 
-extern "C" int svo_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem,
-                             svo_step_result *res)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    return pipeline_add_frame(ctx, left, right, pitch, mem, res);
-}
-
 extern "C" int svo_reset(svo_ctx *ctx)
 {
     if (!ctx) return SVO_ERR_ARG;
@@ -795,15 +765,6 @@ extern "C" int svo_set_pose(svo_ctx *ctx, const double pose[16])
     if (!ctx || !pose) return SVO_ERR_ARG;
     memcpy(ctx->pose, pose, sizeof(double) * 16);
     return SVO_OK;
-}
-
-extern "C" int svo_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames,
-                               int pitch, int64_t frame_stride, int n_frames, const double *pose0,
-                               svo_step_result *results, int results_mem)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    return pipeline_track_batch(ctx, left_frames, right_frames, pitch, frame_stride, n_frames, pose0,
-                                results, results_mem);
 }
 
 // ---- host-resident frame batches ---------------------------------------------------------------
@@ -829,10 +790,153 @@ extern "C" int svo_host_free(svo_ctx *ctx, void *p)
     return SVO_OK;
 }
 
+// ---- the frame input path: every entry point that takes frames, plain (frames of the context's size) or ingest (source-size
+// frames, resized on the device first), goes through one function per family.  That function takes the frame size (w x h) to
+// check against and whether a resize goes in front, states the family's argument rules once -- pointers, counts, pitch / stride,
+// mem / results_mem, stream ids -- and runs them before anything is copied or launched.
+#define SVO_INGEST_ON() do { if (!ctx->ingest.on) { ctx->err = "no ingest stage (svo_ingest_create)"; return SVO_ERR_STATE; } } while (0)
+
+static size_t work_frame_bytes(const svo_ctx *ctx) { return (size_t)ctx->stage_pitch * ctx->cfg.height; }
+static size_t src_frame_bytes(const svo_ctx *ctx) { return (size_t)ctx->ingest.spitch * ctx->ingest.sh; }
+// Frames per eye of a frame buffer, of the ingest stage's working frames and of the staging behind them.
+static size_t frame_slots(const svo_ctx *ctx) { return (size_t)ctx->cfg.max_batch + 1; }
+
+// n HOST frames of w x h (frame f at src + f * sstride) -> DEVICE frames (frame f at dst + f * dstride), on `st`.  The device frames are dense
+// (dstride = dpitch * h): a source laid out the same way goes as one copy.
+static int copy_host_frames(svo_ctx *ctx, uint8_t *dst, int dpitch, int64_t dstride, const uint8_t *src, int spitch, int64_t sstride,
+                            int w, int h, int n, hipStream_t st)
+{
+    if (spitch == dpitch && (n == 1 || sstride == dstride)) {
+        SVO_HIP(hipMemcpyAsync(dst, src, (size_t)dstride * (size_t)n, hipMemcpyHostToDevice, st));
+        return SVO_OK;
+    }
+    for (int f = 0; f < n; f++)
+        SVO_HIP(hipMemcpy2DAsync(dst + f * dstride, (size_t)dpitch, src + f * sstride, (size_t)spitch, (size_t)w, (size_t)h,
+                                 hipMemcpyHostToDevice, st));
+    return SVO_OK;
+}
+
+// One HOST frame pair of the context's size -> the pinned staging of the online step.
+static int stage_host_pair(svo_ctx *ctx, const uint8_t **left, const uint8_t **right, int *pitch)
+{
+    const int hp = *pitch;
+    int rc = svo::stage_host_image(ctx, *left, hp, 0, left, pitch);
+    if (rc) return rc;
+    return svo::stage_host_image(ctx, *right, hp, 1, right, pitch);
+}
+
+// n source-size HOST frames per eye -> the ingest stage's device staging, on the context's stream; the caller's memory is free
+// again when this returns.
+static int ingest_stage_host(svo_ctx *ctx, const uint8_t **left, const uint8_t **right, int *pitch, int64_t *frame_stride, int n)
+{
+    Ingest &g = ctx->ingest;
+    const size_t fbytes = src_frame_bytes(ctx);
+    if (g.src_stage_frames < n) {
+        if (g.src_stage) {
+            SVO_HIP(hipStreamSynchronize(ctx->stream));
+            SVO_HIP(hipFree(g.src_stage));
+            g.src_stage = nullptr; g.src_stage_frames = 0;
+        }
+        SVO_HIP(hipMalloc((void **)&g.src_stage, 2 * fbytes * (size_t)n));
+        g.src_stage_frames = n;
+    }
+    const uint8_t *src[2] = {*left, *right};
+    for (int eye = 0; eye < 2; eye++) {
+        const int rc = copy_host_frames(ctx, g.src_stage + (size_t)eye * fbytes * (size_t)n, g.spitch, (int64_t)fbytes, src[eye], *pitch,
+                                        *frame_stride, g.sw, g.sh, n, ctx->stream);
+        if (rc) return rc;
+    }
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    *left = g.src_stage; *right = g.src_stage + fbytes * (size_t)n;
+    *pitch = g.spitch; *frame_stride = (int64_t)fbytes;
+    return SVO_OK;
+}
+
+// n source-size DEVICE frames per eye -> working frame slots 0 .. n-1 of the ingest stage, on the context's stream.
+static int ingest_resize(svo_ctx *ctx, const uint8_t **left, const uint8_t **right, int *pitch, int64_t *frame_stride, int n)
+{
+    uint8_t *wL = ctx->ingest.work, *wR = wL + frame_slots(ctx) * work_frame_bytes(ctx);
+    const int rc = resize_launch(ctx, ctx->ingest.tab, *left, *right, *pitch, *frame_stride, wL, wR, ctx->stage_pitch,
+                                 (int64_t)work_frame_bytes(ctx), n, ctx->stream);
+    *left = wL; *right = wR;
+    *pitch = ctx->stage_pitch; *frame_stride = (int64_t)work_frame_bytes(ctx);
+    return rc;
+}
+
+// ---- svo_add_frame / svo_ingest_add_frame
+static int add_frame(svo_ctx *ctx, int w, bool resize, const uint8_t *left, const uint8_t *right, int pitch, int mem,
+                     svo_step_result *res)
+{
+    SVO_ARG(left && right && res, "null pointer");
+    SVO_ARG(pitch >= w, (resize ? "pitch < source width" : "pitch < width"));
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
+    SVO_HIP(hipSetDevice(ctx->device));
+    int64_t frame_stride = 0;                               // one frame per eye
+    int rc = SVO_OK;
+    if (mem == SVO_MEM_HOST)
+        rc = resize ? ingest_stage_host(ctx, &left, &right, &pitch, &frame_stride, 1) : stage_host_pair(ctx, &left, &right, &pitch);
+    if (rc == SVO_OK && resize) rc = ingest_resize(ctx, &left, &right, &pitch, &frame_stride, 1);
+    if (rc) return rc;
+    return pipeline_add_frame(ctx, left, right, pitch, res);
+}
+
+extern "C" int svo_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem,
+                             svo_step_result *res)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return add_frame(ctx, ctx->cfg.width, false, left, right, pitch, mem, res);
+}
+
+extern "C" int svo_ingest_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem, svo_step_result *res)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    return add_frame(ctx, ctx->ingest.sw, true, left, right, pitch, mem, res);
+}
+
+// ---- svo_track_batch / svo_ingest_track_batch (DEVICE frames), and the batches of a frame buffer (svo_track_uploaded*)
+// results == NULL with SVO_MEM_DEVICE: the records stay in the context (svo_collect_results)
+static int track_batch(svo_ctx *ctx, int w, int h, bool resize, const uint8_t *lefts, const uint8_t *rights, int pitch,
+                       int64_t frame_stride, int n_frames, const double *pose0, svo_step_result *results, int results_mem,
+                       int carry_first = 0)
+{
+    SVO_ARG(lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
+    SVO_ARG(n_frames >= 2 && n_frames - 1 <= ctx->cfg.max_batch, "n_frames - 1 must be in [1, max_batch]");
+    SVO_ARG(pitch >= w && frame_stride >= (int64_t)pitch * h, "bad pitch / frame_stride");
+    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (resize) {
+        const int rc = ingest_resize(ctx, &lefts, &rights, &pitch, &frame_stride, n_frames);
+        if (rc) return rc;
+    }
+    return pipeline_track_batch(ctx, lefts, rights, pitch, frame_stride, n_frames, pose0, results, results_mem, carry_first);
+}
+
+extern "C" int svo_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames,
+                               int pitch, int64_t frame_stride, int n_frames, const double *pose0,
+                               svo_step_result *results, int results_mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return track_batch(ctx, ctx->cfg.width, ctx->cfg.height, false, left_frames, right_frames, pitch, frame_stride, n_frames, pose0,
+                       results, results_mem);
+}
+
+extern "C" int svo_ingest_track_batch(svo_ctx *ctx, const uint8_t *lefts, const uint8_t *rights, int pitch, int64_t frame_stride,
+                                      int n_frames, const double *pose0, svo_step_result *results, int results_mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    return track_batch(ctx, ctx->ingest.sw, ctx->ingest.sh, true, lefts, rights, pitch, frame_stride, n_frames, pose0, results,
+                       results_mem);
+}
+
+// ---- svo_upload_frames_at / svo_ingest_upload_frames_at: HOST frames -> frame buffer `buf`, everything on the copy stream.
+// With an ingest stage the copy lands in source-size staging and the resize fills the frame buffer, so everything behind
+// ev_up[buf] works unchanged.
 static int frame_buffers(svo_ctx *ctx)
 {
     if (ctx->copy_stream) return SVO_OK;
-    const size_t per_cam = (size_t)ctx->stage_pitch * ctx->cfg.height * (size_t)(ctx->cfg.max_batch + 1);
+    const size_t per_cam = work_frame_bytes(ctx) * frame_slots(ctx);
     // every resource behind its own guard: a call that failed half way leaves what it made for the next attempt
     // (copy_stream, made last, is what marks the set complete)
     for (int k = 0; k < 2; k++) {
@@ -844,46 +948,66 @@ static int frame_buffers(svo_ctx *ctx)
     return SVO_OK;
 }
 
-extern "C" int svo_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *left_frames, const uint8_t *right_frames,
-                                    int pitch, int64_t frame_stride, int n_frames);
-extern "C" int svo_upload_frames(svo_ctx *ctx, int buf, const uint8_t *left_frames, const uint8_t *right_frames,
-                                 int pitch, int64_t frame_stride, int n_frames)
+static int upload_frames_at(svo_ctx *ctx, int w, int h, bool resize, int buf, int first_slot, const uint8_t *lefts, const uint8_t *rights,
+                            int pitch, int64_t frame_stride, int n_frames)
 {
-    return svo_upload_frames_at(ctx, buf, 0, left_frames, right_frames, pitch, frame_stride, n_frames);
+    SVO_ARG(buf == 0 || buf == 1, "buf must be 0 or 1");
+    SVO_ARG(lefts && rights, "null frames");
+    SVO_ARG(first_slot >= 0 && n_frames >= 1 && first_slot + n_frames <= ctx->cfg.max_batch + 1, "first_slot + n_frames must be in [1, max_batch + 1]");
+    // slot 0 is either uploaded or carried on the device (SVO_CONTINUE_CARRY_FRAME): nothing else may be left out
+    SVO_ARG(first_slot <= 1, "first_slot must be 0 (a whole batch) or 1 (frame 0 is carried on the device)");
+    SVO_ARG(pitch >= w && frame_stride >= (int64_t)pitch * h, "bad pitch / frame_stride");
+    SVO_HIP(hipSetDevice(ctx->device));
+    int rc = frame_buffers(ctx);
+    if (rc) return rc;
+    Ingest &g = ctx->ingest;
+    const size_t sbytes = src_frame_bytes(ctx), fbytes = work_frame_bytes(ctx);
+    if (resize && !g.up_stage[buf] && dev_alloc(ctx, &g.up_stage[buf], 2 * sbytes * frame_slots(ctx)) != SVO_OK) return SVO_ERR_HIP;
+    // where the copy lands: the frame buffer itself, or the staging behind it
+    uint8_t *base = resize ? g.up_stage[buf] : ctx->fb[buf];
+    const size_t dbytes = resize ? sbytes : fbytes;
+    const int dpitch = resize ? g.spitch : ctx->stage_pitch;
+    // the batch that last read this buffer must have been ingested (the staging behind it is reused in copy-stream order)
+    if (ctx->fb_used[buf]) SVO_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_fb_free[buf], 0));
+    const uint8_t *src[2] = {lefts, rights};
+    uint8_t *dst[2];
+    for (int cam = 0; cam < 2; cam++) {
+        dst[cam] = base + ((size_t)cam * frame_slots(ctx) + (size_t)first_slot) * dbytes;
+        rc = copy_host_frames(ctx, dst[cam], dpitch, (int64_t)dbytes, src[cam], pitch, frame_stride, w, h, n_frames, ctx->copy_stream);
+        if (rc) return rc;
+    }
+    if (resize) {
+        uint8_t *dL = ctx->fb[buf] + (size_t)first_slot * fbytes;
+        rc = resize_launch(ctx, g.tab, dst[0], dst[1], g.spitch, (int64_t)sbytes, dL, dL + frame_slots(ctx) * fbytes, ctx->stage_pitch,
+                           (int64_t)fbytes, n_frames, ctx->copy_stream);
+        if (rc) return rc;
+    }
+    SVO_HIP(hipEventRecord(ctx->ev_up[buf], ctx->copy_stream));
+    ctx->fb_frames[buf] = first_slot + n_frames;
+    ctx->fb_first[buf] = first_slot;
+    return SVO_OK;
 }
 
 extern "C" int svo_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *left_frames, const uint8_t *right_frames,
                                     int pitch, int64_t frame_stride, int n_frames)
 {
     if (!ctx) return SVO_ERR_ARG;
-    SVO_ARG(buf == 0 || buf == 1, "buf must be 0 or 1");
-    SVO_ARG(left_frames && right_frames, "null frames");
-    SVO_ARG(first_slot >= 0 && n_frames >= 1 && first_slot + n_frames <= ctx->cfg.max_batch + 1, "first_slot + n_frames must be in [1, max_batch + 1]");
-    // slot 0 is either uploaded or carried on the device (SVO_CONTINUE_CARRY_FRAME): nothing else may be left out
-    SVO_ARG(first_slot <= 1, "first_slot must be 0 (a whole batch) or 1 (frame 0 is carried on the device)");
-    SVO_ARG(pitch >= ctx->cfg.width && frame_stride >= (int64_t)pitch * ctx->cfg.height, "bad pitch / frame_stride");
-    SVO_HIP(hipSetDevice(ctx->device));
-    int rc = frame_buffers(ctx);
-    if (rc) return rc;
-    const int w = ctx->cfg.width, h = ctx->cfg.height, sp = ctx->stage_pitch;
-    const size_t fbytes = (size_t)sp * h, per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
-    // the batch that last read this buffer must have been ingested
-    if (ctx->fb_used[buf]) SVO_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_fb_free[buf], 0));
-    const uint8_t *src[2] = {left_frames, right_frames};
-    for (int cam = 0; cam < 2; cam++) {
-        uint8_t *dst = ctx->fb[buf] + cam * per_cam + (size_t)first_slot * fbytes;
-        if (pitch == sp && frame_stride == (int64_t)fbytes) {
-            SVO_HIP(hipMemcpyAsync(dst, src[cam], fbytes * (size_t)n_frames, hipMemcpyHostToDevice, ctx->copy_stream));
-        } else {
-            for (int f = 0; f < n_frames; f++)
-                SVO_HIP(hipMemcpy2DAsync(dst + f * fbytes, sp, src[cam] + f * frame_stride, pitch, w, h,
-                                         hipMemcpyHostToDevice, ctx->copy_stream));
-        }
-    }
-    SVO_HIP(hipEventRecord(ctx->ev_up[buf], ctx->copy_stream));
-    ctx->fb_frames[buf] = first_slot + n_frames;
-    ctx->fb_first[buf] = first_slot;
-    return SVO_OK;
+    return upload_frames_at(ctx, ctx->cfg.width, ctx->cfg.height, false, buf, first_slot, left_frames, right_frames, pitch, frame_stride,
+                            n_frames);
+}
+
+extern "C" int svo_ingest_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *lefts, const uint8_t *rights,
+                                           int pitch, int64_t frame_stride, int n_frames)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    return upload_frames_at(ctx, ctx->ingest.sw, ctx->ingest.sh, true, buf, first_slot, lefts, rights, pitch, frame_stride, n_frames);
+}
+
+extern "C" int svo_upload_frames(svo_ctx *ctx, int buf, const uint8_t *left_frames, const uint8_t *right_frames,
+                                 int pitch, int64_t frame_stride, int n_frames)
+{
+    return svo_upload_frames_at(ctx, buf, 0, left_frames, right_frames, pitch, frame_stride, n_frames);
 }
 
 extern "C" int svo_wait_upload(svo_ctx *ctx, int buf)
@@ -905,10 +1029,10 @@ extern "C" int svo_track_uploaded(svo_ctx *ctx, int buf, int n_frames, const dou
     SVO_ARG(ctx->fb_first[buf] == 0, "frame slot 0 of this buffer was not uploaded (svo_upload_frames_at first_slot = 1): "
                                      "launch it with svo_track_uploaded_async and SVO_CONTINUE_CARRY_FRAME");
     SVO_HIP(hipSetDevice(ctx->device));
-    const size_t fbytes = (size_t)ctx->stage_pitch * ctx->cfg.height, per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
+    const size_t fbytes = work_frame_bytes(ctx), per_cam = fbytes * frame_slots(ctx);
     SVO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_up[buf], 0));
-    int rc = pipeline_track_batch(ctx, ctx->fb[buf], ctx->fb[buf] + per_cam, ctx->stage_pitch, (int64_t)fbytes, n_frames,
-                                  pose0, results, results_mem);
+    int rc = track_batch(ctx, ctx->cfg.width, ctx->cfg.height, false, ctx->fb[buf], ctx->fb[buf] + per_cam, ctx->stage_pitch,
+                         (int64_t)fbytes, n_frames, pose0, results, results_mem);
     if (rc < 0) return rc;
     SVO_HIP(hipEventRecord(ctx->ev_fb_free[buf], ctx->stream));
     ctx->fb_used[buf] = true;
@@ -943,11 +1067,11 @@ extern "C" int svo_track_uploaded_async(svo_ctx *ctx, int buf, int n_frames, con
         SVO_ARG(ctx->async_last_pairs > 0, "continue_chain needs a previous async batch");
         ctx->seed_dev = ctx->d_async[pr][ctx->async_last_pairs - 1].pose;
     }
-    const size_t fbytes = (size_t)ctx->stage_pitch * ctx->cfg.height, per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
+    const size_t fbytes = work_frame_bytes(ctx), per_cam = fbytes * frame_slots(ctx);
     SVO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_up[buf], 0));
-    int rc = pipeline_track_batch(ctx, ctx->fb[buf], ctx->fb[buf] + per_cam, ctx->stage_pitch, (int64_t)fbytes, n_frames,
-                                  continue_chain ? nullptr : pose0, ctx->d_async[r], SVO_MEM_DEVICE,
-                                  (continue_chain & SVO_CONTINUE_CARRY_FRAME) != 0);
+    int rc = track_batch(ctx, ctx->cfg.width, ctx->cfg.height, false, ctx->fb[buf], ctx->fb[buf] + per_cam, ctx->stage_pitch,
+                         (int64_t)fbytes, n_frames, continue_chain ? nullptr : pose0, ctx->d_async[r], SVO_MEM_DEVICE,
+                         (continue_chain & SVO_CONTINUE_CARRY_FRAME) != 0);
     ctx->seed_dev = nullptr;
     if (rc < 0) return rc;
     SVO_HIP(hipEventRecord(ctx->ev_fb_free[buf], ctx->stream));
@@ -986,10 +1110,8 @@ extern "C" int svo_collect_results(svo_ctx *ctx, svo_step_result *results, int n
     // wait for THAT batch only (its successor may be running), then fetch on a stream of its own: the
     // copy stream may be busy with the next chunk's upload
     SVO_HIP(hipEventSynchronize(ctx->ev_async[r]));
-    svo_step_result *h = (svo_step_result *)((char *)ctx->h_pinned + 4096);
-    SVO_HIP(hipMemcpyAsync(h, ctx->d_async[r], sizeof(svo_step_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, ctx->fetch_stream));
-    SVO_HIP(hipStreamSynchronize(ctx->fetch_stream));
-    memcpy(results, h, sizeof(svo_step_result) * (size_t)n_pairs);
+    const int rc = deliver_records(ctx, ctx->d_async[r], n_pairs, results, SVO_MEM_HOST, ctx->fetch_stream);
+    if (rc) return rc;
     ctx->async_n[r] = 0;
     ctx->async_head++;
     return SVO_OK;
@@ -1009,42 +1131,66 @@ extern "C" int svo_streams_count(const svo_ctx *ctx, int *n_streams)
     return SVO_OK;
 }
 
+// svo_streams_step / svo_ingest_streams_step.  HOST frames are staged first -- source-size ones in the ingest stage's staging, one
+// frame of the context's size in the pinned staging of svo_add_frame, several in frame buffer 0 of svo_upload_frames -- and the
+// caller's memory is free again when the call returns.
+static int streams_step(svo_ctx *ctx, int w, int h, bool resize, const int32_t *stream_ids, int m, const uint8_t *lefts,
+                        const uint8_t *rights, int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
+{
+    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(stream_ids && lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
+    SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
+    SVO_ARG(pitch >= w && (m == 1 || frame_stride >= (int64_t)pitch * h), "bad pitch / frame_stride");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
+    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
+    int rc = pipeline_streams_check_ids(ctx, stream_ids, m);
+    if (rc) return rc;
+    SVO_HIP(hipSetDevice(ctx->device));
+    bool in_fb0 = false;
+    if (mem == SVO_MEM_HOST) {
+        if (resize) {
+            rc = ingest_stage_host(ctx, &lefts, &rights, &pitch, &frame_stride, m);
+        } else if (m == 1) {
+            rc = stage_host_pair(ctx, &lefts, &rights, &pitch);
+        } else {
+            rc = upload_frames_at(ctx, w, h, false, 0, 0, lefts, rights, pitch, frame_stride, m);
+            if (rc) return rc;
+            SVO_HIP(hipEventSynchronize(ctx->ev_up[0]));
+            ctx->fb_frames[0] = 0;                          // (not a batch a later svo_track_uploaded may claim)
+            lefts = ctx->fb[0]; rights = ctx->fb[0] + frame_slots(ctx) * work_frame_bytes(ctx);
+            pitch = ctx->stage_pitch; frame_stride = (int64_t)work_frame_bytes(ctx);
+            in_fb0 = true;
+        }
+        if (rc) return rc;
+    }
+    if (resize) {
+        rc = ingest_resize(ctx, &lefts, &rights, &pitch, &frame_stride, m);
+        if (rc) return rc;
+    }
+    rc = pipeline_streams_step(ctx, stream_ids, m, lefts, rights, pitch, frame_stride, results, results_mem);
+    if (in_fb0) {                                           // whatever the step has queued reads frame buffer 0
+        SVO_HIP(hipEventRecord(ctx->ev_fb_free[0], ctx->stream));
+        ctx->fb_used[0] = true;
+    }
+    return rc;
+}
+
 extern "C" int svo_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *left_frames,
                                 const uint8_t *right_frames, int pitch, int64_t frame_stride, int mem,
                                 svo_step_result *results, int results_mem)
 {
     if (!ctx) return SVO_ERR_ARG;
-    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
-    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
-    if (mem == SVO_MEM_DEVICE)
-        return pipeline_streams_step(ctx, stream_ids, m, left_frames, right_frames, pitch, frame_stride, results, results_mem);
-    // host frames: checked here as far as the staging needs it, the rest by the step itself
-    SVO_ARG(stream_ids && left_frames && right_frames, "null pointer");
-    SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
-    SVO_ARG(pitch >= ctx->cfg.width && (m == 1 || frame_stride >= (int64_t)pitch * ctx->cfg.height), "bad pitch / frame_stride");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (m == 1) {
-        // one frame: the pinned staging of svo_add_frame
-        const uint8_t *dL, *dR;
-        int dp = 0;
-        int rc = svo::stage_host_image(ctx, left_frames, pitch, 0, &dL, &dp);
-        if (rc) return rc;
-        rc = svo::stage_host_image(ctx, right_frames, pitch, 1, &dR, &dp);
-        if (rc) return rc;
-        return pipeline_streams_step(ctx, stream_ids, 1, dL, dR, dp, 0, results, results_mem);
-    }
-    // several: frame buffer 0 of svo_upload_frames; the caller's memory is free again when the call returns
-    int rc = svo_upload_frames(ctx, 0, left_frames, right_frames, pitch, frame_stride, m);
-    if (rc) return rc;
-    SVO_HIP(hipEventSynchronize(ctx->ev_up[0]));
-    ctx->fb_frames[0] = 0;                              // (not a batch a later svo_track_uploaded may claim)
-    const size_t fbytes = (size_t)ctx->stage_pitch * ctx->cfg.height, per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
-    rc = pipeline_streams_step(ctx, stream_ids, m, ctx->fb[0], ctx->fb[0] + per_cam, ctx->stage_pitch, (int64_t)fbytes, results,
-                               results_mem);
-    if (rc < 0 && rc != SVO_ERR_HIP) return rc;         // refused before anything was launched
-    SVO_HIP(hipEventRecord(ctx->ev_fb_free[0], ctx->stream));
-    ctx->fb_used[0] = true;
-    return rc;
+    return streams_step(ctx, ctx->cfg.width, ctx->cfg.height, false, stream_ids, m, left_frames, right_frames, pitch, frame_stride, mem,
+                        results, results_mem);
+}
+
+extern "C" int svo_ingest_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *lefts, const uint8_t *rights,
+                                       int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_INGEST_ON();
+    return streams_step(ctx, ctx->ingest.sw, ctx->ingest.sh, true, stream_ids, m, lefts, rights, pitch, frame_stride, mem, results,
+                        results_mem);
 }
 
 extern "C" int svo_streams_reset(svo_ctx *ctx, int stream_id)
@@ -1065,24 +1211,8 @@ extern "C" int svo_streams_set_pose(svo_ctx *ctx, int stream_id, const double po
     return pipeline_streams_set_pose(ctx, stream_id, pose);
 }
 
-extern "C" int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
-                                    svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out);
-extern "C" int svo_streams_get_tracks(svo_ctx *ctx, int item, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
-                                      svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
-    // item i of a step is pair i of its launch set (an init item has no tracks: n = 0)
-    return svo_get_batch_tracks(ctx, item, t1_left, t1_right, t2_right, t2_left, inlier, cap, n_out);
-}
-
-// ---- ingest stage: source-size frames resized on the device into working-size frames the existing entry points read --------
+// ---- ingest stage: source-size frames resized on the device into working-size frames the entry points above read --------
 // (the kernel, the tap tables, svo_resize and svo_scale_projection: resize.hip)
-#define SVO_INGEST_ON() do { if (!ctx->ingest.on) { ctx->err = "no ingest stage (svo_ingest_create)"; return SVO_ERR_STATE; } } while (0)
-
-static size_t ingest_work_frame(const svo_ctx *ctx) { return (size_t)ctx->stage_pitch * ctx->cfg.height; }
-static size_t ingest_src_frame(const svo_ctx *ctx) { return (size_t)ctx->ingest.spitch * ctx->ingest.sh; }
-
 extern "C" int svo_ingest_create(svo_ctx *ctx, int src_width, int src_height, int interp, double fx, double fy)
 {
     if (!ctx) return SVO_ERR_ARG;
@@ -1092,7 +1222,7 @@ extern "C" int svo_ingest_create(svo_ctx *ctx, int src_width, int src_height, in
     int tab = -1;
     int rc = resize_plan(ctx, src_width, src_height, ctx->cfg.width, ctx->cfg.height, interp, fx, fy, &tab);
     if (rc) return rc;
-    if (!g.work && dev_alloc(ctx, &g.work, 2 * ingest_work_frame(ctx) * (size_t)(ctx->cfg.max_batch + 1)) != SVO_OK) return SVO_ERR_HIP;
+    if (!g.work && dev_alloc(ctx, &g.work, 2 * work_frame_bytes(ctx) * frame_slots(ctx)) != SVO_OK) return SVO_ERR_HIP;
     g.sw = src_width; g.sh = src_height; g.tab = tab;
     g.spitch = (src_width + 15) & ~15;
     g.on = true;
@@ -1109,158 +1239,6 @@ extern "C" int svo_ingest_info(const svo_ctx *ctx, int *src_width, int *src_heig
     if (interp) *interp = t.interp;
     if (inv_x) *inv_x = t.inv_x;
     if (inv_y) *inv_y = t.inv_y;
-    return SVO_OK;
-}
-
-// Left / right working-size frames of slot `slot`.
-static uint8_t *ingest_work(svo_ctx *ctx, int eye, int slot)
-{
-    return ctx->ingest.work + ((size_t)eye * (size_t)(ctx->cfg.max_batch + 1) + (size_t)slot) * ingest_work_frame(ctx);
-}
-
-// n source-size HOST frames per eye -> the stage's device staging, on the context's stream; the caller's memory is free again
-// when this returns.
-static int ingest_stage_host(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int64_t frame_stride, int n,
-                             const uint8_t **dL, const uint8_t **dR)
-{
-    Ingest &g = ctx->ingest;
-    const size_t fbytes = ingest_src_frame(ctx);
-    if (g.src_stage_frames < n) {
-        if (g.src_stage) {
-            SVO_HIP(hipStreamSynchronize(ctx->stream));
-            SVO_HIP(hipFree(g.src_stage));
-            g.src_stage = nullptr; g.src_stage_frames = 0;
-        }
-        SVO_HIP(hipMalloc((void **)&g.src_stage, 2 * fbytes * (size_t)n));
-        g.src_stage_frames = n;
-    }
-    const uint8_t *src[2] = {left, right};
-    for (int eye = 0; eye < 2; eye++) {
-        uint8_t *dst = g.src_stage + (size_t)eye * fbytes * (size_t)n;
-        if (pitch == g.spitch && (n == 1 || frame_stride == (int64_t)fbytes)) {
-            SVO_HIP(hipMemcpyAsync(dst, src[eye], fbytes * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            for (int f = 0; f < n; f++)
-                SVO_HIP(hipMemcpy2DAsync(dst + f * fbytes, (size_t)g.spitch, src[eye] + (n > 1 ? f * frame_stride : 0), (size_t)pitch,
-                                         (size_t)g.sw, (size_t)g.sh, hipMemcpyHostToDevice, ctx->stream));
-        }
-    }
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    *dL = g.src_stage; *dR = g.src_stage + fbytes * (size_t)n;
-    return SVO_OK;
-}
-
-extern "C" int svo_ingest_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem, svo_step_result *res)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    SVO_INGEST_ON();
-    SVO_ARG(left && right && res, "null pointer");
-    SVO_ARG(pitch >= ctx->ingest.sw, "pitch < source width");
-    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
-    SVO_HIP(hipSetDevice(ctx->device));
-    const uint8_t *sL = left, *sR = right;
-    int sp = pitch;
-    if (mem == SVO_MEM_HOST) {
-        int rc = ingest_stage_host(ctx, left, right, pitch, 0, 1, &sL, &sR);
-        if (rc) return rc;
-        sp = ctx->ingest.spitch;
-    }
-    uint8_t *wL = ingest_work(ctx, 0, 0), *wR = ingest_work(ctx, 1, 0);
-    int rc = resize_launch(ctx, ctx->ingest.tab, sL, sR, sp, 0, wL, wR, ctx->stage_pitch, 0, 1, ctx->stream);
-    if (rc) return rc;
-    return pipeline_add_frame(ctx, wL, wR, ctx->stage_pitch, SVO_MEM_DEVICE, res);
-}
-
-extern "C" int svo_ingest_track_batch(svo_ctx *ctx, const uint8_t *lefts, const uint8_t *rights, int pitch, int64_t frame_stride,
-                                      int n_frames, const double *pose0, svo_step_result *results, int results_mem)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    SVO_INGEST_ON();
-    // svo_track_batch's rules, against the source size: nothing is launched for a call it would refuse
-    SVO_ARG(lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
-    SVO_ARG(n_frames >= 2 && n_frames - 1 <= ctx->cfg.max_batch, "n_frames - 1 must be in [1, max_batch]");
-    SVO_ARG(pitch >= ctx->ingest.sw && frame_stride >= (int64_t)pitch * ctx->ingest.sh, "bad pitch / frame_stride");
-    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
-    SVO_HIP(hipSetDevice(ctx->device));
-    uint8_t *wL = ingest_work(ctx, 0, 0), *wR = ingest_work(ctx, 1, 0);
-    const int64_t wstride = (int64_t)ingest_work_frame(ctx);
-    int rc = resize_launch(ctx, ctx->ingest.tab, lefts, rights, pitch, frame_stride, wL, wR, ctx->stage_pitch, wstride, n_frames, ctx->stream);
-    if (rc) return rc;
-    return pipeline_track_batch(ctx, wL, wR, ctx->stage_pitch, wstride, n_frames, pose0, results, results_mem);
-}
-
-extern "C" int svo_ingest_streams_step(svo_ctx *ctx, const int32_t *stream_ids, int m, const uint8_t *lefts, const uint8_t *rights,
-                                       int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    SVO_INGEST_ON();
-    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
-    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
-    SVO_ARG(stream_ids && lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
-    SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
-    SVO_ARG(pitch >= ctx->ingest.sw && (m == 1 || frame_stride >= (int64_t)pitch * ctx->ingest.sh), "bad pitch / frame_stride");
-    SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
-    // ids: checked before anything is launched, as svo_streams_step does (the step itself checks them again and counts the call)
-    for (int i = 0; i < m; i++) {
-        SVO_ARG(stream_ids[i] >= 0 && stream_ids[i] < ctx->streams.n, "stream id out of range");
-        for (int j = 0; j < i; j++) SVO_ARG(stream_ids[j] != stream_ids[i], "the same stream id twice in one step");
-    }
-    SVO_HIP(hipSetDevice(ctx->device));
-    const uint8_t *sL = lefts, *sR = rights;
-    int sp = pitch;
-    int64_t sstride = frame_stride;
-    if (mem == SVO_MEM_HOST) {
-        int rc = ingest_stage_host(ctx, lefts, rights, pitch, frame_stride, m, &sL, &sR);
-        if (rc) return rc;
-        sp = ctx->ingest.spitch; sstride = (int64_t)ingest_src_frame(ctx);
-    }
-    uint8_t *wL = ingest_work(ctx, 0, 0), *wR = ingest_work(ctx, 1, 0);
-    const int64_t wstride = (int64_t)ingest_work_frame(ctx);
-    int rc = resize_launch(ctx, ctx->ingest.tab, sL, sR, sp, sstride, wL, wR, ctx->stage_pitch, wstride, m, ctx->stream);
-    if (rc) return rc;
-    return pipeline_streams_step(ctx, stream_ids, m, wL, wR, ctx->stage_pitch, wstride, results, results_mem);
-}
-
-// svo_upload_frames_at with the resize between the copy and the frame buffer: host -> source-size staging -> fb[buf], all on
-// the copy stream, so everything behind ev_up[buf] works unchanged.
-extern "C" int svo_ingest_upload_frames_at(svo_ctx *ctx, int buf, int first_slot, const uint8_t *lefts, const uint8_t *rights,
-                                           int pitch, int64_t frame_stride, int n_frames)
-{
-    if (!ctx) return SVO_ERR_ARG;
-    SVO_INGEST_ON();
-    Ingest &g = ctx->ingest;
-    SVO_ARG(buf == 0 || buf == 1, "buf must be 0 or 1");
-    SVO_ARG(lefts && rights, "null frames");
-    SVO_ARG(first_slot >= 0 && n_frames >= 1 && first_slot + n_frames <= ctx->cfg.max_batch + 1, "first_slot + n_frames must be in [1, max_batch + 1]");
-    SVO_ARG(first_slot <= 1, "first_slot must be 0 (a whole batch) or 1 (frame 0 is carried on the device)");
-    SVO_ARG(pitch >= g.sw && frame_stride >= (int64_t)pitch * g.sh, "bad pitch / frame_stride");
-    SVO_HIP(hipSetDevice(ctx->device));
-    int rc = frame_buffers(ctx);
-    if (rc) return rc;
-    const size_t sbytes = ingest_src_frame(ctx), s_per_cam = sbytes * (size_t)(ctx->cfg.max_batch + 1);
-    if (!g.up_stage[buf] && dev_alloc(ctx, &g.up_stage[buf], 2 * s_per_cam) != SVO_OK) return SVO_ERR_HIP;
-    const size_t fbytes = ingest_work_frame(ctx), per_cam = fbytes * (size_t)(ctx->cfg.max_batch + 1);
-    // the batch that last read this buffer must have been ingested (the staging behind it is reused in copy-stream order)
-    if (ctx->fb_used[buf]) SVO_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_fb_free[buf], 0));
-    const uint8_t *src[2] = {lefts, rights};
-    uint8_t *stg[2];
-    for (int cam = 0; cam < 2; cam++) {
-        stg[cam] = g.up_stage[buf] + cam * s_per_cam + (size_t)first_slot * sbytes;
-        if (pitch == g.spitch && frame_stride == (int64_t)sbytes) {
-            SVO_HIP(hipMemcpyAsync(stg[cam], src[cam], sbytes * (size_t)n_frames, hipMemcpyHostToDevice, ctx->copy_stream));
-        } else {
-            for (int f = 0; f < n_frames; f++)
-                SVO_HIP(hipMemcpy2DAsync(stg[cam] + f * sbytes, (size_t)g.spitch, src[cam] + f * frame_stride, (size_t)pitch, (size_t)g.sw,
-                                         (size_t)g.sh, hipMemcpyHostToDevice, ctx->copy_stream));
-        }
-    }
-    uint8_t *dL = ctx->fb[buf] + (size_t)first_slot * fbytes;
-    rc = resize_launch(ctx, g.tab, stg[0], stg[1], g.spitch, (int64_t)sbytes, dL, dL + per_cam, ctx->stage_pitch, (int64_t)fbytes, n_frames,
-                       ctx->copy_stream);
-    if (rc) return rc;
-    SVO_HIP(hipEventRecord(ctx->ev_up[buf], ctx->copy_stream));
-    ctx->fb_frames[buf] = first_slot + n_frames;
-    ctx->fb_first[buf] = first_slot;
     return SVO_OK;
 }
 
@@ -1324,6 +1302,21 @@ extern "C" int svo_get_frame_keypoints(svo_ctx *ctx, int side, svo_keypoint *kps
     return SVO_OK;
 }
 
+// The four point lists and the inlier mask of n tracks that start at `offset` in the pair buffers (null: not wanted).
+static int read_tracks(svo_ctx *ctx, size_t offset, int n, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right, svo_pt2f *t2_left,
+                       uint8_t *inlier)
+{
+    svo_pt2f *dst[4] = {t1_left, t1_right, t2_right, t2_left};
+    for (int k = 0; k < 4; k++) {
+        if (!dst[k]) continue;
+        if (k == 2 && ctx->cfg.track_mode == SVO_MODE_ORB) { memset(dst[k], 0, sizeof(svo_pt2f) * (size_t)n); continue; }
+        SVO_HIP(hipMemcpyAsync(dst[k], ctx->cmp[k] + offset, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (inlier) SVO_HIP(hipMemcpyAsync(inlier, pnp_inlier_mask(ctx) + offset, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
 // The same read-back for pair `pair` of the most recent svo_track_batch / svo_track_uploaded launch (ABI v6): what a
 // caller needs to audit a batch against another implementation -- bench.py's self-check does.
 extern "C" int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
@@ -1342,16 +1335,16 @@ extern "C" int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, s
     SVO_ARG(n <= cap, "track capacity too small");
     *n_out = n;
     if (n == 0) return SVO_OK;
-    const size_t o = (size_t)pair * ctx->cfg.max_keypoints;
-    svo_pt2f *dst[4] = {t1_left, t1_right, t2_right, t2_left};
-    for (int k = 0; k < 4; k++) {
-        if (!dst[k]) continue;
-        if (k == 2 && ctx->cfg.track_mode == SVO_MODE_ORB) { memset(dst[k], 0, sizeof(svo_pt2f) * (size_t)n); continue; }
-        SVO_HIP(hipMemcpyAsync(dst[k], ctx->cmp[k] + o, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (inlier) SVO_HIP(hipMemcpyAsync(inlier, pnp_inlier_mask(ctx) + o, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    return read_tracks(ctx, (size_t)pair * ctx->cfg.max_keypoints, n, t1_left, t1_right, t2_right, t2_left, inlier);
+}
+
+extern "C" int svo_streams_get_tracks(svo_ctx *ctx, int item, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
+                                      svo_pt2f *t2_left, uint8_t *inlier, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
+    // item i of a step is pair i of its launch set (an init item has no tracks: n = 0)
+    return svo_get_batch_tracks(ctx, item, t1_left, t1_right, t2_right, t2_left, inlier, cap, n_out);
 }
 
 extern "C" int svo_get_last_tracks(svo_ctx *ctx, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_right,
@@ -1365,15 +1358,7 @@ extern "C" int svo_get_last_tracks(svo_ctx *ctx, svo_pt2f *t1_left, svo_pt2f *t1
     SVO_ARG(n <= cap, "track capacity too small");
     *n_out = n;
     if (n == 0) return SVO_OK;
-    svo_pt2f *dst[4] = {t1_left, t1_right, t2_right, t2_left};
-    for (int k = 0; k < 4; k++) {
-        if (!dst[k]) continue;
-        if (k == 2 && ctx->cfg.track_mode == SVO_MODE_ORB) { memset(dst[k], 0, sizeof(svo_pt2f) * (size_t)n); continue; }
-        SVO_HIP(hipMemcpyAsync(dst[k], ctx->cmp[k], sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (inlier) SVO_HIP(hipMemcpyAsync(inlier, pnp_inlier_mask(ctx), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    return read_tracks(ctx, 0, n, t1_left, t1_right, t2_right, t2_left, inlier);
 }
 
 // ---- FAST corner buckets: the strongest corners per grid cell (fast.hip: fast_bucket_kernel) -------------------------

@@ -23,8 +23,8 @@ struct DevArena {
 };
 
 // A stream set (svo_streams_create): n independent live stereo streams of one context.  What a stream keeps in HBM between
-// steps is what carry_last_frame moves -- seg[k] + id * seg_bytes[k], k < n_seg -- and its frame_pose_ (pose + 16 * id); the
-// INITING / TRACKING state is host-side (steps are issued in host order).
+// steps is the segments stream_segments() lists (pipeline.hip; carry_last_frame moves the same list) -- seg[k] + id * seg_bytes[k],
+// k < n_seg -- and its frame_pose_ (pose + 16 * id); the INITING / TRACKING state is host-side (steps are issued in host order).
 struct StreamSet {
     int n = 0;
     int n_seg = 0;
@@ -118,7 +118,7 @@ struct svo_ctx {
     int *orb_sel = nullptr, *orb_sel_cnt = nullptr, *orb_overflow = nullptr;
     void *orb_kps = nullptr; uint8_t *orb_desc = nullptr; int *orb_n = nullptr; int orb_kp_cap = 0, orb_cand_cap = 0;
     int *orb_midx[2] = {nullptr, nullptr}; float *orb_mdist[2] = {nullptr, nullptr};
-    // ---- pinned host scratch
+    // ---- pinned host scratch: counts and small read-backs at the front, step records from kPinnedRecords on
     void *h_pinned = nullptr; size_t h_pinned_bytes = 0;
     // ---- overlap mode (svo_set_overlap): the pose stage of batch k runs on side_stream while
     //      the caller's stream already ingests / tracks batch k+1
@@ -182,6 +182,7 @@ struct svo_ctx {
     } while (0)
 
 namespace svo {
+constexpr size_t kPinnedRecords = 4096;                 // byte offset of the step records in svo_ctx::h_pinned
 // svo_abi.hip: the context's device memory
 int dev_alloc_raw(svo_ctx *ctx, void **out, size_t bytes);
 template <class T> inline int dev_alloc(svo_ctx *ctx, T **out, size_t bytes) { return dev_alloc_raw(ctx, (void **)out, bytes); }
@@ -189,6 +190,10 @@ int dev_defer(svo_ctx *ctx, std::function<int()> fn);      // runs fn now, or af
 // geometry.hip
 int geom_workspace_bytes(const svo_config &cfg, int n_items, size_t *bytes);
 int geom_workspace_init(svo_ctx *ctx);
+int stage_triangulate(svo_ctx *ctx, const double P1[12], const double P2[12], const svo_pt2f *x1, const svo_pt2f *x2, int n,
+                      svo_pt3f *out, int mem);
+int stage_pnp_ransac(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img, int n, const double K[9], int iterations,
+                     float reproj_err, double confidence, svo_pnp_result *res, uint8_t *inlier_mask, int mem);
 // snap: the frames' keypoint counts / capacity flags to freeze into ctx->kp_n_snap beside the triangulation (null: none)
 struct SnapSpec { const int *n, *ovf; int fp0, fc0, fstep, per; };
 void launch_triangulate_batch(svo_ctx *ctx, int n_items, int max_pts, const float2 *x1, const float2 *x2,
@@ -219,4 +224,20 @@ void launch_finalize_streams(svo_ctx *ctx, int item0, int n_items, int n_pairs, 
 void launch_streams_set_pose(svo_ctx *ctx, int id0, int n, const double *pose_host);    // null: identity
 void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
                            const double *pose0_host, hipStream_t st);      // ctx->seed_dev != null: seed read on the device
+// pipeline.hip: the fused steps.  Their arguments arrive checked -- the rules of each entry-point family are written once, in
+// svo_abi.hip, and run before anything is copied or launched -- and their frames are DEVICE frames of the context's size,
+// already ordered before the context's stream, on the device svo_abi.hip has made current.
+int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, svo_step_result *res);
+int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch, int64_t frame_stride,
+                         int n_frames, const double *pose0, svo_step_result *results, int results_mem, int carry_first);
+int pipeline_streams_create(svo_ctx *ctx, int n_streams);
+int pipeline_streams_reset(svo_ctx *ctx, int id);
+int pipeline_streams_set_pose(svo_ctx *ctx, int id, const double *pose);
+int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose);
+int pipeline_streams_check_ids(svo_ctx *ctx, const int32_t *ids, int m);      // in range, no id twice; nothing launched
+int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
+                          int64_t frame_stride, svo_step_result *results, int results_mem);
+// n step records from device memory to `out`, in the order of stream `st`: SVO_MEM_DEVICE: one copy, nothing waited for
+// (out null: they stay where they are); SVO_MEM_HOST: through the pinned scratch, and `st` is synchronised.
+int deliver_records(svo_ctx *ctx, const svo_step_result *d_src, int n, svo_step_result *out, int mem, hipStream_t st);
 }  // namespace svo

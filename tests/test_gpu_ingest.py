@@ -185,6 +185,44 @@ def test_argument_errors_leave_the_context_alone(pkg, small_seq):
     c.close()
 
 
+def test_refused_ingest_stream_ids_stage_nothing(pkg, synth, tc):
+    """svo_ingest_streams_step with host frames and stream ids it must refuse (twice the same, out of range, more than
+    (max_batch + 1) / 2) answers SVO_ERR_ARG before anything is staged: stream 3, one frame in, goes on exactly as a fresh
+    context fed the same frames alone."""
+    seq, frames = _render(synth, tc, 832, 256, 4)
+    P1, P2 = (pkg.scale_projection(P, 0.5, 0.5, "linear").reshape(12) for P in seq.proj())
+
+    def make():
+        c = pkg.Context(416, 128, device=0, P1=P1, P2=P2, max_batch=4)                      # LK, exact sums: the defaults
+        assert c.cfg.track_mode == pkg.MODE_LK and c.cfg.lk_accum == pkg.LK_ACCUM_EXACT
+        c.ingest_create(832, 256, "linear", 0.5, 0.5)
+        return c
+
+    fresh = make()
+    alone = [fresh.ingest_add_frame(*frames[t])[1] for t in range(3)]
+    fresh.close()
+    _all_ok(alone)
+    c = make()
+    c.streams_create(4)
+    L, R = [f[0] for f in frames], [f[1] for f in frames]
+    _same(c.ingest_streams_step([3], L[:1], R[:1])[0], alone[0], "stream 3, frame 0")
+    for bad_ids in ([3, 3], [4], [-1], [0, 1, 2]):
+        m = len(bad_ids)
+        ids = np.asarray(bad_ids, np.int32)
+        fl, fr = np.stack([L[1]] * m), np.stack([R[1]] * m)
+        out = np.zeros(m, dtype=pkg.STEP_DTYPE)
+        rc = c.lib.svo_ingest_streams_step(c.h, ctypes.c_void_p(ids.ctypes.data), m, ctypes.c_void_p(fl.ctypes.data),
+                                           ctypes.c_void_p(fr.ctypes.data), 832, 832 * 256, pkg.MEM_HOST,
+                                           ctypes.c_void_p(out.ctypes.data), pkg.MEM_HOST)
+        assert rc == ERR_ARG, (bad_ids, rc)
+        assert not out.tobytes().strip(b"\0"), bad_ids
+    _same(c.ingest_streams_step([3], L[1:2], R[1:2])[0], alone[1], "stream 3, frame 1")
+    got = c.ingest_streams_step([1, 3], [L[0], L[2]], [R[0], R[2]])
+    _same(got[0], alone[0], "stream 1, frame 0")
+    _same(got[1], alone[2], "stream 3, frame 2")
+    c.close()
+
+
 # ---- g. the contract: svo_ingest_X == svo_X on _resize_ref frames -----------------------------------------------------------
 #        (dw, dh, interp, f) for 832 x 256 sources
 GEOMS = [(416, 128, "nearest", 0.5), (416, 128, "linear", 0.5), (499, 154, "linear", 0.0)]
