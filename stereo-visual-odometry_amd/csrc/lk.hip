@@ -4,8 +4,8 @@
 // as called four times per frame by Tracking::LK_Robust_Find_MuliImage_MatchedFeatures
 // (reference src/tracking.cpp:583-622), plus the deleteBadmatchFeatures predicate (:623-660).
 //
-// Mapping: ONE WAVEFRONT TRACKS FOUR POINTS ("slots"), four waves per workgroup, no workgroup
-// barrier.  The kernel is VALU-issue bound (tiles come from L2), and more than half of a
+// Mapping: ONE WAVEFRONT TRACKS FOUR POINTS ("slots"), ONE WAVE PER WORKGROUP (kLkWavesPerWg; four in
+// the latency shape), no barrier.  The kernel is VALU-issue bound (tiles come from L2), and more than half of a
 // one-point-per-wave iteration is per-point SCALAR work (window position, bilinear weights, 2x2
 // solve, convergence tests) that a wave executes as full vector instructions.  Here that scalar work
 // is done once for four points: lane l carries the control state of slot l >> 4 (its row of 16
@@ -28,7 +28,10 @@
 //     slot s's four sums in every quad of row s, exactly where that slot's control lanes need them.
 // With ncalls == 4 the wave walks the whole circular chain L1 -> R1 -> R2 -> L2 -> L1' for its
 // four points and stops early once all of them are rejected.  The column-word J tiles cost 4x the
-// LDS of byte tiles (52 KB per workgroup): three waves per SIMD, 168 VGPRs.
+// LDS of byte tiles (13 KB per wave): three waves per SIMD, 168 VGPRs.  A wave's life varies 2x with the
+// iteration counts of its points, so a throughput launch's workgroup is ONE wave: it gives its LDS back the
+// moment it ends and the dispatcher starts the next one (four-wave workgroups hold 52 KB until their slowest
+// wave has ended).
 //
 // Exactness: all pixel arithmetic is upstream's fixed point (14-bit weights, 5 fractional bits);
 // the five sums A11,A12,A22,b1,b2 are accumulated as exact integers (per-lane int32 partials,
@@ -433,17 +436,34 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
     LK_CALL_END(lane);
 }
 
-// Grid: ONE dimension, a.gx workgroups per batch item; the workgroups of an item walk its points in
-// strides of a.gx * 16 (four waves x four slots), so the launch is sized from the batch, not from
-// the keypoint CAPACITY (cv::FAST is uncapped and the capacity is generous: a grid of capacity / 16
-// workgroups per item was mostly empty waves).  XCD-aware mapping: consecutive workgroup ids go
+// Waves per workgroup (4, 2 or 1; -DSVO_LK_WAVES_PER_WG=k for A/B builds).  The waves of a workgroup share
+// nothing but the LDS allocation, and a workgroup gives its LDS back only when its SLOWEST wave has ended:
+// with four waves the slots of the finished ones stay empty until then, because no other workgroup fits
+// beside 3 x 52 KB.  With single-wave workgroups the hardware dispatcher is the
+// work queue: a wave that ends frees its LDS at once and the next one starts.
+#ifndef SVO_LK_WAVES_PER_WG
+#define SVO_LK_WAVES_PER_WG 1
+#endif
+constexpr int kLkWavesPerWg = SVO_LK_WAVES_PER_WG;
+static_assert(kLkWavesPerWg == 4 || kLkWavesPerWg == 2 || kLkWavesPerWg == 1, "lk_kernel: 4, 2 or 1 waves per workgroup");
+// The latency shape (launches of fewer than 4 items) stays at four: LDS is handed out in 1280-byte granules
+// (tools/gpu/lds_granule_probe.hip), so a lone wave's 12 992 B take 14 080 and only ELEVEN fit into a CU's
+// 160 KB where three four-wave workgroups hold twelve.  A throughput launch gains more from the early hand-back
+// than it loses with the twelfth wave; a launch whose waves all start at once only loses (stream k = 2: -3 %).
+constexpr int kLkSpreadWavesPerWg = 4;
+
+// Grid: ONE dimension, a.gx workgroups of W waves per batch item; the waves of an item walk its
+// points in strides of a.gx * W * 4 (waves x four slots), so the launch is sized from the batch,
+// not from the keypoint CAPACITY (cv::FAST is uncapped and the capacity is generous: a grid of capacity / 16
+// workgroups of four per item was mostly empty waves).  XCD-aware mapping: consecutive workgroup ids go
 // round-robin to the 8 XCDs, each with its own 4 MB L2, so item = (id / 8 / gx) * 8 + id % 8 keeps
 // every XCD on its own items -- an XCD then has about one item's four pyramids (3.3 MB) in flight
 // instead of slices of all items that are in flight anywhere on the chip (L2 hit rate 63 % -> see
 // DESIGN.md).  No workgroup barrier anywhere: each wave loops on its own.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void lk_kernel(LkArgs a)
+template <int W>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(3, 3))) void lk_kernel(LkArgs a)
 {
-    __shared__ uint32_t lds[4 * kLdsDwPerWave];
+    __shared__ uint32_t lds[W * kLdsDwPerWave];
     // items in whole groups of 8 are dealt one per XCD; the last (batch % 8) items -- the single pair of
     // the online path among them -- are spread over all XCDs in the plain order
     const int n_aware = (a.batch & ~7) * a.gx;
@@ -455,7 +475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const int r = blockIdx.x - n_aware;
         b = (a.batch & ~7) + r / a.gx; bx = r % a.gx;
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = W == 1 ? 0 : (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int slot = lane >> 4;
     int n = a.n_pts ? a.n_pts[b] : a.n_fixed;
     n = min(n, a.cap);
@@ -464,8 +484,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     // four points); a launch of a few items only (the online path: one pair) is latency-bound -- there the
     // points are spread over as many waves as the grid has, down to one point per wave
     int spw = kSlots;
-    if (a.spread) spw = min(kSlots, max(1, (n + a.gx * 4 - 1) / (a.gx * 4)));
-    for (int first = (bx * 4 + wave) * spw; first < n; first += a.gx * 4 * spw) {
+    if (a.spread) spw = min(kSlots, max(1, (n + a.gx * W - 1) / (a.gx * W)));
+    for (int first = (bx * W + wave) * spw; first < n; first += a.gx * W * spw) {
         const int idx = first + slot;
         const bool valid = slot < spw && idx < n;
         const bool writer = valid && lane == 16 * slot;         // one lane per slot stores results
@@ -554,21 +574,23 @@ void launch_lk(const LkArgs &a0, int batch, int max_pts, hipStream_t st)
 {
     if (max_pts <= 0 || batch <= 0) return;
     if (a0.accum != 0) { launch_lk_sse2(a0, batch, max_pts, st); return; }      // SVO_LK_ACCUM_SSE2 / _SIMD128: the float-order kernel
-    // up to 192 workgroups per item (3072 points per pass: a KITTI frame's ~2.5 k corners in one pass,
-    // a few workgroups leave at once; denser frames loop), never more than capacity / 16
-    const int chunks = (max_pts + 4 * kSlots - 1) / (4 * kSlots);
+    // up to 768 waves per item (3072 points per pass: a KITTI frame's ~2.5 k corners in one pass, a few
+    // waves leave at once; denser frames loop), never more than capacity / 4
+    constexpr int W = kLkWavesPerWg;
+    const int chunks = (max_pts + W * kSlots - 1) / (W * kSlots);
     LkArgs a = a0;
-    a.gx = chunks < 192 ? chunks : 192;
+    a.gx = chunks < 768 / W ? chunks : 768 / W;
     a.spread = 0;
-    if (batch < 4) {                             // fewer than 768 workgroups: 3 per CU are resident at once
+    a.batch = batch;
+    if (batch < 4) {                             // fewer than 768 workgroups of four: 3 per CU are resident at once
         static const int room_all = getenv("SVO_LK_SPREAD_ROOM") ? atoi(getenv("SVO_LK_SPREAD_ROOM")) : 768;     // test hook (A/B runs)
         const int wide = (max_pts + 3) / 4, room = room_all / batch;
         a.gx = wide < room ? wide : room;
         a.spread = 1;
+        hipLaunchKernelGGL(lk_kernel<kLkSpreadWavesPerWg>, dim3(batch * a.gx), dim3(64 * kLkSpreadWavesPerWg), 0, st, a);
+        return;
     }
-    a.batch = batch;
-    dim3 grid(batch * a.gx, 1, 1), blk(256, 1, 1);
-    hipLaunchKernelGGL(lk_kernel, grid, blk, 0, st, a);
+    hipLaunchKernelGGL(lk_kernel<W>, dim3(batch * a.gx), dim3(64 * W), 0, st, a);
 }
 
 void launch_compact(const CompactArgs &a, int batch, hipStream_t st)

@@ -51,6 +51,9 @@ out = {
     "grbm_gui_active": vals.get("GRBM_GUI_ACTIVE"),
     # shader clock during the launch: GRBM_GUI_ACTIVE sums the busy cycles of the 8 XCDs
     "clock_ghz_measured": (round(vals["GRBM_GUI_ACTIVE"] / 8 / avg_ns, 4) if vals.get("GRBM_GUI_ACTIVE") and avg_ns else None),
+    # SQ_WAVE_CYCLES counts quad-cycles; 1024 SIMDs are busy for GRBM_GUI_ACTIVE / 8 cycles
+    "mean_resident_waves_per_simd": (round(4 * vals["SQ_WAVE_CYCLES"] / (vals["GRBM_GUI_ACTIVE"] / 8 * 1024), 3)
+                                     if vals.get("SQ_WAVE_CYCLES") and vals.get("GRBM_GUI_ACTIVE") else None),
     "valu_peak_wave_instr_per_cycle_per_simd": 0.246,
     "valu_peak_source": "profiles/r02_valu_roof.txt: v_dot2_i32_i16, v_perm_b32, v_alignbyte_b32, v_pk_*, DPP, v_cndmask, v_readlane "
                         "all issue one wave-instruction per 4.06-4.2 cycles per SIMD at 2-8 waves per SIMD (plain 32-bit add/and/shift: 2.03-2.3)",
