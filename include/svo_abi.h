@@ -471,6 +471,63 @@ int svo_get_fast_buckets(const svo_ctx *ctx, int *cell_w, int *cell_h, int *per_
 int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, int width, int height,
                        int cell_w, int cell_h, int per_cell, svo_keypoint *out, int cap, int *n_out, int mem);
 
+/* ---- Shi-Tomasi corners: cv::goodFeaturesToTrack as the LK-mode detector (additive; detected by symbol, the ABI version
+ * stays 9 and svo_config is unchanged) -------------------------------------------------------------------------------------
+ * The detector the reference's author prepared and never called: cv::GFTTDetector::create(num_features, 0.01, 20)
+ * (src/tracking.cpp:18,41), i.e. cv::goodFeaturesToTrack(img, maxCorners, qualityLevel, minDistance, noArray(), 3, false,
+ * 0.04).  A bounded, strength-ordered corner set spaced at least minDistance apart.  The default detector stays cv::FAST.
+ *
+ * Semantics (restated from memory of OpenCV 3.4, unpinned; every choice is listed in DESIGN.md section 2; the numpy twin is
+ * tests/_gftt_ref.py).  float32 with one rounding per operation (no fused multiply-add) unless stated; s = float(1/(4*3*255)),
+ * f0 = 2s, f1 = s; image border reflect-101.
+ *   1. dx: r = p[x+1] - p[x-1] in integers, dx = float(r[y])*f0 + float(r[y-1] + r[y+1])*f1.
+ *   2. dy: q = float(p[x])*f0 + float(p[x-1] + p[x+1])*f1, dy = q[y+1] - q[y-1].
+ *   3. cxx = dx*dx, cxy = dx*dy, cyy = dy*dy.
+ *   4. Sxx, Sxy, Syy: 3x3 unnormalised box sums, accumulated in double -- the three products of a row first, (p0 + p1) + p2, then
+ *      the rows, (r0 + r1) + r2 -- and rounded once; the border is reflect-101 OF THE
+ *      COVARIANCE MAPS (c(-1, y) := c(1, y)), not the covariance of the reflected image.
+ *   5. a = Sxx*0.5f, b = Sxy, c = Syy*0.5f; eig = (a + c) - sqrtf((a - c)*(a - c) + b*b), correctly rounded sqrt; tiny
+ *      negative values are kept.
+ *   6. thr = float(double(max eig over the image) * double(qualityLevel)).
+ *   7. Candidates: 1 <= x <= w-2, 1 <= y <= h-2, eig > thr, eig >= all eight neighbours.
+ *   8. Order: eig descending, ties to the LARGER raster index y*w + x first.
+ *   9. minDistance >= 1: cell = cvRound(minDistance) (half to even), grid of ceil(w/cell) x ceil(h/cell) cells; a candidate is
+ *      dropped when a kept corner in its 3x3 cell neighbourhood has integer dx*dx + dy*dy < double(minDistance)^2, else kept;
+ *      stop at maxCorners when maxCorners > 0.  minDistance < 1: the first maxCorners of the order.  maxCorners <= 0: uncapped.
+ *  10. Output in SELECTION order (strongest first), each the record GFTTDetector::detect makes: (x, y, size 3, angle -1,
+ *      response 0, octave 0, class_id -1).
+ *   svo_set_lk_detector : LK mode.  Applies to frames whose corners are detected by LATER calls on every fused entry point
+ *       (svo_add_frame, svo_track_batch, svo_track_uploaded(_async), svo_streams_step and their svo_ingest_* twins): a frame
+ *       already detected (svo_add_frame's previous frame, a stream's stored frame, a carried frame) keeps its corners.
+ *       n_prev_kps / n_cur_kps, the < 30 gate, svo_get_frame_keypoints (records as in 10) and the tracks read-backs see the kept
+ *       set.  An image with more CANDIDATES (step 7) than svo_config.max_keypoints gets no list and its pairs end in
+ *       SVO_FAIL_CAPACITY.  SVO_DETECTOR_FAST switches back; the other arguments are ignored.  SVO_ERR_ARG (nothing changes):
+ *       an ORB-mode context; an unknown detector; quality_level not in (0, inf) or not finite; min_distance negative, not
+ *       finite, or >= 1 with more than 16384 grid cells at the context's size; SVO_DETECTOR_GFTT while the FAST buckets are on or
+ *       svo_config.fast_keep_strongest > 0 -- and svo_set_fast_buckets with per_cell > 0 while the detector is GFTT.
+ *       Memory: allocated by the first call that selects SVO_DETECTOR_GFTT (that call, and one that needs more, waits for the
+ *       device), per working frame (max_batch + 1 of them) one float per pixel (rows of align64(width)) -- the eigenvalue where
+ *       the pixel is a candidate before the threshold -- 8 bytes per max_keypoints rounded up to a power of two, and 16 bytes per
+ *       grid cell where the grid has more than 1536 cells (1241 x 376, max_batch = 256, max_keypoints = 8192: 512 MB).  A
+ *       context that never selects it allocates and pays nothing.
+ *   svo_get_lk_detector : what is set (max_corners, quality_level, min_distance 0 while the detector is FAST).  Any pointer may
+ *       be NULL.
+ *   svo_min_eigen_map (stage API): steps 1-5 of one width x height image (1..16384 each), independent of the context's frame
+ *       size and mode.  `mem` says where img AND out live; SVO_MEM_DEVICE: in stream order on the context's stream, no host
+ *       synchronisation; SVO_MEM_HOST: returns when out is complete.  Floats of an out row beyond width are not written.
+ *   svo_gftt_detect (stage API): steps 1-10.  `mem` says where img, out, strength AND n_out live.  out receives the records,
+ *       strength (may be NULL) the eigenvalue of each, *n_out the count.  More candidates (step 7) than cap: nothing is listed
+ *       and *n_out is the candidate count; SVO_MEM_HOST returns SVO_ERR_ARG then (SVO_MEM_DEVICE cannot know: compare *n_out
+ *       with cap).  Device scratch grows on demand (a call that grows it waits for the device). */
+#define SVO_DETECTOR_FAST 0
+#define SVO_DETECTOR_GFTT 1
+int svo_set_lk_detector(svo_ctx *ctx, int detector, int max_corners, double quality_level, double min_distance);
+int svo_get_lk_detector(const svo_ctx *ctx, int *detector, int *max_corners, double *quality_level, double *min_distance);
+int svo_min_eigen_map(svo_ctx *ctx, const uint8_t *img, int width, int height, int pitch, int mem, float *out, int out_pitch_floats);
+int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int height, int pitch, int mem,
+                    int max_corners, double quality_level, double min_distance,
+                    svo_keypoint *out, float *strength, int cap, int *n_out);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

@@ -32,6 +32,7 @@ class Config(C.Structure):
 
 
 MODE_LK, MODE_ORB = 0, 1
+DETECTOR_FAST, DETECTOR_GFTT = 0, 1                                                         # svo_set_lk_detector
 INTERP_NEAREST, INTERP_LINEAR = 0, 1                                                        # svo_resize / svo_ingest_create
 LK_ACCUM_EXACT, LK_ACCUM_SSE2, LK_ACCUM_SIMD128, LK_ACCUM_SSE2_LEGACY = 0, 1, 2, 3          # svo_config.lk_accum
 
@@ -135,6 +136,13 @@ def load_library():
     lib.svo_get_fast_buckets.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.svo_bucket_corners.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    # Shi-Tomasi corners (additive entry points, like the stream sets)
+    lib.svo_set_lk_detector.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+    lib.svo_get_lk_detector.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)]
+    lib.svo_min_eigen_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.svo_gftt_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -497,6 +505,74 @@ class Context:
         if ordered:
             self._order_out(out)
         return out, m
+
+    # ---- Shi-Tomasi corners (svo_set_lk_detector / svo_min_eigen_map / svo_gftt_detect) ------------
+    def set_lk_detector(self, detector, max_corners=500, quality_level=0.01, min_distance=20.0):
+        """LK mode: the detector of the frames detected by later calls -- "fast" (the default; the other arguments are
+        ignored) or "gftt", cv::goodFeaturesToTrack(img, max_corners, quality_level, min_distance)."""
+        if isinstance(detector, str):
+            if detector not in ("fast", "gftt"):
+                raise ValueError(f"detector must be 'fast' or 'gftt', not {detector!r}")
+            detector = DETECTOR_GFTT if detector == "gftt" else DETECTOR_FAST
+        self._check(self.lib.svo_set_lk_detector(self.h, int(detector), int(max_corners), float(quality_level), float(min_distance)))
+
+    def lk_detector(self):
+        """("fast" | "gftt", max_corners, quality_level, min_distance) as set; ("fast", 0, 0.0, 0.0) while FAST."""
+        d, n, q, m = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
+        self._check(self.lib.svo_get_lk_detector(self.h, C.byref(d), C.byref(n), C.byref(q), C.byref(m)))
+        return ("gftt" if d.value == DETECTOR_GFTT else "fast"), n.value, q.value, m.value
+
+    def _img_any(self, img):
+        """(pointer, width, height, row pitch, memory kind, is numpy) of a u8 image of any size; rows may be padded."""
+        h, w = (int(v) for v in img.shape)
+        p, pitch, mem = self._img(img, (h, w))
+        return p, w, h, pitch, mem, isinstance(img, np.ndarray)
+
+    def min_eigen_map(self, img):
+        """svo_min_eigen_map: the minimal-eigenvalue map (float32, h x w) of a u8 image of any size -- numpy in, numpy out;
+        cuda tensor in, cuda tensor out (stream order, no host synchronisation)."""
+        p, w, h, pitch, mem, is_np = self._img_any(img)
+        if mem == MEM_HOST:
+            out = np.zeros((h, w), np.float32)
+            self._check(self.lib.svo_min_eigen_map(self.h, p, w, h, pitch, MEM_HOST, C.c_void_p(out.ctypes.data), w))
+            if is_np:
+                return out
+            import torch
+            return torch.from_numpy(out)
+        import torch
+        out = torch.zeros((h, w), dtype=torch.float32, device=img.device)
+        ordered = self._order_in(out)
+        self._check(self.lib.svo_min_eigen_map(self.h, p, w, h, pitch, MEM_DEVICE, C.c_void_p(out.data_ptr()), w))
+        if ordered:
+            self._order_out(out)
+        return out
+
+    def gftt_detect(self, img, max_corners=500, quality_level=0.01, min_distance=20.0, cap=None):
+        """svo_gftt_detect on a u8 image of any size.  numpy (host) image: returns (KP_DTYPE records in selection order,
+        float32 strengths).  cuda tensor: returns (uint8 tensor of cap * KP_DTYPE.itemsize bytes, float32 tensor of cap
+        strengths, int32 count tensor), filled in stream order without a host synchronisation; a count above cap means
+        more candidates than cap and no list."""
+        p, w, h, pitch, mem, is_np = self._img_any(img)
+        cap = int(self.cfg.max_keypoints if cap is None else cap)
+        if mem == MEM_HOST:
+            out = np.zeros(max(cap, 1), dtype=KP_DTYPE)
+            strength = np.zeros(max(cap, 1), np.float32)
+            n = C.c_int(0)
+            self._check(self.lib.svo_gftt_detect(self.h, p, w, h, pitch, MEM_HOST, int(max_corners), float(quality_level),
+                                                 float(min_distance), C.c_void_p(out.ctypes.data), C.c_void_p(strength.ctypes.data),
+                                                 cap, C.cast(C.byref(n), C.c_void_p)))
+            return out[:n.value].copy(), strength[:n.value].copy()
+        import torch
+        out = torch.zeros(max(cap, 1) * KP_DTYPE.itemsize, dtype=torch.uint8, device=img.device)
+        strength = torch.zeros(max(cap, 1), dtype=torch.float32, device=img.device)
+        n = torch.zeros(1, dtype=torch.int32, device=img.device)
+        ordered = self._order_in(out)
+        self._check(self.lib.svo_gftt_detect(self.h, p, w, h, pitch, MEM_DEVICE, int(max_corners), float(quality_level),
+                                             float(min_distance), C.c_void_p(out.data_ptr()), C.c_void_p(strength.data_ptr()),
+                                             cap, C.c_void_p(n.data_ptr())))
+        if ordered:
+            self._order_out(out)
+        return out, strength, n
 
     # ---- cv::resize and the ingest stage (svo_resize / svo_ingest_*) -------------------------------
     def resize(self, src, dw, dh, interp="nearest", fx=0, fy=0, out=None):

@@ -52,6 +52,12 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
     p.img = L; p.img2 = R; p.slots = ctx->bslots + (size_t)(2 * f0) * g.slot_bytes;
     launch_pyramid(p, 2 * n_new, ctx->stream);
     mark(ctx, kTPyr);
+    if (ctx->lk_detector == SVO_DETECTOR_GFTT) {
+        // svo_set_lk_detector: cv::goodFeaturesToTrack instead of cv::FAST (the buckets and fast_keep_strongest are excluded with it)
+        const int rc = gftt_detect_frames(ctx, L, pitch, frame_stride, f0, n_new);
+        mark(ctx, kTFast);
+        return rc;
+    }
     FastArgs a{};
     a.img = L; a.pitch = pitch; a.img_stride = frame_stride;
     a.w = ctx->cfg.width; a.h = ctx->cfg.height; a.thr = ctx->cfg.fast_threshold; a.nms = 1;

@@ -130,6 +130,8 @@ static void free_all(svo_ctx *c)
     if (c->ingest.src_stage) (void)hipFree(c->ingest.src_stage);
     if (c->bucket_cells) (void)hipFree(c->bucket_cells);
     if (c->bucket_stage) (void)hipFree(c->bucket_stage);
+    if (c->gftt_fused.base) (void)hipFree(c->gftt_fused.base);
+    if (c->gftt_stage.base) (void)hipFree(c->gftt_stage.base);
     if (c->ev_front) (void)hipEventDestroy(c->ev_front);
     if (c->ev_back) (void)hipEventDestroy(c->ev_back);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -1293,9 +1295,13 @@ extern "C" int svo_get_frame_keypoints(svo_ctx *ctx, int side, svo_keypoint *kps
         SVO_HIP(hipMemcpyAsync(xy.data(), ctx->kp_xy + (size_t)cur * kcap, sizeof(float2) * n, hipMemcpyDeviceToHost, ctx->stream));
         SVO_HIP(hipMemcpyAsync(resp.data(), ctx->kp_resp + (size_t)cur * kcap, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
         SVO_HIP(hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < n; i++) {                   // the cv::KeyPoint cv::FAST produces
-            kps[i].x = xy[i].x; kps[i].y = xy[i].y; kps[i].size = 7.f; kps[i].angle = -1.f;
-            kps[i].response = resp[i]; kps[i].octave = 0; kps[i].class_id = -1;
+        // the cv::KeyPoint cv::FAST produces (response = its score), or the one cv::GFTTDetector makes (size 3, response 0) where
+        // kp_resp carries the Shi-Tomasi tag, a value no FAST score takes (gftt.hip): a frame keeps the records of the detector
+        // that made them when svo_set_lk_detector switches between two frames
+        for (int i = 0; i < n; i++) {
+            const bool gftt = resp[i] == gftt_resp_tag();
+            kps[i].x = xy[i].x; kps[i].y = xy[i].y; kps[i].size = gftt ? 3.f : 7.f; kps[i].angle = -1.f;
+            kps[i].response = gftt ? 0.f : resp[i]; kps[i].octave = 0; kps[i].class_id = -1;
         }
     }
     *n_out = n;
@@ -1375,6 +1381,7 @@ extern "C" int svo_set_fast_buckets(svo_ctx *ctx, int cell_w, int cell_h, int pe
     SVO_ARG(per_cell >= 0, "per_cell < 0");
     if (per_cell == 0) { ctx->bucket_keep = 0; return SVO_OK; }      // off: the sizes are ignored
     SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "FAST buckets are an LK-mode option (ORB mode spreads its keypoints with the quadtree)");
+    SVO_ARG(ctx->lk_detector != SVO_DETECTOR_GFTT, "FAST buckets cannot be combined with the Shi-Tomasi detector (svo_set_lk_detector): it spaces its own corners");
     SVO_ARG(cell_w >= 1 && cell_h >= 1, "cell_w / cell_h < 1");
     const int64_t ncells = bucket_cell_count(ctx->cfg.width, ctx->cfg.height, cell_w, cell_h);
     SVO_ARG(ncells <= kMaxBucketCells, "more than 16384 cells per image");
@@ -1451,6 +1458,201 @@ extern "C" int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, i
     *n_out = m;
     if (m > 0) {
         SVO_HIP(hipMemcpyAsync(out, d_out, sizeof(svo_keypoint) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        SVO_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SVO_OK;
+}
+
+// ---- Shi-Tomasi corners: cv::goodFeaturesToTrack as the LK-mode detector and as stage calls (gftt.hip) ----------------
+static int gftt_cell_of(double min_distance) { return min_distance >= 1.0 ? (int)nearbyint(min_distance) : 0; }   // cvRound: half to even
+
+// Scratch for n images of w x h pixels with `cap` candidates each and a grid of ncells cells (+ `extra` bytes at the end,
+// returned in *extra_at): allocated when it has to grow (that call waits for the device), cut up on every call.
+// with_lists false: the per-image words only (svo_min_eigen_map writes its map where the caller says).
+static int gftt_plan(svo_ctx *ctx, GfttBuf &g, int w, int h, int n, int cap, int64_t ncells, size_t extra, uint8_t **extra_at,
+                     bool with_lists = true)
+{
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    int64_t ks = 64;
+    while (ks < cap) ks <<= 1;
+    const int mpitch = align_up(w, 64);
+    const bool dev_cells = ncells > gftt_lds_cells();
+    const size_t o_max = 0, o_cnt = up(sizeof(unsigned) * (size_t)n), o_map = o_cnt + up(sizeof(int) * (size_t)n),
+                 o_keys = o_map + (with_lists ? up(sizeof(float) * (size_t)mpitch * h * n) : 0),
+                 o_cells = o_keys + (with_lists ? up(sizeof(unsigned long long) * (size_t)ks * n) : 0),
+                 o_extra = o_cells + (dev_cells ? up(sizeof(int) * 4 * (size_t)ncells * n) : 0), bytes = o_extra + up(extra);
+    if (bytes > g.bytes) {
+        // the larger block first: a call that cannot get it leaves the scratch, and with it the context, as it was
+        uint8_t *grown = nullptr;
+        SVO_HIP(hipMalloc((void **)&grown, bytes));
+        uint8_t *old = g.base;
+        g.base = grown; g.bytes = bytes;
+        if (old) (void)hipFree(old);                           // (waits for the launches that still use it; the new block is in place either way)
+    }
+    g.maxkey = (unsigned *)(g.base + o_max); g.n_cand = (int *)(g.base + o_cnt);
+    g.map = with_lists ? (float *)(g.base + o_map) : nullptr; g.mpitch = mpitch; g.map_stride = (int64_t)mpitch * h;
+    g.keys = with_lists ? (unsigned long long *)(g.base + o_keys) : nullptr; g.keys_stride = ks;
+    g.cells = dev_cells ? (int *)(g.base + o_cells) : nullptr; g.cells_stride = dev_cells ? 4 * ncells : 0;
+    if (extra_at) *extra_at = g.base + o_extra;
+    return SVO_OK;
+}
+
+// the detector's parameters into a launch block (the image, the scratch and the outputs are the caller's to fill)
+static void gftt_params(GfttArgs &a, const GfttBuf &g, int w, int h, int cap, int max_corners, double quality, double min_distance)
+{
+    a.w = w; a.h = h; a.cap = cap;
+    a.map = g.map; a.mpitch = g.mpitch; a.map_stride = g.map_stride; a.full = 0;
+    a.maxkey = g.maxkey; a.n_cand = g.n_cand; a.keys = g.keys; a.keys_stride = g.keys_stride;
+    a.quality = quality; a.min_dist2 = min_distance * min_distance; a.max_corners = max_corners;
+    a.cell = gftt_cell_of(min_distance);
+    a.gcols = a.cell > 0 ? (w + a.cell - 1) / a.cell : 0; a.grows = a.cell > 0 ? (h + a.cell - 1) / a.cell : 0;
+    a.ncells = a.gcols * a.grows;
+    a.cells = g.cells; a.cells_stride = g.cells_stride;
+}
+
+static int64_t gftt_cell_count(int w, int h, double min_distance)
+{
+    const int cell = gftt_cell_of(min_distance);
+    return cell > 0 ? (int64_t)((w + cell - 1) / cell) * ((h + cell - 1) / cell) : 0;
+}
+
+namespace svo {
+// pipeline.hip: the detector of the fused LK front end -- n_new left images -> kp_xy / kp_resp / kp_n of frame slots f0 ..
+int gftt_detect_frames(svo_ctx *ctx, const uint8_t *L, int pitch, int64_t frame_stride, int f0, int n_new)
+{
+    GfttArgs a{};
+    const int cap = ctx->cfg.max_keypoints;
+    gftt_params(a, ctx->gftt_fused, ctx->cfg.width, ctx->cfg.height, cap, ctx->gftt_max_corners, ctx->gftt_quality, ctx->gftt_min_distance);
+    a.img = L; a.pitch = pitch; a.img_stride = frame_stride;
+    a.kp_xy = ctx->kp_xy + (size_t)f0 * cap; a.kp_resp = ctx->kp_resp + (size_t)f0 * cap; a.strength = nullptr; a.kp_stride = cap;
+    a.n_out = ctx->kp_n + f0;
+    // (stage marks of svo_get_timing: the detector stage is gftt_eigen + gftt_emit + the caller's `fast` mark, which ends the select)
+    SVO_HIP(launch_gftt_eigen(a, n_new, ctx->stream));
+    timing_mark(ctx, "gftt_eigen");
+    SVO_HIP(launch_gftt_emit(a, n_new, ctx->stream));
+    timing_mark(ctx, "gftt_emit");
+    SVO_HIP(launch_gftt_select(a, n_new, ctx->stream));
+    return SVO_OK;
+}
+}  // namespace svo
+
+extern "C" int svo_set_lk_detector(svo_ctx *ctx, int detector, int max_corners, double quality_level, double min_distance)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "the detector switch is an LK-mode option (ORB mode has its own extractor)");
+    if (detector == SVO_DETECTOR_FAST) { ctx->lk_detector = SVO_DETECTOR_FAST; return SVO_OK; }      // the other arguments are ignored
+    SVO_ARG(detector == SVO_DETECTOR_GFTT, "detector must be SVO_DETECTOR_FAST or SVO_DETECTOR_GFTT");
+    SVO_ARG(std::isfinite(quality_level) && quality_level > 0.0, "quality_level must be finite and > 0");
+    SVO_ARG(std::isfinite(min_distance) && min_distance >= 0.0, "min_distance must be finite and >= 0");
+    const int64_t ncells = gftt_cell_count(ctx->cfg.width, ctx->cfg.height, min_distance);
+    SVO_ARG(ncells <= kMaxBucketCells, "min_distance gives more than 16384 grid cells per image");
+    SVO_ARG(ctx->bucket_keep == 0, "the Shi-Tomasi detector cannot be combined with the FAST buckets (svo_set_fast_buckets)");
+    SVO_ARG(ctx->cfg.fast_keep_strongest == 0, "the Shi-Tomasi detector cannot be combined with svo_config.fast_keep_strongest");
+    SVO_HIP(hipSetDevice(ctx->device));
+    const int rc = gftt_plan(ctx, ctx->gftt_fused, ctx->cfg.width, ctx->cfg.height, ctx->n_img, ctx->cfg.max_keypoints, ncells, 0, nullptr);
+    if (rc) return rc;                                   // (the scratch and the detector are what they were)
+    ctx->lk_detector = SVO_DETECTOR_GFTT;
+    ctx->gftt_max_corners = max_corners; ctx->gftt_quality = quality_level; ctx->gftt_min_distance = min_distance;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_lk_detector(const svo_ctx *ctx, int *detector, int *max_corners, double *quality_level, double *min_distance)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    const bool on = ctx->lk_detector == SVO_DETECTOR_GFTT;
+    if (detector) *detector = ctx->lk_detector;
+    if (max_corners) *max_corners = on ? ctx->gftt_max_corners : 0;
+    if (quality_level) *quality_level = on ? ctx->gftt_quality : 0.0;
+    if (min_distance) *min_distance = on ? ctx->gftt_min_distance : 0.0;
+    return SVO_OK;
+}
+
+extern "C" int svo_min_eigen_map(svo_ctx *ctx, const uint8_t *img, int width, int height, int pitch, int mem, float *out, int out_pitch_floats)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(img && out, "null pointer");
+    SVO_ARG(width >= 1 && height >= 1 && width <= 16384 && height <= 16384, "width / height out of range");
+    SVO_ARG(pitch >= width && out_pitch_floats >= width, "pitch < width");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "mem must be SVO_MEM_HOST or SVO_MEM_DEVICE");
+    SVO_HIP(hipSetDevice(ctx->device));
+    const bool host = mem == SVO_MEM_HOST;
+    const int dpitch = align_up(width, 256);
+    uint8_t *d_img = nullptr;
+    GfttBuf &g = ctx->gftt_stage;
+    // a device `out` is written in place: only the per-image words are needed then
+    int rc = gftt_plan(ctx, g, width, height, 1, 64, 0, host ? (size_t)dpitch * height : 0, &d_img, /*with_lists*/ host);
+    if (rc) return rc;
+    GfttArgs a{};
+    gftt_params(a, g, width, height, 64, 0, 1.0, 0.0);
+    a.full = 1;
+    if (host) {
+        SVO_HIP(hipMemcpy2DAsync(d_img, (size_t)dpitch, img, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice, ctx->stream));
+        a.img = d_img; a.pitch = dpitch;
+    } else {
+        a.img = img; a.pitch = pitch; a.map = out; a.mpitch = out_pitch_floats;
+    }
+    SVO_HIP(launch_gftt_eigen(a, 1, ctx->stream));
+    SVO_HIP(hipGetLastError());
+    if (!host) return SVO_OK;
+    SVO_HIP(hipMemcpy2DAsync(out, sizeof(float) * (size_t)out_pitch_floats, g.map, sizeof(float) * (size_t)g.mpitch, sizeof(float) * (size_t)width,
+                             (size_t)height, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
+extern "C" int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int height, int pitch, int mem, int max_corners,
+                               double quality_level, double min_distance, svo_keypoint *out, float *strength, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(img && n_out && cap >= 0 && cap <= (1 << 24) && (out || cap == 0), "null pointer / bad cap");
+    SVO_ARG(width >= 1 && height >= 1 && width <= 16384 && height <= 16384, "width / height out of range");
+    SVO_ARG(pitch >= width, "pitch < width");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "mem must be SVO_MEM_HOST or SVO_MEM_DEVICE");
+    SVO_ARG(std::isfinite(quality_level) && quality_level > 0.0, "quality_level must be finite and > 0");
+    SVO_ARG(std::isfinite(min_distance) && min_distance >= 0.0, "min_distance must be finite and >= 0");
+    const int64_t ncells = gftt_cell_count(width, height, min_distance);
+    SVO_ARG(ncells <= kMaxBucketCells, "min_distance gives more than 16384 grid cells");
+    SVO_HIP(hipSetDevice(ctx->device));
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const bool host = mem == SVO_MEM_HOST;
+    const int dpitch = align_up(width, 256);
+    const size_t ncap = (size_t)(cap > 0 ? cap : 1);
+    const size_t o_n = 0, o_xy = 256, o_resp = o_xy + up(sizeof(float2) * ncap), o_str = o_resp + up(sizeof(float) * ncap),
+                 o_rec = o_str + up(sizeof(float) * ncap), o_img = o_rec + (host ? up(sizeof(svo_keypoint) * ncap) : 0),
+                 extra = o_img + (host ? (size_t)dpitch * height : 0);
+    uint8_t *x = nullptr;
+    GfttBuf &g = ctx->gftt_stage;
+    int rc = gftt_plan(ctx, g, width, height, 1, cap, ncells, extra, &x);
+    if (rc) return rc;
+    GfttArgs a{};
+    gftt_params(a, g, width, height, cap, max_corners, quality_level, min_distance);
+    int *d_n = (int *)(x + o_n);
+    float2 *xy = (float2 *)(x + o_xy);
+    a.kp_xy = xy; a.kp_resp = (float *)(x + o_resp); a.kp_stride = 0; a.n_out = d_n;
+    a.strength = host ? (float *)(x + o_str) : strength;
+    svo_keypoint *d_rec = host ? (svo_keypoint *)(x + o_rec) : out;
+    if (host) {
+        uint8_t *d_img = x + o_img;
+        SVO_HIP(hipMemcpy2DAsync(d_img, (size_t)dpitch, img, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice, ctx->stream));
+        a.img = d_img; a.pitch = dpitch;
+    } else {
+        a.img = img; a.pitch = pitch;
+    }
+    SVO_HIP(launch_gftt_eigen(a, 1, ctx->stream));
+    SVO_HIP(launch_gftt_emit(a, 1, ctx->stream));
+    SVO_HIP(launch_gftt_select(a, 1, ctx->stream));
+    launch_gftt_pack(xy, d_n, cap, d_rec, host ? nullptr : n_out, ctx->stream);
+    SVO_HIP(hipGetLastError());
+    if (!host) return SVO_OK;
+    int *h_n = (int *)ctx->h_pinned;
+    SVO_HIP(hipMemcpyAsync(h_n, d_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    const int m = *h_n;
+    *n_out = m;
+    SVO_ARG(m <= cap, "more candidates than cap");
+    if (m > 0) {
+        SVO_HIP(hipMemcpyAsync(out, d_rec, sizeof(svo_keypoint) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (strength) SVO_HIP(hipMemcpyAsync(strength, a.strength, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         SVO_HIP(hipStreamSynchronize(ctx->stream));
     }
     return SVO_OK;

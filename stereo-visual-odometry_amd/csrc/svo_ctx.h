@@ -59,6 +59,17 @@ struct Ingest {
     uint8_t *up_stage[2] = {nullptr, nullptr};   // source-size staging behind fb[0] / fb[1] (svo_ingest_upload_frames_at), first use
 };
 
+// Scratch of the Shi-Tomasi detector (gftt.hip) for n images of w x h pixels: ONE device allocation cut into the candidate
+// map, the per-image words, the candidate keys, the cell words of a grid too large for LDS and (stage calls) the staged image
+// and the output lists.
+struct GfttBuf {
+    uint8_t *base = nullptr; size_t bytes = 0;
+    float *map = nullptr; int mpitch = 0; int64_t map_stride = 0;
+    unsigned *maxkey = nullptr; int *n_cand = nullptr;
+    unsigned long long *keys = nullptr; int64_t keys_stride = 0;
+    int *cells = nullptr; int64_t cells_stride = 0;
+};
+
 struct svo_ctx {
     svo_config cfg;
     DevArena arena;
@@ -157,6 +168,11 @@ struct svo_ctx {
     size_t bucket_cells_bytes = 0;
     uint8_t *bucket_stage = nullptr;                     // svo_bucket_corners: the caller's list as structure of arrays (+ its cells)
     size_t bucket_stage_bytes = 0;
+    // ---- Shi-Tomasi detector (svo_set_lk_detector / svo_gftt_detect; off and nothing allocated until then)
+    int lk_detector = SVO_DETECTOR_FAST;
+    int gftt_max_corners = 0;
+    double gftt_quality = 0.0, gftt_min_distance = 0.0;
+    GfttBuf gftt_fused, gftt_stage;                      // scratch of the fused path (n_img images of the context's size) / of the stage calls
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -237,6 +253,8 @@ int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose);
 int pipeline_streams_check_ids(svo_ctx *ctx, const int32_t *ids, int m);      // in range, no id twice; nothing launched
 int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t *L, const uint8_t *R, int pitch,
                           int64_t frame_stride, svo_step_result *results, int results_mem);
+// svo_abi.hip: the Shi-Tomasi detector of the fused LK front end (svo_set_lk_detector), n_new left images into frame slots f0 ..
+int gftt_detect_frames(svo_ctx *ctx, const uint8_t *L, int pitch, int64_t frame_stride, int f0, int n_new);
 // n step records from device memory to `out`, in the order of stream `st`: SVO_MEM_DEVICE: one copy, nothing waited for
 // (out null: they stay where they are); SVO_MEM_HOST: through the pinned scratch, and `st` is synchronised.
 int deliver_records(svo_ctx *ctx, const svo_step_result *d_src, int n, svo_step_result *out, int mem, hipStream_t st);

@@ -33,6 +33,30 @@ int fast_bucket_lds_cells();
 void launch_bucket_unpack(const svo_keypoint *in, int n, float2 *xy, float *resp, int *n_dev, hipStream_t st);
 void launch_bucket_pack(const float2 *xy, const float *resp, const int *n_dev, int n_max, svo_keypoint *out, int *n_out, hipStream_t st);
 
+// ---- Shi-Tomasi corners (gftt.hip): cv::goodFeaturesToTrack -----------------------------------------------------------
+struct GfttArgs {
+    const uint8_t *img; int pitch; int64_t img_stride;     // batch b reads img + b*img_stride
+    int w, h;
+    float *map; int mpitch; int64_t map_stride;            // eigenvalue of interior local maxima, -inf elsewhere (full: every eigenvalue)
+    int full;
+    unsigned *maxkey; int *n_cand;                         // per image: largest eigenvalue (order-preserving key), candidates found
+    unsigned long long *keys; int64_t keys_stride;         // candidate keys, keys_stride (a power of two >= max(cap, 64)) per image
+    int cap;                                               // candidates per image at most; an image with more gets no list
+    double quality, min_dist2;                             // qualityLevel, minDistance^2
+    int max_corners;                                       // <= 0: uncapped
+    int cell, gcols, grows, ncells;                        // cvRound(minDistance) and its grid; cell 0: minDistance < 1, no spacing
+    int *cells; int64_t cells_stride;                      // 4 words per cell and image; only read when ncells > gftt_lds_cells()
+    float2 *kp_xy; float *kp_resp; float *strength;        // outputs in selection order (kp_resp: gftt_resp_tag(); strength may be null)
+    int64_t kp_stride;
+    int *n_out;                                            // corners kept per image; the candidate count where that exceeds cap
+};
+hipError_t launch_gftt_eigen(const GfttArgs &a, int batch, hipStream_t st);      // image -> map + maxkey
+hipError_t launch_gftt_emit(const GfttArgs &a, int batch, hipStream_t st);       // map + maxkey -> keys + n_cand
+hipError_t launch_gftt_select(const GfttArgs &a, int batch, hipStream_t st);     // keys + n_cand -> kp_xy / kp_resp / n_out
+float gftt_resp_tag();                                                     // kp_resp of a Shi-Tomasi corner (no FAST score)
+void launch_gftt_pack(const float2 *xy, const int *n_dev, int cap, svo_keypoint *out, int *n_out, hipStream_t st);
+int gftt_lds_cells();
+
 // ---- LK pyramid (pyramid.hip) ---------------------------------------------------------------
 struct PyrArgs {
     PyrGeom g;

@@ -55,6 +55,13 @@ public:
     // ReadFastBuckets reads and checks them for the loaded YAML: a keep value without both sizes, a size < 1, a negative keep
     // or ORB mode with keep > 0 is refused (false + a message that names the key).  The keys are applied right after svo_create.
     static bool ReadFastBuckets(int *cell_w, int *cell_h, int *keep, std::string *err);
+    // additive YAML keys lk_detector: fast | gftt (absent: fast), gftt_quality_level (default 0.01) and gftt_min_distance
+    // (default 20) -- the literals of the reference's dormant cv::GFTTDetector::create(num_features, 0.01, 20)
+    // (src/tracking.cpp:18); the corner count is the existing key num_features (GFTTDetector_num_; absent: 500).
+    // svo_set_lk_detector, include/svo_abi.h.  ReadLkDetector reads and checks them for the loaded YAML: an unknown detector, a
+    // quality level that is not a finite number > 0, a negative or non-finite distance, and gftt together with ORB mode, the
+    // FAST buckets or fast_keep_strongest are refused (false + a message that names the key).  Applied right after svo_create.
+    static bool ReadLkDetector(int *detector, int *max_corners, double *quality_level, double *min_distance, std::string *err);
     bool Ingest() const { return image_scale_ < 1.0; }
     double ImageScale() const { return image_scale_; }
     int ImageInterp() const { return image_interp_; }
@@ -102,6 +109,8 @@ private:
     long max_keypoints_key_ = 0;                             // additive YAML key max_keypoints, read once (0 = absent)
     int fast_keep_strongest_ = 0;                            // additive YAML key fast_keep_strongest (0 = every corner)
     int bucket_w_ = 0, bucket_h_ = 0, bucket_keep_ = 0;      // additive YAML keys fast_bucket_width / _height / _keep (keep 0 = off)
+    int lk_detector_ = SVO_DETECTOR_FAST, gftt_num_ = 500;    // additive YAML keys lk_detector: fast (default) | gftt, num_features
+    double gftt_quality_ = 0.01, gftt_min_distance_ = 20.0;  // additive YAML keys gftt_quality_level, gftt_min_distance
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128
     double image_scale_ = 1.0;                               // additive YAML key image_scale (1 = no ingest stage)
     int image_interp_ = SVO_INTERP_NEAREST;                  // additive YAML key image_interp: nearest (default) | linear

@@ -155,6 +155,9 @@ int RunInterleaved(const std::vector<std::string> &yamls, const std::vector<std:
         // ... and so are fast_bucket_width / fast_bucket_height / fast_bucket_keep
         int cw, ch, keep;
         if (!Tracking::ReadFastBuckets(&cw, &ch, &keep, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
+        // ... and lk_detector / gftt_quality_level / gftt_min_distance
+        int det, num; double q, md;
+        if (!Tracking::ReadLkDetector(&det, &num, &q, &md, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
     }
     for (int s = 0; s < n; s++) {
         cv::Mat l, r;

@@ -47,6 +47,30 @@ bool Tracking::ReadFastBuckets(int *cell_w, int *cell_h, int *keep, std::string 
     return true;
 }
 
+bool Tracking::ReadLkDetector(int *detector, int *max_corners, double *quality_level, double *min_distance, std::string *err)
+{
+    *detector = SVO_DETECTOR_FAST; *max_corners = 500; *quality_level = 0.01; *min_distance = 20.0;
+    const std::string d = Config::Has("lk_detector") ? Config::Get<std::string>("lk_detector") : std::string("fast");
+    const int n = Config::Has("num_features") ? Config::Get<int>("num_features") : 500;
+    // (a value that does not parse as a number reads as 0)
+    const double q = Config::Has("gftt_quality_level") ? Config::Get<double>("gftt_quality_level") : 0.01;
+    const double m = Config::Has("gftt_min_distance") ? Config::Get<double>("gftt_min_distance") : 20.0;
+    const bool gftt = d == "gftt";
+    char msg[240] = "";
+    if (d != "fast" && !gftt) snprintf(msg, sizeof(msg), "lk_detector: '%s' is neither 'fast' nor 'gftt'", d.c_str());
+    else if (!(std::isfinite(q) && q > 0.0)) snprintf(msg, sizeof(msg), "gftt_quality_level: %g is not a finite number > 0", q);
+    else if (!(std::isfinite(m) && m >= 0.0)) snprintf(msg, sizeof(msg), "gftt_min_distance: %g is not a finite number >= 0", m);
+    else if (gftt && Config::Has("track_mode") && Config::Get<std::string>("track_mode") == "ORB_stereof2f_pnp")
+        snprintf(msg, sizeof(msg), "lk_detector: gftt with track_mode ORB_stereof2f_pnp (the detector switch is an LK-mode option)");
+    else if (gftt && Config::Has("fast_bucket_keep") && Config::Get<int>("fast_bucket_keep") > 0)
+        snprintf(msg, sizeof(msg), "lk_detector: gftt with fast_bucket_keep > 0 (the Shi-Tomasi detector spaces its own corners)");
+    else if (gftt && Config::Has("fast_keep_strongest") && Config::Get<int>("fast_keep_strongest") > 0)
+        snprintf(msg, sizeof(msg), "lk_detector: gftt with fast_keep_strongest > 0 (num_features bounds the Shi-Tomasi corners)");
+    if (msg[0]) { if (err) *err = msg; return false; }
+    if (gftt) { *detector = SVO_DETECTOR_GFTT; *max_corners = n; *quality_level = q; *min_distance = m; }
+    return true;
+}
+
 Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensors)
 {
     sensors_ = sensors;
@@ -72,6 +96,12 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
     if (!ReadImageScale(&image_scale_, &image_interp_, &config_error_)) image_scale_ = 1.0;     // the owner refuses to run (ConfigError)
     std::string bucket_error;
     if (!ReadFastBuckets(&bucket_w_, &bucket_h_, &bucket_keep_, &bucket_error) && config_error_.empty()) config_error_ = bucket_error;
+    std::string detector_error;
+    if (!ReadLkDetector(&lk_detector_, &gftt_num_, &gftt_quality_, &gftt_min_distance_, &detector_error) && config_error_.empty())
+        config_error_ = detector_error;
+    else if (lk_detector_ == SVO_DETECTOR_GFTT)
+        LZB_LOG("INFO", "lk_detector: gftt (num_features %d, gftt_quality_level %g, gftt_min_distance %g)", gftt_num_, gftt_quality_,
+                gftt_min_distance_);
 }
 
 Tracking::~Tracking()
@@ -190,6 +220,14 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
     if (bucket_keep_ > 0 && (rc = svo_set_fast_buckets(ctx_, bucket_w_, bucket_h_, bucket_keep_)) != SVO_OK) {
         LZB_LOG("ERROR", "svo_set_fast_buckets (fast_bucket_width %d, fast_bucket_height %d, fast_bucket_keep %d at %dx%d) failed (%d): %s",
                 bucket_w_, bucket_h_, bucket_keep_, width, height, rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    if (lk_detector_ == SVO_DETECTOR_GFTT &&
+        (rc = svo_set_lk_detector(ctx_, SVO_DETECTOR_GFTT, gftt_num_, gftt_quality_, gftt_min_distance_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_lk_detector (lk_detector gftt, num_features %d, gftt_quality_level %g, gftt_min_distance %g at %dx%d) "
+                "failed (%d): %s", gftt_num_, gftt_quality_, gftt_min_distance_, width, height, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;
