@@ -1,6 +1,17 @@
-// lk_common.h -- pieces shared by the two pyramidal-LK kernels (lk.hip: exact integer sums, the canonical
-// recipe; lk_sse2.hip: upstream's x86 float accumulation order): tile geometry, the packed dot-product helpers,
-// the bilinear weights and the tile staging.  See lk.hip for the mapping these serve.
+// lk_common.h -- everything the two pyramidal-LK kernels share, stated once.  lk.hip (exact integer sums, the canonical
+// recipe) and lk_sse2.hip (upstream's x86 float accumulation orders) differ in three things only: the tile geometry (a
+// traits type: ExactTile in lk.hip, ChainTile in lk_sse2.hip), the patch packing, and how the five sums A11, A12, A22,
+// b1, b2 are formed.  Those stay in the two files, with the level / iteration skeleton of their lk_call4 that orders the
+// LDS hand-offs.  Here:
+//   * the packed dot-product helpers, cvFloor, the bilinear weights;
+//   * tile staging: the lane's staging items, the source loads, the I- and J-tile stores as row-pair column words;
+//   * the packed Scharr passes with the zero border of the derivative image, and the bilinear patch samples;
+//   * every CONTROL RULE of cv::calcOpticalFlowPyrLK -- window position, weights and status per level, the I-tile
+//     requests, the J-tile origin and the re-stage test, the minEig / D degeneracy test, the 2x2 solve with the
+//     convergence and oscillation tests, the final-window check -- each with its exactness argument;
+//   * the kernel driver: workgroup -> (batch item, wave of the item), the wave's chunks of four points, the chain of
+//     ncalls calls, the deleteBadmatchFeatures predicate, the keep byte.
+// See lk.hip for the mapping these serve.
 #pragma once
 #include "svo_device.h"
 #include "svo_kernels.h"
@@ -8,26 +19,14 @@
 namespace svo {
 
 constexpr int kSlots = 4;                                 // points per wave
-// I tile: 24 rows x 28 bytes of the level, staged as ROW-PAIR COLUMN WORDS: Q[p][c] = byte c of tile
-// row p | byte c of row p + 1 << 16 (23 pairs x 28 columns, one dword each).  The patch build wants
-// exactly these words for the row pairs (r, r+1), (r+1, r+2), (r+2, r+3) of every lane's 10 columns;
-// formed while staging (4 v_perm per staged dword pair, 12 per lane) they replace the 30 v_perm +
-// 12 v_alignbyte every lane spent on its own copy, and the lane's reads become plain dword reads.
-// Stored COLUMN-MAJOR with 29 words per column, like the J tile below and for the same reason: a lane's
-// reads of its row pairs (row, row+1, row+2) of column offI + 7 seg + j then fall on banks 11 seg + row + d
-// (mod 32) -- conflict-free -- where the row-major order was 2-way conflicted for every row stride below 53
-// (half of all LDS-array cycles of the patch build; SQ_LDS_BANK_CONFLICT was 30 % of SQ_LDS_IDX_ACTIVE).
-constexpr int kQPairs = 23, kQCols = 28, kQColDw = 29, kQTileDw = kQCols * kQColDw;   // 812 dwords per slot
-// J tile: the same row-pair column words, 27 pairs x 28 columns around the window (3 spare on every side:
-// a window drifts that far at one level only rarely, and then the tile is staged again), stored
-// COLUMN-MAJOR with 29 words per column: lane (row, seg) reads column cx + 7 seg + k, pair cy + row, so
-// the banks of a 32-lane half are 7 * 29 * seg + row = 11 seg + row (mod 32) -- conflict-free; the
-// row-major order is 2-way conflicted for every stride below 53.
-constexpr int kJPairs = 27, kJCols = 28, kJColDw = 29, kJTileDw = kJCols * kJColDw;   // 812 dwords per slot
-constexpr int kJMargin = 3;
-static_assert(kQTileDw == kJTileDw && kQColDw == kJColDw, "slot s's J tile takes over slot s's I tile");
-constexpr int kLdsDwPerWave = kSlots * kJTileDw;                                         // 3248 dwords
 constexpr int W_BITS = 14;
+constexpr float kHalfWin = 10.f;                          // (winSize - 1) * 0.5
+constexpr float kFltScale = 1.f / (1 << 20);              // FLT_SCALE of the five sums
+constexpr int kNoJTile = -(1 << 20);                      // tx0 of a slot without a staged J tile
+
+// A tile geometry (the template parameter T below) names: kColDw (words per tile column), kTileDw (words per slot
+// tile), kQPairs / kJPairs (row pairs of the I / J tile), kJMargin (spare J rows and columns around the window) and
+// kAlignedI (the I tile starts at a 4-byte aligned image column).
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -115,9 +114,39 @@ __device__ __forceinline__ int dot2_sv(uint32_t a, uint32_t b_uniform, int c)   
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b_uniform), "v"(c));
     return r;
 }
+// the rounding of the J samples, 2^8 scaled like the column words (pixel << 7), held in a VGPR: a VOP3P instruction can
+// read ONE scalar operand, and that one is the slot's weight (an SGPR from v_readlane); a scalar rounding constant cost
+// a v_mov per slot and iteration
+__device__ __forceinline__ int j_sample_rounding()
+{
+    int vround = 1 << (W_BITS - 5 - 1 + 7);
+    asm volatile("" : "+v"(vround));
+    return vround;
+}
 
-// A tile's source dwords for this lane: items lane + 64 t = (row pair, dword column), rows `rowA` (upper) and
-// `rowB` = rowA + pitch, at 32-bit offsets from the wave-uniform base (global_load with an SGPR base)
+// ---- tile staging -------------------------------------------------------------------------------
+// A tile is staged from 7 source dwords (28 columns) per row pair: staging item lane + 64 t = row pair * 7 + dword
+// column.  dst: the item's first column word in a column-major tile with CS words per column.
+struct StageLane { int pr[3], dc4[3], dst[3]; };
+template <int CS>
+__device__ __forceinline__ StageLane stage_lane(int lane)
+{
+    StageLane q;
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        const int i = lane + 64 * t;
+        q.pr[t] = i / 7; q.dc4[t] = 4 * (i - q.pr[t] * 7); q.dst[t] = q.dc4[t] * CS + q.pr[t];
+    }
+    return q;
+}
+// lane part of the items' source offsets at a level
+__device__ __forceinline__ void stage_src(uint32_t (&src)[3], const StageLane &q, int pitch)
+{
+#pragma unroll
+    for (int t = 0; t < 3; t++) src[t] = (uint32_t)(q.pr[t] * pitch + q.dc4[t]);
+}
+// A tile's source dwords for this lane: rows `rowA` (upper) and `rowB` = rowA + pitch of every item, at 32-bit
+// offsets from the slot's wave-uniform base (global_load with an SGPR base: scalar part per slot, lane part per level)
 __device__ __forceinline__ void tile_loads(uint32_t (&r)[3][2], const uint8_t *rowA, const uint8_t *rowB, uint32_t s_off,
                                            const uint32_t (&q_src)[3], int lane, int n_items)
 {
@@ -129,21 +158,328 @@ __device__ __forceinline__ void tile_loads(uint32_t (&r)[3][2], const uint8_t *r
         }
     }
 }
-// ... and their four column words each into a column-major J tile
-__device__ __forceinline__ void tile_store_j(uint32_t *tile, const uint32_t (&r)[3][2], const int (&jq_dst)[3], int lane)
+// the tile of PAIRS row pairs whose first pixel is (x, y) of the level; x, y from slot s's control lane
+template <int PAIRS>
+__device__ __forceinline__ void tile_request(uint32_t (&r)[3][2], const PyrGeom &g, int level, int pitch, const uint8_t *slot,
+                                             int x, int y, int s, const uint32_t (&q_src)[3], int lane)
+{
+    const int xs = __builtin_amdgcn_readlane(x, 16 * s), ys = __builtin_amdgcn_readlane(y, 16 * s);
+    tile_loads(r, slot, slot + pitch, (uint32_t)(g.origin[level] + ys * pitch + xs), q_src, lane, PAIRS * 7);
+}
+// ... and their four column words each (pixel[r][c] | pixel[r + 1][c] << 16) into a column-major I tile
+template <class T>
+__device__ __forceinline__ void tile_store_i(uint32_t *tile, const uint32_t (&r)[3][2], const StageLane &q, int lane)
 {
 #pragma unroll
     for (int t = 0; t < 3; t++) {
-        if (lane + 64 * t < kJPairs * 7) {
+        if (lane + 64 * t < T::kQPairs * 7) {
             const uint32_t top = r[t][0], bot = r[t][1];
-            uint32_t *d = tile + jq_dst[t];
+            uint32_t *d = tile + q.dst[t];
+#pragma unroll
+            for (int c = 0; c < 4; c++) d[c * T::kColDw] = perm_b32(bot, top, 0x0c040c00u + 0x00010001u * c);
+        }
+    }
+}
+// ... into a J tile.  MASKED (tiles narrower than the 28 staged columns): columns 26, 27 are left out.
+template <class T, bool MASKED>
+__device__ __forceinline__ void tile_store_j(uint32_t *tile, const uint32_t (&r)[3][2], const StageLane &q, int lane)
+{
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        if (lane + 64 * t < T::kJPairs * 7) {
+            const uint32_t top = r[t][0], bot = r[t][1];
+            uint32_t *d = tile + q.dst[t];
             // samples are stored as pixel << 7 (byte into the high byte of its half, one packed shift): the
             // bilinear sums then come out scaled by 2^7 and "sum >> 9" is simply their high half
             const u16x2 one = {1, 1};
 #pragma unroll
-            for (int c = 0; c < 4; c++)
-                d[c * kJColDw] = as_u32(as_u16x2(perm_b32(bot, top, 0x040c000cu + 0x01000100u * c)) >> one);
+            for (int c = 0; c < 4; c++) {
+                if (MASKED && c >= 2 && q.dc4[t] == 24) continue;
+                d[c * T::kColDw] = as_u32(as_u16x2(perm_b32(bot, top, 0x040c000cu + 0x01000100u * c)) >> one);
+            }
         }
+    }
+}
+
+// ---- the patch: packed Scharr derivatives and bilinear samples -----------------------------------------------------
+// A lane's NC tile columns from `q0` (its first column, row pair `row`) as COLUMN WORDS pairing two vertically adjacent
+// rows (low half = upper row): Q01/Q12/Q23[j] = tile rows (row, row+1)/(row+1, row+2)/(row+2, row+3) of column j.  The
+// packed Scharr passes produce the derivative rows A (image row gyA) and B (gyA + 1) side by side in one register per
+// column, which is exactly the operand the bilinear v_dot2 wants:
+//   val_k = dot2(D[k], (w00 | w10 << 16)) + dot2(D[k+1], (w01 | w11 << 16)) + rounding
+// so no lane ever realigns a pixel pair.  Derivative column c = 0..NC-3 (image column gx0 + c) comes from tile columns
+// c..c+2; Q12[c + 1] is the pixel pair under it.
+template <int NC, int CS, bool EDGE>
+__device__ __forceinline__ void scharr_columns(lds_cu32 *q0, int gx0, int gyA, int w, int h, uint32_t (&Q12)[NC],
+                                               uint32_t (&DX)[NC - 2], uint32_t (&DY)[NC - 2])
+{
+    uint32_t Q01[NC], Q23[NC];
+    // ONE address per slot: everything else is an immediate offset of the reads
+#pragma unroll
+    for (int j = 0; j < NC; j++) { Q01[j] = q0[j * CS]; Q12[j] = q0[j * CS + 1]; Q23[j] = q0[j * CS + 2]; }
+    // vertical Scharr passes, rows A | B packed.  Both passes carry a factor 4 (coefficients 12 / 40
+    // instead of 3 / 10; |4 d| <= 16320 still fits 16 bits): the interpolated derivative
+    // (sum + 2^13) >> 14 then equals (4 sum + 2^15) >> 16, i.e. the HIGH half of the accumulator, and
+    // the patch packing picks bytes 2-3 directly instead of shifting every value first.
+    uint32_t T0[NC], T1[NC];
+    const u16x2 k12 = {12, 12}, k40 = {40, 40};
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+        T0[j] = as_u32((as_u16x2(Q01[j]) + as_u16x2(Q23[j])) * k12 + as_u16x2(Q12[j]) * k40);       // 4 t0
+        T1[j] = as_u32(as_u16x2(Q23[j]) - as_u16x2(Q01[j]));                                          // t1
+    }
+    // horizontal passes
+#pragma unroll
+    for (int c = 0; c < NC - 2; c++) {
+        DX[c] = as_u32(as_u16x2(T0[c + 2]) - as_u16x2(T0[c]));                                        // 4 dx
+        DY[c] = as_u32((as_u16x2(T1[c]) + as_u16x2(T1[c + 2])) * k12 + as_u16x2(T1[c + 1]) * k40);    // 4 dy
+    }
+    // the derivative image's border is BORDER_CONSTANT 0: mask positions outside the image
+    // (only possible when the window hangs over the edge: the EDGE instantiation)
+    if (EDGE) {
+        const int gyB = gyA + 1;
+        const uint32_t rows = ((gyA >= 0 && gyA < h) ? 0x0000FFFFu : 0u) | ((gyB >= 0 && gyB < h) ? 0xFFFF0000u : 0u);
+#pragma unroll
+        for (int c = 0; c < NC - 2; c++) {
+            const int gx = gx0 + c;
+            const uint32_t mk = (gx >= 0 && gx < w) ? rows : 0u;
+            DX[c] &= mk; DY[c] &= mk;
+        }
+    }
+}
+// the lane's NP = NC - 3 patch pixels: I with 5 fractional bits; Ix, Iy as value << 16 | rounding residue
+template <int NC>
+__device__ __forceinline__ void patch_samples(const uint32_t (&Q12)[NC], const uint32_t (&DX)[NC - 2], const uint32_t (&DY)[NC - 2],
+                                              uint32_t Wa, uint32_t Wb, int (&iv)[8], int (&ix)[8], int (&iy)[8])
+{
+#pragma unroll
+    for (int k = 0; k < NC - 3; k++) {
+        iv[k] = dot2(Q12[k + 2], Wb, dot2_k(Q12[k + 1], Wa, 1 << (W_BITS - 5 - 1))) >> (W_BITS - 5);
+        ix[k] = dot2(DX[k + 1], Wb, dot2_k(DX[k], Wa, 1 << (W_BITS + 1)));
+        iy[k] = dot2(DY[k + 1], Wb, dot2_k(DY[k], Wa, 1 << (W_BITS + 1)));
+    }
+}
+
+// ---- the control rules of one cv::calcOpticalFlowPyrLK call ---------------------------------------------------------
+// Control values are per lane = per slot lane >> 4: one vector instruction advances all four points.
+
+// first image column of the I tile: the patch needs the columns from ipx - 1
+template <class T> __device__ __forceinline__ int i_tile_x0(int ipx) { return T::kAlignedI ? (ipx - 1) & ~3 : ipx - 1; }
+
+// The I tiles of a level depend on prevPt only: they are requested one level ahead (the top level's before the level
+// loop), so their latency is covered by the previous level's iterations.
+template <class T>
+__device__ __forceinline__ void request_I(uint32_t (&rI)[kSlots][3][2], const PyrGeom &g, int level, const uint8_t *slotI,
+                                          float2 prevPt, bool live, const StageLane &q, int lane)
+{
+    const float lscale = 1.f / (float)(1 << level);
+    const int ipx = cv_floor(prevPt.x * lscale - kHalfWin), ipy = cv_floor(prevPt.y * lscale - kHalfWin);
+    const int pitch = g.pitch[level];
+    const unsigned long long m = __ballot(live && !window_oob(ipx, ipy, g.w[level], g.h[level]));
+    const int x0 = i_tile_x0<T>(ipx), y0 = ipy - 1;
+    uint32_t src[3];
+    stage_src(src, q, pitch);
+#pragma unroll
+    for (int s = 0; s < kSlots; s++) {
+        if (!((m >> (16 * s)) & 1ull)) continue;
+        tile_request<T::kQPairs>(rI[s], g, level, pitch, slotI, x0, y0, s, src, lane);
+    }
+}
+
+// A level's start: nextPt scaled up, the I window position and weights, the status rule for a window outside the
+// level, and the J window of the first iteration (nextPt is known, so its tile is requested together with the I tiles
+// and the patch arithmetic covers the latency of both).
+struct LkLevel {
+    int w, h;
+    int ipx, ipy;               // I window corner
+    uint32_t WIa, WIb;          // I weights
+    bool on;                    // the slot iterates at this level
+    float qx, qy;               // nextPt - halfWin
+    int tx0, ty0;               // J tile origin; tx0 == kNoJTile: none staged
+};
+template <class T>
+__device__ __forceinline__ LkLevel level_begin(const PyrGeom &g, int level, float2 prevPt, bool live, float &nx, float &ny,
+                                               int &status)
+{
+    LkLevel v;
+    v.w = g.w[level]; v.h = g.h[level];
+    const float lscale = 1.f / (float)(1 << level);
+    float px = prevPt.x * lscale, py = prevPt.y * lscale;
+    if (level == g.nlevels - 1) { nx = px; ny = py; }
+    else { nx = nx * 2.f; ny = ny * 2.f; }
+    px -= kHalfWin; py -= kHalfWin;
+    v.ipx = cv_floor(px); v.ipy = cv_floor(py);
+    const bool oob = window_oob(v.ipx, v.ipy, v.w, v.h);
+    if (live && oob && level == 0) status = 0;
+    v.on = live && !oob;
+    const PackedWeights wt = bilinear_weights(px - (float)v.ipx, py - (float)v.ipy);
+    v.WIa = wt.Wa; v.WIb = wt.Wb;
+    v.qx = nx - kHalfWin; v.qy = ny - kHalfWin;
+    v.tx0 = kNoJTile; v.ty0 = 0;
+    const int inx = cv_floor(v.qx), iny = cv_floor(v.qy);
+    if (v.on && !window_oob(inx, iny, v.w, v.h)) { v.tx0 = inx - T::kJMargin; v.ty0 = iny - T::kJMargin; }
+    return v;
+}
+
+// The 2x2 system of a level: a slot whose minimum eigenvalue or determinant is too small stops here (status 0 at
+// level 0).  Dinv = 1 / D; returns whether the slot goes on.  (Flags travel by value: a bool behind a reference becomes
+// a byte in a VGPR where the loops carry it, instead of a lane mask.)
+__device__ __forceinline__ bool level_solve_setup(float A11, float A12, float A22, int level, bool lvl_on, int &status, float &Dinv)
+{
+    const float D = A11 * A22 - A12 * A12;
+    const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
+                         (float)(2 * kWin * kWin);
+    const bool degenerate = minEig < 0.001f || D < 1.1920929e-07f;
+    if (lvl_on && degenerate && level == 0) status = 0;
+    Dinv = 1.f / D;
+    return lvl_on && !degenerate;
+}
+
+// An iteration's start: the J window position and weights, the status rule for a window that left the level, and the
+// re-stage test: the tile holds kJMargin spare rows and columns on every side of the window it was staged for; a
+// window that drifted further gets a new tile around itself.
+struct LkIter {
+    bool on;                    // the slot still iterates
+    uint32_t Wa, Wb;            // J weights
+    int joff;                   // slot part of the J sample offset (bytes), tile position of the slot included
+    bool restage;
+};
+template <class T>
+__device__ __forceinline__ LkIter iter_begin(float qx, float qy, int w, int h, int level, int lane, bool it_on, int &status,
+                                             int &tx0, int &ty0)
+{
+    LkIter it;
+    const int inx = cv_floor(qx), iny = cv_floor(qy);
+    if (it_on && window_oob(inx, iny, w, h)) {
+        if (level == 0) status = 0;
+        it_on = false;
+    }
+    const PackedWeights wj = bilinear_weights(qx - (float)inx, qy - (float)iny);
+    it.Wa = wj.Wa; it.Wb = wj.Wb;
+    int cx = inx - tx0, cy = iny - ty0;
+    it.restage = it_on && ((unsigned)cx > (unsigned)(2 * T::kJMargin) || (unsigned)cy > (unsigned)(2 * T::kJMargin));
+    if (it.restage) { tx0 = inx - T::kJMargin; ty0 = iny - T::kJMargin; cx = T::kJMargin; cy = T::kJMargin; }
+    it.joff = ((int)__umul24((unsigned)cx, T::kColDw) + cy + (lane >> 4) * T::kTileDw) * 4;
+    it.on = it_on;
+    return it;
+}
+
+// An iteration's end: the 2x2 solve, the step, the convergence and oscillation tests (a slot drops out when it
+// converges or oscillates); returns whether the slot goes on
+__device__ __forceinline__ bool iter_update(float A11, float A12, float A22, float Dinv, float b1f, float b2f, int j, bool it_on,
+                                            float &qx, float &qy, float &nx, float &ny, float &pdx, float &pdy)
+{
+    const float dlx = (A12 * b2f - A22 * b1f) * Dinv;
+    const float dly = (A12 * b1f - A11 * b2f) * Dinv;
+    // "delta.ddot(delta) <= epsilon" is a double comparison upstream; float decides it unless
+    // the sum lands within 1e-4 relative of epsilon (float error here < 2e-7 relative)
+    const float dd = dlx * dlx + dly * dly;
+    bool conv = dd <= 0.9999e-4f;
+    if (__builtin_expect(__any(it_on && !conv && dd < 1.0001e-4f), 0)) {
+        asm volatile("" ::: "memory");               // a real branch: if-converted, the f64 path ran every iteration
+        conv = (double)dlx * (double)dlx + (double)dly * (double)dly <= 0.01 * 0.01;
+    }
+    if (it_on) {
+        qx += dlx; qy += dly;
+        nx = qx + kHalfWin; ny = qy + kHalfWin;
+        if (conv) it_on = false;
+        // "std::abs(delta.x + prevDelta.x) < 0.01" compares a float with the double 0.01; the
+        // largest float below 0.01 is 0.01f itself, so "<= 0.01f" in float is the same predicate
+        else if (j > 0 && fabsf(dlx + pdx) <= 0.01f && fabsf(dly + pdy) <= 0.01f) {
+            nx -= dlx * 0.5f; ny -= dly * 0.5f;
+            it_on = false;
+        }
+        pdx = dlx; pdy = dly;
+    }
+    return it_on;
+}
+
+// err is requested by the reference: the final window must still be inside (A.4 step 7)
+__device__ __forceinline__ void final_window_check(float nx, float ny, int w, int h, int level, bool live, int &status)
+{
+    if (live && status && level == 0) {
+        const int fx = cv_floor(nx - kHalfWin), fy = cv_floor(ny - kHalfWin);
+        if (window_oob(fx, fy, w, h)) status = 0;
+    }
+}
+
+// ---- the kernel driver ---------------------------------------------------------------------------------------------
+// Grid: ONE dimension, a.gx workgroups of W waves per batch item.  XCD-aware mapping: consecutive workgroup ids go
+// round-robin to the 8 XCDs, each with its own 4 MB L2, so item = (id / 8 / gx) * 8 + id % 8 keeps
+// every XCD on its own items -- an XCD then has about one item's four pyramids (3.3 MB) in flight
+// instead of slices of all items that are in flight anywhere on the chip (L2 hit rate 63 % -> see
+// DESIGN.md).  Items in whole groups of 8 are dealt one per XCD; the last (batch % 8) items -- the single pair of
+// the online path among them -- are spread over all XCDs in the plain order.
+struct LkItem { int b, bx; };                           // batch item, workgroup of the item
+__device__ __forceinline__ LkItem lk_item_of_workgroup(const LkArgs &a)
+{
+    const int n_aware = (a.batch & ~7) * a.gx;
+    LkItem it;
+    if ((int)blockIdx.x < n_aware) {
+        const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
+        it.b = (slot_id / a.gx) * 8 + xcd; it.bx = slot_id % a.gx;
+    } else {
+        const int r = blockIdx.x - n_aware;
+        it.b = (a.batch & ~7) + r / a.gx; it.bx = r % a.gx;
+    }
+    return it;
+}
+
+// The waves of an item walk its points in strides of a.gx * W * 4 (waves x four slots), so the launch is sized from
+// the batch, not from the keypoint CAPACITY (cv::FAST is uncapped and the capacity is generous: a grid of capacity / 16
+// workgroups of four per item was mostly empty waves).  No workgroup barrier anywhere: each wave loops on its own.
+// With ncalls == 4 the wave walks the whole circular chain L1 -> R1 -> R2 -> L2 -> L1' for its four points and stops
+// early once all of them are rejected.
+// lk_call(slotI, slotJ, prevPt, outPt, status, live): one cv::calcOpticalFlowPyrLK call for the wave's four points.
+template <int W, class Call>
+__device__ __forceinline__ void lk_track_item(const LkArgs &a, int wave, int lane, Call &&lk_call)
+{
+    const LkItem item = lk_item_of_workgroup(a);
+    const int b = item.b, slot = lane >> 4;
+    int n = a.n_pts ? a.n_pts[b] : a.n_fixed;
+    n = min(n, a.cap);
+    // slots per wave: four when the launch fills the chip (the control work of an iteration is shared by
+    // four points); a launch of a few items only (the online path: one pair) is latency-bound -- there the
+    // points are spread over as many waves as the grid has, down to one point per wave
+    int spw = kSlots;
+    if (a.spread) spw = min(kSlots, max(1, (n + a.gx * W - 1) / (a.gx * W)));
+    for (int first = (item.bx * W + wave) * spw; first < n; first += a.gx * W * spw) {
+        const int idx = first + slot;
+        const bool valid = slot < spw && idx < n;
+        const bool writer = valid && lane == 16 * slot;         // one lane per slot stores results
+        const int64_t po = (int64_t)b * a.pts_stride + (valid ? idx : first);
+        const float2 p0 = a.pts_in[po];
+        float2 cur = p0, nxt;
+        bool outside = p0.x < 0 || p0.y < 0, bad = false, noepi = false;
+        bool live = valid;
+        float prev_y = p0.y;
+#pragma nounroll
+        for (int c = 0; c < a.ncalls; c++) {
+            const uint8_t *sI = a.prev[c] + (int64_t)b * a.slot_stride;
+            const uint8_t *sJ = a.next[c] + (int64_t)b * a.slot_stride;
+            int st;
+            lk_call(sI, sJ, cur, nxt, st, live);
+            if (writer && live) {
+                a.pts_out[c][po] = nxt;
+                a.status[c][po] = (uint8_t)st;
+            }
+            // Tracking::deleteBadmatchFeatures terms (p0 = t1_left, p1 = t1_right, p2 = t2_right,
+            // p3 = t2_left, p0_return = LK#4 output; call-site mapping src/tracking.cpp:619-620,
+            // predicate :623-660)
+            if (live) {
+                outside = outside || nxt.x < 0 || nxt.y < 0;
+                bad = bad || st == 0;
+                if (c == 0 || c == 2) noepi = noepi || (double)fabsf(prev_y - nxt.y) > a.match_err;   // |y0-y1|, |y2-y3|
+                prev_y = nxt.y;
+                cur = nxt;
+            }
+            // a rejected point can never be kept: the remaining calls of the circular chain only feed
+            // the keep predicate (their pts_out/status entries are scratch in the fused mode)
+            if (a.ncalls == 4 && (outside || bad || noepi)) live = false;
+            if (!__any(live)) break;
+        }
+        if (a.ncalls == 4 && writer) a.keep[po] = !(outside || bad || noepi);
+        wave_lds_fence();                                      // the next chunk restages this wave's tiles
     }
 }
 

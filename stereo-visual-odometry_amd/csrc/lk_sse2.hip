@@ -35,8 +35,14 @@
 //     in float, so the fused form rounds exactly as _mm_mul_ps + _mm_add_ps do), three independent chains a lane;
 //   * tiles: 26 columns x 26 words (margin 2 around the J window): 20 096 B of LDS per wave, EIGHT waves per CU --
 //     two per SIMD, so a dependent chain of one wave issues beside the other's.
-// Everything else -- tiles as row-pair column words, packed Scharr on the fly, weights, control flow, the circular
-// chain of four calls, the keep predicate -- is lk.hip's, and so are the fixed-point pixel values (integers: exact).
+// Everything else -- tiles as row-pair column words, packed Scharr on the fly, weights, the control rules, the circular
+// chain of four calls, the keep predicate -- is shared with lk.hip through lk_common.h, and so are the fixed-point pixel
+// values (integers: exact).
+//
+// What lives where: this file holds the tile geometry (ChainTile) and the LDS plan, the lane roles (make_lane), the
+// 8-pixel patch packing as madd pairs (patch_slot8), the b terms (mismatch_slot8), the serial chains (chain_a, chain_b),
+// the level / iteration skeleton of lk_call4_sse2 with its LDS hand-offs, lk_sse2_kernel's LDS declaration and the
+// launcher.  lk_common.h holds the control rules, the tile staging, the Scharr passes and the kernel driver.
 #include "lk_common.h"
 
 namespace svo {
@@ -47,11 +53,16 @@ namespace svo {
 // a staged source dword carries four columns, so the seventh dword of a row spills two columns past the tile: into
 // the next slot's first two columns (which that slot's own stores, issued later, overwrite) or, behind slot 3, into
 // the first 52 words of the chain staging, which are dead while tiles are staged at a level's start (the A words start
-// behind them).  A re-stage of one slot during the iterations masks those two stores instead (tile_store_j2<true>).
+// behind them).  A re-stage of one slot during the iterations masks those two stores instead (tile_store_j<ChainTile, true>).
 constexpr int kCS2 = 26, kJMargin2 = 2;
 constexpr int kQPairs2 = 23, kJPairs2 = kWin + 2 * kJMargin2;                       // 23, 25 (<= kCS2)
 constexpr int kTileDw2 = 26 * kCS2, kTileSpill = 2 * kCS2;                         // 676, 52
 constexpr int kTilesDw = kSlots * kTileDw2;                                        // 2704
+struct ChainTile {
+    static constexpr int kColDw = kCS2, kTileDw = kTileDw2;
+    static constexpr int kQPairs = kQPairs2, kJPairs = kJPairs2, kJMargin = kJMargin2;
+    static constexpr bool kAlignedI = false;       // fetched from image column ipx - 1, like the J tiles: the patch needs exactly 24 columns from there
+};
 // Chain staging of one slot, 576 words.  b (per iteration): the eight lane chains c = 2 k + (x|y) (42 terms + 2 the
 // chain reads but does not use) and the two tails (105 terms, 108 read) at the offsets below.  A ds_read_b128 is served
 // in four groups of sixteen lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- on 64 banks
@@ -195,42 +206,8 @@ __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c)       // two 
     return r;
 }
 
-// A staged source dword pair's four column words into an I tile (cf. lk.hip); the seventh dword's last two columns
-// land past the tile (see the LDS plan)
-__device__ __forceinline__ void tile_store_i2(uint32_t *tile, const uint32_t (&r)[3][2], const int (&q_dst)[3], int lane)
-{
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        if (lane + 64 * t < kQPairs2 * 7) {
-            const uint32_t top = r[t][0], bot = r[t][1];
-            uint32_t *d = tile + q_dst[t];
-#pragma unroll
-            for (int c = 0; c < 4; c++) d[c * kCS2] = perm_b32(bot, top, 0x0c040c00u + 0x00010001u * c);
-        }
-    }
-}
-// ... into a J tile (samples as pixel << 7, lk_common.h).  MASKED: the re-stage of ONE slot beside live tiles keeps the
-// two columns past the tile away from its neighbour.
-template <bool MASKED>
-__device__ __forceinline__ void tile_store_j2(uint32_t *tile, const uint32_t (&r)[3][2], const int (&q_dst)[3], const int (&q_dc4)[3], int lane)
-{
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        if (lane + 64 * t < kJPairs2 * 7) {
-            const uint32_t top = r[t][0], bot = r[t][1];
-            uint32_t *d = tile + q_dst[t];
-            const u16x2 one = {1, 1};
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                if (MASKED && c >= 2 && q_dc4[t] == 24) continue;
-                d[c * kCS2] = as_u32(as_u16x2(perm_b32(bot, top, 0x040c000cu + 0x01000100u * c)) >> one);
-            }
-        }
-    }
-}
-
 // ---- phase A for one slot: the lane's 8 patch pixels from the staged I tile (cf. patch_slot in lk.hip) ------------
-// Tile bytes j = 0..10 of the lane = image columns ipx - 1 + x0 + j.  Outputs: the patch packed as madd pairs
+// Tile columns j = 0..10 of the lane = image columns ipx - 1 + x0 + j (scharr_columns, lk_common.h).  Outputs: the patch packed as madd pairs
 // (pixel m | pixel m + 4 << 16, m = 0..3) -- I with 5 fractional bits, Ix, Iy -- and the 8 patch words Ix | Iy << 16
 // of the A chains.  Pixels right of column 20 (tail lanes, i > 4) are computed from whatever lies beside the tile and
 // masked out of the pairs; their patch words go to a dump entry.  A tail lane's pixel 4 (x = 20) is a scalar-tail pixel of
@@ -241,42 +218,10 @@ __device__ __forceinline__ void patch_slot8(uint32_t tile_addr, const Sse2Lane &
                                             uint32_t (&IyP)[4], uint32_t &Ix4, uint32_t &Iy4, uint32_t (&Aw)[8])
 {
     const uint32_t Wa = Wau & L.onmask, Wb = Wbu & L.onmask;
-    uint32_t Q01[11], Q12[11], Q23[11];
-    {
-        lds_cu32 *q0 = (lds_cu32 *)(size_t)(tile_addr + L.qoff);
-#pragma unroll
-        for (int j = 0; j < 11; j++) { Q01[j] = q0[j * kCS2]; Q12[j] = q0[j * kCS2 + 1]; Q23[j] = q0[j * kCS2 + 2]; }
-    }
-    uint32_t T0[11], T1[11];
-    const u16x2 k12 = {12, 12}, k40 = {40, 40};
-#pragma unroll
-    for (int j = 0; j < 11; j++) {
-        T0[j] = as_u32((as_u16x2(Q01[j]) + as_u16x2(Q23[j])) * k12 + as_u16x2(Q12[j]) * k40);       // 4 t0
-        T1[j] = as_u32(as_u16x2(Q23[j]) - as_u16x2(Q01[j]));                                          // t1
-    }
-    uint32_t DX[9], DY[9];
-#pragma unroll
-    for (int c = 0; c < 9; c++) {
-        DX[c] = as_u32(as_u16x2(T0[c + 2]) - as_u16x2(T0[c]));                                        // 4 dx
-        DY[c] = as_u32((as_u16x2(T1[c]) + as_u16x2(T1[c + 2])) * k12 + as_u16x2(T1[c + 1]) * k40);    // 4 dy
-    }
-    if (EDGE) {                                  // the derivative image's border is BORDER_CONSTANT 0
-        const int gyA = ipy + L.row, gyB = gyA + 1;
-        const uint32_t rows = ((gyA >= 0 && gyA < h) ? 0x0000FFFFu : 0u) | ((gyB >= 0 && gyB < h) ? 0xFFFF0000u : 0u);
-#pragma unroll
-        for (int c = 0; c < 9; c++) {
-            const int gx = ipx + L.x0 + c;
-            const uint32_t mk = (gx >= 0 && gx < w) ? rows : 0u;
-            DX[c] &= mk; DY[c] &= mk;
-        }
-    }
-    int iv[8], ix[8], iy[8];                     // ix, iy: value << 16 | rounding residue
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        iv[k] = dot2(Q12[k + 2], Wb, dot2_k(Q12[k + 1], Wa, 1 << (W_BITS - 5 - 1))) >> (W_BITS - 5);
-        ix[k] = dot2(DX[k + 1], Wb, dot2_k(DX[k], Wa, 1 << (W_BITS + 1)));
-        iy[k] = dot2(DY[k + 1], Wb, dot2_k(DY[k], Wa, 1 << (W_BITS + 1)));
-    }
+    uint32_t Q12[11], DX[9], DY[9];
+    scharr_columns<11, kCS2, EDGE>((lds_cu32 *)(size_t)(tile_addr + L.qoff), ipx + L.x0, ipy + L.row, w, h, Q12, DX, DY);
+    int iv[8], ix[8], iy[8];
+    patch_samples<11>(Q12, DX, DY, Wa, Wb, iv, ix, iy);
 #pragma unroll
     for (int m = 0; m < 4; m++) {
         IvP[m] = perm_b32((uint32_t)iv[m + 4], (uint32_t)iv[m], 0x05040100u);
@@ -374,42 +319,6 @@ __device__ __forceinline__ float chain_b(const Sse2Lane &L)
     tail_adds<4>(acc, qb, 76); tail_adds<5>(acc, qb, 76); tail_adds<6>(acc, qb, 76); tail_adds<7>(acc, qb, 76);
     return L.b_tail ? acc : acc42;
 }
-#ifdef SVO_LKS_EXPERIMENTS
-// TIMING EXPERIMENTS of round 6 (never in the shipped build: tools/gpu/lks_chain_bound.sh compiles them in on the GPU box and
-// selects one with SVO_LKS_EXP; results in profiles/r06_lk_sse2_chain_bound.json).  Question: what would an integer / tree
-// fast path for the b chains buy when the float sums are provably exact?  chain_b_tree adds the same staged terms as a TREE --
-// four accumulators over phase 1, every lane of a half row its own eight tail terms, three DPP steps -- which is what ANY
-// exact fast path has to do at least (its sums differ from the serial order in the last bit when a partial sum passes 2^24:
-// a bound, not a product path), optionally with the sums of |terms| beside it (a guard evaluated in the chain lanes).
-template <bool GUARD>
-__device__ __forceinline__ float chain_b_tree(const Sse2Lane &L, int lane, float &guard)
-{
-    lds_cf32x4 *p = (lds_cf32x4 *)(size_t)L.cb;
-    const f32x4 qa = *(lds_cf32x4 *)(size_t)L.cbA, qb = *(lds_cf32x4 *)(size_t)L.cbB;
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, a[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 10; t++) {
-        const f32x4 q = p[t];
-#pragma unroll
-        for (int e = 0; e < 4; e++) { s[e] += q[e]; if (GUARD) a[e] += __builtin_fabsf(q[e]); }
-    }
-    const f32x4 q10 = p[10];
-    s[0] += q10[0]; s[1] += q10[1];
-    if (GUARD) { a[0] += __builtin_fabsf(q10[0]); a[1] += __builtin_fabsf(q10[1]); }
-    const float pad_s = q10[2] + q10[3], pad_a = __builtin_fabsf(q10[2]) + __builtin_fabsf(q10[3]);
-    float S = (s[0] + s[1]) + (s[2] + s[3]), A = (a[0] + a[1]) + (a[2] + a[3]);
-    const int f = lane & 7;
-    const bool v1 = f < 7;
-    float ts = (qa[0] + qa[1]) + (qa[2] + qa[3]) + (qb[0] + (v1 ? (qb[1] + qb[2]) + qb[3] : 0.f));
-    float ta = 0.f;
-    if (GUARD) ta = (__builtin_fabsf(qa[0]) + __builtin_fabsf(qa[1])) + (__builtin_fabsf(qa[2]) + __builtin_fabsf(qa[3])) +
-                    (__builtin_fabsf(qb[0]) + (v1 ? (__builtin_fabsf(qb[1]) + __builtin_fabsf(qb[2])) + __builtin_fabsf(qb[3]) : 0.f));
-    ts += row_shl<4>(ts); ts += row_shl<2>(ts); ts += row_shl<1>(ts);
-    if (GUARD) { ta += row_shl<4>(ta); ta += row_shl<2>(ta); ta += row_shl<1>(ta); }
-    guard = L.b_tail ? A + pad_a + ta : A;
-    return L.b_tail ? S + pad_s + ts : S;
-}
-#endif
 // A: positions 0..3 of a row = the SSE lanes q (105 terms), position 4 = the scalar tail (21 terms); every lane carries
 // all three sums.  A term is the product of two 16-bit patch values, < 2^24: exact in float, so fma(fx, fy, acc) rounds
 // once exactly where _mm_add_ps(acc, _mm_mul_ps(fx, fy)) / iA += (float)(ix * iy) round.
@@ -474,90 +383,50 @@ __device__ __forceinline__ float combine_a(float r)
 }
 
 // One cv::calcOpticalFlowPyrLK call for the wave's four points (cf. lk_call4 in lk.hip; control values are per
-// lane = per slot lane >> 4).
-template <bool LEGACY, int EXP>
+// lane = per slot lane >> 4, the rules they follow are lk_common.h's).
+template <bool LEGACY>
 __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *slotI, const uint8_t *slotJ, float2 prevPt,
                                               float2 &outPt, int &status, bool live, uint32_t *lds, int lane,
                                               const Sse2Lane &L)
 {
-    const float half = 10.f;                     // (winSize - 1) * 0.5
-    const float FLT_SCALE = 1.f / (1 << 20);
+    typedef ChainTile T;
     uint32_t IvP[kSlots][4], IxP[kSlots][4], IyP[kSlots][4], Ix4[kSlots], Iy4[kSlots];
-    int q_pr[3], q_dc4[3], q_dst[3];             // staging item lane + 64 t = row pair * 7 + dword column
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        const int i = lane + 64 * t;
-        q_pr[t] = i / 7; q_dc4[t] = 4 * (i - q_pr[t] * 7); q_dst[t] = q_dc4[t] * kCS2 + q_pr[t];
-    }
+    const StageLane q = stage_lane<T::kColDw>(lane);
     const uint32_t lds_base = (uint32_t)(size_t)(lds_cu32 *)lds;
-    int vround = 1 << (W_BITS - 5 - 1 + 7);
-    asm volatile("" : "+v"(vround));
+    const int vround = j_sample_rounding();
     status = 1;
     float nx = 0.f, ny = 0.f;
     uint32_t rI[kSlots][3][2];
-    auto request_I = [&](int level) {
-        const int w = g.w[level], h = g.h[level], pitch = g.pitch[level];
-        const float lscale = 1.f / (float)(1 << level);
-        const int ipx = cv_floor(prevPt.x * lscale - half), ipy = cv_floor(prevPt.y * lscale - half);
-        const unsigned long long m = __ballot(live && !window_oob(ipx, ipy, w, h));
-        const int x0 = ipx - 1;                  // unaligned, like the J tiles: the patch needs exactly 24 columns from here
-        uint32_t src[3];
-#pragma unroll
-        for (int t = 0; t < 3; t++) src[t] = (uint32_t)(q_pr[t] * pitch + q_dc4[t]);
-#pragma unroll
-        for (int s = 0; s < kSlots; s++) {
-            if (!((m >> (16 * s)) & 1ull)) continue;
-            const int x0s = __builtin_amdgcn_readlane(x0, 16 * s), ipys = __builtin_amdgcn_readlane(ipy, 16 * s);
-            tile_loads(rI[s], slotI, slotI + pitch, (uint32_t)(g.origin[level] + (ipys - 1) * pitch + x0s), src, lane, kQPairs2 * 7);
-        }
-    };
-    request_I(g.nlevels - 1);
+    request_I<T>(rI, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
     for (int level = g.nlevels - 1; level >= 0; --level) {
-        const int w = g.w[level], h = g.h[level], pitch = g.pitch[level];
-        const float lscale = 1.f / (float)(1 << level);
-        float px = prevPt.x * lscale, py = prevPt.y * lscale;
-        if (level == g.nlevels - 1) { nx = px; ny = py; }
-        else { nx = nx * 2.f; ny = ny * 2.f; }
-        px -= half; py -= half;
-        const int ipx = cv_floor(px), ipy = cv_floor(py);
-        const bool oob = window_oob(ipx, ipy, w, h);
-        if (live && oob && level == 0) status = 0;
-        bool lvl_on = live && !oob;
-        const PackedWeights wt = bilinear_weights(px - (float)ipx, py - (float)ipy);
-        const uint32_t WIa = wt.Wa, WIb = wt.Wb;
-        float qx = nx - half, qy = ny - half;       // nextPt - halfWin
-        int tx0 = -(1 << 20), ty0 = 0;              // no J tile staged
-        {
-            const int inx = cv_floor(qx), iny = cv_floor(qy);
-            if (lvl_on && !window_oob(inx, iny, w, h)) { tx0 = inx - kJMargin2; ty0 = iny - kJMargin2; }
-        }
-        const unsigned long long m_on = __ballot(lvl_on), m_j = __ballot(tx0 != -(1 << 20));
+        LkLevel lv = level_begin<T>(g, level, prevPt, live, nx, ny, status);
+        bool lvl_on = lv.on;
+        const int w = lv.w, h = lv.h, pitch = g.pitch[level];
+        const unsigned long long m_on = __ballot(lvl_on), m_j = __ballot(lv.tx0 != kNoJTile);
         uint32_t q_src[3];
-#pragma unroll
-        for (int t = 0; t < 3; t++) q_src[t] = (uint32_t)(q_pr[t] * pitch + q_dc4[t]);
+        stage_src(q_src, q, pitch);
         uint32_t rJ[kSlots][3][2];
         // ---- I tiles as row-pair column words (the J tiles take their place afterwards)
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
             if (!((m_on >> (16 * s)) & 1ull)) continue;
-            tile_store_i2(lds + s * kTileDw2, rI[s], q_dst, lane);
+            tile_store_i<T>(lds + s * T::kTileDw, rI[s], q, lane);
         }
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
             if (!((m_j >> (16 * s)) & 1ull)) continue;
-            const int tx0s = __builtin_amdgcn_readlane(tx0, 16 * s), ty0s = __builtin_amdgcn_readlane(ty0, 16 * s);
-            tile_loads(rJ[s], slotJ, slotJ + pitch, (uint32_t)(g.origin[level] + ty0s * pitch + tx0s), q_src, lane, kJPairs2 * 7);
+            tile_request<T::kJPairs>(rJ[s], g, level, pitch, slotJ, lv.tx0, lv.ty0, s, q_src, lane);
         }
         wave_lds_fence();
         // ---- patches; their words Ix | Iy << 16 go to the chain staging in the order of the A chains
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
             if (!((m_on >> (16 * s)) & 1ull)) continue;
-            const uint32_t qaddr = lds_base + (uint32_t)(s * kTileDw2 * 4);
-            const uint32_t W01s = __builtin_amdgcn_readlane(WIa, 16 * s), W23s = __builtin_amdgcn_readlane(WIb, 16 * s);
-            const int ipxs = __builtin_amdgcn_readlane(ipx, 16 * s), ipys = __builtin_amdgcn_readlane(ipy, 16 * s);
+            const uint32_t qaddr = lds_base + (uint32_t)(s * T::kTileDw * 4);
+            const uint32_t W01s = __builtin_amdgcn_readlane(lv.WIa, 16 * s), W23s = __builtin_amdgcn_readlane(lv.WIb, 16 * s);
+            const int ipxs = __builtin_amdgcn_readlane(lv.ipx, 16 * s), ipys = __builtin_amdgcn_readlane(lv.ipy, 16 * s);
             uint32_t Aw[8];
-            if (__builtin_expect(ipxs < 0 || ipxs + kWin >= w || ipys < 0 || ipys + kWin >= h, 0))
+            if (__builtin_expect(ipxs < 0 || ipxs + kWin >= w || ipys < 0 || ipys + kWin >= h, 0))     // the window hangs over the edge
                 patch_slot8<true>(qaddr, L, W01s, W23s, ipxs, ipys, w, h, IvP[s], IxP[s], IyP[s], Ix4[s], Iy4[s], Aw);
             else
                 patch_slot8<false>(qaddr, L, W01s, W23s, ipxs, ipys, w, h, IvP[s], IxP[s], IyP[s], Ix4[s], Iy4[s], Aw);
@@ -569,63 +438,48 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
             if (!((m_j >> (16 * s)) & 1ull)) continue;
-            tile_store_j2<false>(lds + s * kTileDw2, rJ[s], q_dst, q_dc4, lane);
+            tile_store_j<T, false>(lds + s * T::kTileDw, rJ[s], q, lane);
         }
-        float A11, A12, A22, D;
+        float A11, A12, A22;
         {
             float r11, r12, r22;
             chain_a(L, r11, r12, r22);
             // iA += A_buf[0] + A_buf[1] + A_buf[2] + A_buf[3] after the scalar tail went into iA
-            A11 = combine_a(r11) * FLT_SCALE;
-            A12 = combine_a(r12) * FLT_SCALE;
-            A22 = combine_a(r22) * FLT_SCALE;
+            A11 = combine_a(r11) * kFltScale;
+            A12 = combine_a(r12) * kFltScale;
+            A22 = combine_a(r22) * kFltScale;
         }
         wave_lds_fence();                        // the iterations' b terms overwrite the patch words
-        D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
-                             (float)(2 * kWin * kWin);
-        const bool degenerate = minEig < 0.001f || D < 1.1920929e-07f;
-        if (lvl_on && degenerate && level == 0) status = 0;
-        lvl_on = lvl_on && !degenerate;
-        D = 1.f / D;
+        float Dinv;
+        lvl_on = level_solve_setup(A11, A12, A22, level, lvl_on, status, Dinv);
 
-        if (level > 0) request_I(level - 1);
+        if (level > 0) request_I<T>(rI, g, level - 1, slotI, prevPt, live, q, lane);
         float pdx = 0.f, pdy = 0.f;
         bool it_on = lvl_on;
         for (int j = 0; j < kLkMaxIter; j++) {
             if (!__any(it_on)) break;
-            const int inx = cv_floor(qx), iny = cv_floor(qy);
-            if (it_on && window_oob(inx, iny, w, h)) {
-                if (level == 0) status = 0;
-                it_on = false;
-            }
-            const PackedWeights wj = bilinear_weights(qx - (float)inx, qy - (float)iny);
-            const uint32_t Wa = wj.Wa, Wb = wj.Wb;
-            int cx = inx - tx0, cy = iny - ty0;
-            const bool restage = it_on && ((unsigned)cx > (unsigned)(2 * kJMargin2) || (unsigned)cy > (unsigned)(2 * kJMargin2));
-            if (restage) { tx0 = inx - kJMargin2; ty0 = iny - kJMargin2; cx = kJMargin2; cy = kJMargin2; }
-            const int joff = ((int)__umul24((unsigned)cx, kCS2) + cy + (lane >> 4) * kTileDw2) * 4;
-            const unsigned long long m_it = __ballot(it_on), m_rs = __ballot(restage);
+            const LkIter it = iter_begin<T>(lv.qx, lv.qy, w, h, level, lane, it_on, status, lv.tx0, lv.ty0);
+            it_on = it.on;
+            const unsigned long long m_it = __ballot(it_on), m_rs = __ballot(it.restage);
             if (__builtin_expect(m_rs != 0, 0)) {     // a window drifted out of its tile
 #pragma unroll
                 for (int s = 0; s < kSlots; s++) {
                     if (!((m_rs >> (16 * s)) & 1ull)) continue;
-                    const int tx0s = __builtin_amdgcn_readlane(tx0, 16 * s), ty0s = __builtin_amdgcn_readlane(ty0, 16 * s);
                     uint32_t r[3][2];
-                    tile_loads(r, slotJ, slotJ + pitch, (uint32_t)(g.origin[level] + ty0s * pitch + tx0s), q_src, lane, kJPairs2 * 7);
-                    tile_store_j2<true>(lds + s * kTileDw2, r, q_dst, q_dc4, lane);
+                    tile_request<T::kJPairs>(r, g, level, pitch, slotJ, lv.tx0, lv.ty0, s, q_src, lane);
+                    tile_store_j<T, true>(lds + s * T::kTileDw, r, q, lane);
                 }
                 wave_lds_fence();
             }
 #pragma unroll
             for (int s = 0; s < kSlots; s++) {
                 if (!((m_it >> (16 * s)) & 1ull)) continue;
-                const int joffs = __builtin_amdgcn_readlane(joff, 16 * s);
-                const uint32_t Was = __builtin_amdgcn_readlane(Wa, 16 * s), Wbs = __builtin_amdgcn_readlane(Wb, 16 * s);
+                const int joffs = __builtin_amdgcn_readlane(it.joff, 16 * s);
+                const uint32_t Was = __builtin_amdgcn_readlane(it.Wa, 16 * s), Wbs = __builtin_amdgcn_readlane(it.Wb, 16 * s);
                 lds_cu32 *pj = (lds_cu32 *)(size_t)(lds_base + (uint32_t)joffs + L.qoff);
                 uint32_t C[9];
 #pragma unroll
-                for (int k = 0; k < 9; k++) C[k] = pj[k * kCS2];
+                for (int k = 0; k < 9; k++) C[k] = pj[k * T::kColDw];
                 float v[16];
                 mismatch_slot8<LEGACY>(C, Was, Wbs, IvP[s], IxP[s], IyP[s], Ix4[s], Iy4[s], vround, v);
                 const uint32_t so = (uint32_t)(s * stage_dw<LEGACY>() * 4);
@@ -635,112 +489,34 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
             wave_lds_fence();
             float b1f, b2f;
             {
-                float r;
-#ifdef SVO_LKS_EXPERIMENTS
-                float guard = 0.f;
-                if (EXP == 1) __builtin_amdgcn_s_setprio(3);                       // the chain wave first at the issue arbiter
-                if (EXP == 2) r = chain_b_tree<false>(L, lane, guard);             // no serial chain at all: the bound
-                else if (EXP == 3) {                                               // tree + guard max(P, N) = (sum |t| + |S|) / 2 < 2^24, else the chain
-                    r = chain_b_tree<true>(L, lane, guard);
-                    if (__builtin_expect(__any(guard + __builtin_fabsf(r) >= 33546240.f), 0)) r = chain_b<LEGACY>(L);
-                } else r = chain_b<LEGACY>(L);
-                if (EXP == 1) __builtin_amdgcn_s_setprio(0);
-#else
-                r = chain_b<LEGACY>(L);
-#endif
+                const float r = chain_b<LEGACY>(L);
                 // bbuf = qb0 + qb1; ib1 += bbuf[0] + bbuf[2]; ib2 += bbuf[1] + bbuf[3]  (the tails are already in ib), on the
                 // DPP network inside the row.  Positions: 0 tail x | 1..4 chains 0, 4, 2, 6 | 8 tail y | 9..12 chains 1, 5, 3, 7:
                 // position 1 + 2 = bb0, 3 + 4 = bb2 (9.. : bb1, bb3), then their sum, then the tail at the head of the half row
                 const float bb = r + row_shl<1>(r);
                 const float u = bb + row_shl<2>(bb);
                 const float f = r + row_shl<1>(u);
-                b1f = row_first(f) * FLT_SCALE;
-                b2f = row_first(row_shl<8>(f)) * FLT_SCALE;
+                b1f = row_first(f) * kFltScale;
+                b2f = row_first(row_shl<8>(f)) * kFltScale;
             }
             wave_lds_fence();                    // the next iteration's terms overwrite these
-            const float dlx = (A12 * b2f - A22 * b1f) * D;
-            const float dly = (A12 * b1f - A11 * b2f) * D;
-            const float dd = dlx * dlx + dly * dly;
-            bool conv = dd <= 0.9999e-4f;
-            if (__builtin_expect(__any(it_on && !conv && dd < 1.0001e-4f), 0)) {
-                asm volatile("" ::: "memory");
-                conv = (double)dlx * (double)dlx + (double)dly * (double)dly <= 0.01 * 0.01;
-            }
-            if (it_on) {
-                qx += dlx; qy += dly;
-                nx = qx + half; ny = qy + half;
-                if (conv) it_on = false;
-                else if (j > 0 && fabsf(dlx + pdx) <= 0.01f && fabsf(dly + pdy) <= 0.01f) {
-                    nx -= dlx * 0.5f; ny -= dly * 0.5f;
-                    it_on = false;
-                }
-                pdx = dlx; pdy = dly;
-            }
+            it_on = iter_update(A11, A12, A22, Dinv, b1f, b2f, j, it_on, lv.qx, lv.qy, nx, ny, pdx, pdy);
         }
-        if (live && status && level == 0) {
-            int fx = cv_floor(nx - half), fy = cv_floor(ny - half);
-            if (window_oob(fx, fy, w, h)) status = 0;
-        }
+        final_window_check(nx, ny, w, h, level, live, status);
     }
     outPt = make_float2(nx, ny);
 }
 
-// Grid: ONE wave per workgroup, a.gx WAVES per batch item walking the item's points in strides of a.gx * 4 slots;
-// the same XCD-aware item mapping as lk_kernel (consecutive workgroup ids go round the 8 XCDs).
-template <bool LEGACY, int EXP = 0>
+// Grid and item mapping: lk_track_item (lk_common.h) with ONE wave per workgroup, so a.gx WAVES per batch item.
+template <bool LEGACY>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void lk_sse2_kernel(LkArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[LEGACY ? kLdsDwLegacy : kLdsDwSse2];
-    const int n_aware = (a.batch & ~7) * a.gx;
-    int b, wv;
-    if ((int)blockIdx.x < n_aware) {
-        const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-        b = (slot_id / a.gx) * 8 + xcd; wv = slot_id % a.gx;
-    } else {
-        const int r = blockIdx.x - n_aware;
-        b = (a.batch & ~7) + r / a.gx; wv = r % a.gx;
-    }
     const int lane = threadIdx.x & 63;
-    const int slot = lane >> 4;
-    int n = a.n_pts ? a.n_pts[b] : a.n_fixed;
-    n = min(n, a.cap);
     const Sse2Lane L = make_lane<LEGACY>(lane, (uint32_t)(size_t)(lds_cu32 *)lds, a.accum == 2);
-    int spw = kSlots;
-    if (a.spread) spw = min(kSlots, max(1, (n + a.gx - 1) / a.gx));
-    for (int first = wv * spw; first < n; first += a.gx * spw) {
-        const int idx = first + slot;
-        const bool valid = slot < spw && idx < n;
-        const bool writer = valid && lane == 16 * slot;
-        const int64_t po = (int64_t)b * a.pts_stride + (valid ? idx : first);
-        const float2 p0 = a.pts_in[po];
-        float2 cur = p0, nxt;
-        bool outside = p0.x < 0 || p0.y < 0, bad = false, noepi = false;
-        bool live = valid;
-        float prev_y = p0.y;
-#pragma nounroll
-        for (int c = 0; c < a.ncalls; c++) {
-            const uint8_t *sI = a.prev[c] + (int64_t)b * a.slot_stride;
-            const uint8_t *sJ = a.next[c] + (int64_t)b * a.slot_stride;
-            int st;
-            lk_call4_sse2<LEGACY, EXP>(a.g, sI, sJ, cur, nxt, st, live, lds, lane, L);
-            if (writer && live) {
-                a.pts_out[c][po] = nxt;
-                a.status[c][po] = (uint8_t)st;
-            }
-            // Tracking::deleteBadmatchFeatures terms, as in lk_kernel (src/tracking.cpp:619-660)
-            if (live) {
-                outside = outside || nxt.x < 0 || nxt.y < 0;
-                bad = bad || st == 0;
-                if (c == 0 || c == 2) noepi = noepi || (double)fabsf(prev_y - nxt.y) > a.match_err;
-                prev_y = nxt.y;
-                cur = nxt;
-            }
-            if (a.ncalls == 4 && (outside || bad || noepi)) live = false;
-            if (!__any(live)) break;
-        }
-        if (a.ncalls == 4 && writer) a.keep[po] = !(outside || bad || noepi);
-        wave_lds_fence();
-    }
+    lk_track_item<1>(a, 0, lane, [&](const uint8_t *sI, const uint8_t *sJ, float2 cur, float2 &nxt, int &st, bool live) {
+        lk_call4_sse2<LEGACY>(a.g, sI, sJ, cur, nxt, st, live, lds, lane, L);
+    });
 }
 
 void launch_lk_sse2(const LkArgs &a0, int batch, int max_pts, hipStream_t st)
@@ -763,13 +539,6 @@ void launch_lk_sse2(const LkArgs &a0, int batch, int max_pts, hipStream_t st)
         }
         hipLaunchKernelGGL(lk_sse2_kernel<true>, dim3(batch * a.gx), dim3(64), 0, st, a);
     } else {
-#ifdef SVO_LKS_EXPERIMENTS
-        static const int exp_variant = getenv("SVO_LKS_EXP") ? atoi(getenv("SVO_LKS_EXP")) : 0;
-        if (exp_variant == 1) hipLaunchKernelGGL((lk_sse2_kernel<false, 1>), dim3(batch * a.gx), dim3(64), 0, st, a);
-        else if (exp_variant == 2) hipLaunchKernelGGL((lk_sse2_kernel<false, 2>), dim3(batch * a.gx), dim3(64), 0, st, a);
-        else if (exp_variant == 3) hipLaunchKernelGGL((lk_sse2_kernel<false, 3>), dim3(batch * a.gx), dim3(64), 0, st, a);
-        else
-#endif
         hipLaunchKernelGGL(lk_sse2_kernel<false>, dim3(batch * a.gx), dim3(64), 0, st, a);
     }
 }

@@ -532,7 +532,6 @@ static void fill_lk_common(svo_ctx *ctx, LkArgs &a, int n)
     a.pts_stride = 0;
     a.n_pts = nullptr; a.n_fixed = n; a.cap = n;
     a.match_err = ctx->cfg.feature_match_error;
-    a.match_err_f = (float)ctx->cfg.feature_match_error;
     a.accum = ctx->cfg.lk_accum;
 }
 

@@ -110,17 +110,6 @@ __device__ inline int dpp_xor2(int v) { return __builtin_amdgcn_update_dpp(0, v,
 __device__ inline int dpp_ror4(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, true); }
 __device__ inline int dpp_ror8(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, true); }
 
-// every lane ends with the sum over all lanes congruent to it mod 4
-__device__ inline int allsum_mod4(int v)
-{
-    v += dpp_ror4(v);
-    v += dpp_ror8(v);
-    auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    v = (int)(a[0] + a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)(b[0] + b[1]);
-}
-
 // Reduce-scatter of 8 per-lane values v[2*slot + t] (slot 0..3, t 0..1) whose 64-lane totals may
 // exceed 32 bits (each |v| < 2^28).  The SLOT is scattered over the four rows of 16 lanes with the
 // CDNA4 row exchanges: v_permlane32_swap / v_permlane16_swap hand the partner's half of a value
@@ -154,19 +143,6 @@ __device__ inline int reduce_scatter8_rows(const int (&v)[8], int lane)
     e += dpp_ror4(e);
     e += dpp_ror8(e);
     return e;
-}
-
-// The same result layout for ONE slot's two values (each |v| < 2^28) summed over all 64 lanes: {t0.lo, t1.lo, t0.hi, t1.hi}
-// in every quad of EVERY row.  A third of lk_kernel's wave-iterations serve a single slot (its three partners have
-// converged): 13 cross-lane / select operations with two row swaps instead of 22 with six.
-__device__ inline int reduce_pair_all(int v0, int v1, int lane)
-{
-    const bool b0 = lane & 1, b1 = lane & 2;
-    const int keep = b0 ? v1 : v0, give = b0 ? v0 : v1;
-    int d = keep + dpp_xor1(give);                         // t = lane bit 0; sums of 2 lanes
-    d += dpp_xor2(d);                                      // sums of 4 lanes (< 2^30), the same in lanes i and i ^ 2
-    const int e = b1 ? d >> 16 : d & 0xFFFF;               // half = lane bit 1
-    return allsum_mod4(e);                                 // over the 16 quads: |lo| < 2^20, |hi| < 2^18
 }
 
 // broadcast lane q of every quad to the whole quad

@@ -84,7 +84,7 @@ struct LkArgs {
     float2 *pts_out[kMaxChain];                   // call c output (failed points included)
     uint8_t *status[kMaxChain];
     uint8_t *keep;                                // ncalls == 4: deleteBadmatchFeatures predicate
-    float match_err_f; double match_err;          // feature_match_error
+    double match_err;                             // feature_match_error
     int accum;                                    // svo_config.lk_accum: SVO_LK_ACCUM_EXACT (lk.hip), _SSE2 or _SIMD128 (lk_sse2.hip)
     int gx, batch, spread;                                // filled by launch_lk: workgroups (sse2: waves) per item, items
 };

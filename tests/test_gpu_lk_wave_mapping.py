@@ -11,16 +11,23 @@ size, every output byte is the oracle's.  The shapes are the smallest at which t
   * svo_track_batch on the dense frames (> 3072 corners per frame): B = 1, 2, 3 give 2, 4 and 4 points per wave with
     a second chunk at B = 3; B = 4 is the throughput shape, whose 768 waves per item loop over chunks.
 
+The item mapping and the per-item loop are one driver shared by lk_kernel and the float-order lk_sse2_kernel (csrc/lk_common.h),
+so the one-pair and the batch cases run again with lk_accum = sse2, simd128 and sse2_legacy against the oracle in the matching
+accumulation mode (single-wave workgroups, 2048 / 1536 waves in the latency shape).
+
 The references are computed once per module and only read."""
 import numpy as np
 import pytest
 
+from test_gpu_parity_lk_sse2 import accum_oracle
 from test_gpu_parity_sequence import CHAIN_TIGHT, _check_record, _oracle_lk_sequence, _render, relfro
 
 pytestmark = pytest.mark.gpu
 
 W, H = 416, 128
 DISPARITY, STEP = 3, 2          # whole-pixel shifts of the dense frames: right eye, and frame to frame
+# lk_accum name -> (the package's constant, the oracle's accumulation mode)
+FLOAT_ORDERS = {"sse2": ("LK_ACCUM_SSE2", 2), "simd128": ("LK_ACCUM_SIMD128", 4), "sse2_legacy": ("LK_ACCUM_SSE2_LEGACY", 3)}
 
 
 @pytest.fixture(scope="module")
@@ -43,9 +50,9 @@ def _circular_reference(oracle, imgs, pts):
     return (pts, t1r, t2r, t2l), keep.astype(bool)
 
 
-def _check_circular(pkg, imgs, tracks, keep, idx, max_keypoints):
+def _check_circular(pkg, imgs, tracks, keep, idx, max_keypoints, **ctx_kw):
     """svo_circular_match on the points tracks[0][idx] == the oracle's rows idx that it keeps, in order, byte for byte."""
-    ctx = pkg.Context(W, H, device=0, max_keypoints=max_keypoints)
+    ctx = pkg.Context(W, H, device=0, max_keypoints=max_keypoints, **ctx_kw)
     for s, im in enumerate(imgs):
         ctx.build_pyramid(s, im)
     got = ctx.circular_match((0, 1, 2, 3), np.ascontiguousarray(tracks[0][idx]))
@@ -73,6 +80,31 @@ def test_first_n_corners_of_one_pair(pkg, tc, sparse, n):
     """Partial waves, waves without points, n_fixed: the first n oracle FAST corners."""
     imgs, (tracks, keep) = sparse
     _check_circular(pkg, imgs, tracks, keep, np.arange(n), max_keypoints=1024)
+
+
+@pytest.fixture(scope="module")
+def sparse_float(oracle, sparse):
+    """The same corners through the oracle in each float accumulation order."""
+    imgs, (tracks, _) = sparse
+    ref = {}
+    for name, (_, mode) in FLOAT_ORDERS.items():
+        with accum_oracle(oracle, mode):
+            ref[name] = _circular_reference(oracle, imgs, tracks[0])
+    return ref
+
+
+@pytest.mark.parametrize("n", [0, 1, 3, 4, 5, 15, 16, 17, 63, 64, 65])
+@pytest.mark.parametrize("accum", list(FLOAT_ORDERS))
+def test_first_n_corners_of_one_pair_float_order(pkg, tc, sparse, sparse_float, accum, n):
+    """The same partial waves through lk_sse2_kernel: the shared driver under the float-order call."""
+    imgs, (exact, _) = sparse
+    tracks, keep = sparse_float[accum]
+    kept = _check_circular(pkg, imgs, tracks, keep, np.arange(n), max_keypoints=1024, lk_accum=getattr(pkg, FLOAT_ORDERS[accum][0]))
+    if n == 65:
+        # the mode was in force: every track array of these points differs from the exact order's, and points survive
+        assert kept > 0
+        for t, e in zip(tracks[1:], exact[1:]):
+            assert t[:n].tobytes() != e[:n].tobytes()
 
 
 def test_n_equals_capacity_not_a_multiple_of_four(pkg, tc, sparse):
@@ -160,3 +192,23 @@ def seq17(oracle, synth, tc):
 def test_batch_sizes_around_the_xcd_mapping(pkg, tc, seq17, B):
     seq, frames, ref = seq17
     _batch(pkg, tc, seq, frames[:B + 1], ref)
+
+
+@pytest.fixture(scope="module")
+def seq17_float(oracle, seq17):
+    """The first nine pairs of seq17 through the oracle in each float accumulation order."""
+    seq, frames, _ = seq17
+    ref = {}
+    for name, (_, mode) in FLOAT_ORDERS.items():
+        with accum_oracle(oracle, mode):
+            ref[name] = _oracle_lk_sequence(oracle, seq, frames[:10])
+    return ref
+
+
+@pytest.mark.parametrize("B", [1, 3, 4, 8, 9])
+@pytest.mark.parametrize("accum", list(FLOAT_ORDERS))
+def test_batch_sizes_around_the_xcd_mapping_float_order(pkg, tc, seq17, seq17_float, accum, B):
+    """Latency shape (B = 1, 3), plain order (4), one item per XCD (8), XCD-aware part + plain remainder (9) through
+    lk_sse2_kernel."""
+    seq, frames, _ = seq17
+    _batch(pkg, tc, seq, frames[:B + 1], seq17_float[accum], lk_accum=getattr(pkg, FLOAT_ORDERS[accum][0]))
