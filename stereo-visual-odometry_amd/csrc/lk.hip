@@ -25,7 +25,14 @@
 //     pixel << 7, so the sample is the high half of its sum), then v_dot2 mismatch sums;
 //   * the 16 partial sums of an iteration (4 slots x {b1,b2} x {low,high half}) are reduced with ONE
 //     reduce-scatter over the rows (v_permlane32/16_swap + add, then DPP inside the row) that leaves
-//     slot s's four sums in every quad of row s, exactly where that slot's control lanes need them.
+//     slot s's four sums in every quad of row s, exactly where that slot's control lanes need them;
+//   * the flags of the control path (live, iterating at the level / in the loop, re-stage, converged, status) are
+//     wave-uniform LANE MASKS in SGPR pairs (lk_common.h): vector compares write them, the scalar unit combines them,
+//     a ballot is the mask itself and one v_cndmask_b32 applies it; a slot that sits an iteration out leaves its
+//     partial sums undefined instead of zero-filling them ("dead slots" below).  A wave-iteration with all four
+//     slots at work is 207 vector instructions: 87 of control, reduction and solve + 30 per slot (3 v_readlane, 1 address
+//     add, 14 + 8 v_dot2, 3 v_perm, 1 shift) -- 221 = 101 + 4 x 30 with bool flags and zero fills; the loop body has
+//     no branch besides the per-slot skips, the re-stage test and the near-epsilon f64 test.
 // The column-word J tiles cost 4x the LDS of byte tiles (13 KB per wave): three waves per SIMD, 168 VGPRs.
 // A wave's life varies 2x with the iteration counts of its points, so a throughput launch's workgroup is
 // ONE wave: it gives its LDS back the moment it ends and the dispatcher starts the next one (four-wave
@@ -155,10 +162,23 @@ __device__ __forceinline__ void mismatch_slot(const uint32_t (&C)[8], uint32_t W
 }
 
 
-// One cv::calcOpticalFlowPyrLK call for the wave's four points.  Control values (prevPt, outPt,
-// status, live) are per lane = per slot lane >> 4; the rules they follow are lk_common.h's.
+// Partial sums that are defined without an instruction.  DEAD SLOTS: a slot that does no pixel work in a pass (its bit
+// of m_on / it_on is clear) hands reduce_scatter8_rows whatever these registers hold instead of zeros (zero-filling cost
+// 8 v_mov per wave-iteration and 12 per level).  That garbage reaches neither a live slot nor a stored byte:
+//   * reduce_scatter8_rows never mixes slots: its two swap steps hand the values of slot s to row s of the wave and
+//     every later step adds lanes of one row, so rows of live slots sum live values only (integer adds: no traps);
+//   * row s's results are read by slot s's control lanes alone, and every use of what they become is guarded by that
+//     slot's flag: A11, A12, A22, D, minEig, Dinv by "lvl_on &" in level_solve_setup and by it_on (a subset of lvl_on)
+//     in the iterations; b1, b2 and the step by "it_on &" in iter_update's near-epsilon test, nextPt selects and
+//     returned mask (lk_common.h spells the guards out next to each rule).
+// (one statement for all sums of a slot: identical single definitions are merged into one register and copied apart)
+__device__ __forceinline__ void undefined_sums(int &x, int &y) { asm("" : "=v"(x), "=v"(y)); }
+__device__ __forceinline__ void undefined_sums(int &x, int &y, int &z) { asm("" : "=v"(x), "=v"(y), "=v"(z)); }
+
+// One cv::calcOpticalFlowPyrLK call for the wave's four points.  Control values (prevPt, outPt) are per lane = per
+// slot lane >> 4, flags (status, live) lane masks; the rules they follow are lk_common.h's.
 __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI, const uint8_t *slotJ, float2 prevPt,
-                                         float2 &outPt, int &status, bool live, uint32_t *lds, const uint32_t *lds_wg,
+                                         float2 &outPt, lanemask &status, lanemask live, uint32_t *lds, const uint32_t *lds_wg,
                                          int wave_off, int lane)
 {
     typedef ExactTile T;
@@ -176,7 +196,7 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
     const StageLane q = stage_lane<T::kColDw>(lane);
     const uint32_t lds_base = (uint32_t)(size_t)(lds_cu32 *)lds;   // byte address of the wave's LDS region
     const int vround = j_sample_rounding();
-    status = 1;
+    status = ~0ull;
     float nx = 0.f, ny = 0.f;                    // nextPts[i]
     uint32_t rI[kSlots][3][2];
     request_I<T>(rI, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
@@ -184,10 +204,10 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         LK_AT(0);
         // ---- control: window position and weights of every slot, the J window of the first iteration
         LkLevel lv = level_begin<T>(g, level, prevPt, live, nx, ny, status);
-        bool lvl_on = lv.on;
+        lanemask lvl_on = lv.on;
         const int w = lv.w, h = lv.h, pitch = g.pitch[level];
         const int offI = (lv.ipx - 1) - i_tile_x0<T>(lv.ipx);
-        const unsigned long long m_on = __ballot(lvl_on), m_j = __ballot(lv.tx0 != kNoJTile);
+        const lanemask m_on = lvl_on, m_j = lv.j_staged;
         uint32_t q_src[3];                       // lane part of the tile source offsets at this level
         stage_src(q_src, q, pitch);
         uint32_t rJ[kSlots][3][2];
@@ -196,21 +216,21 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         int pA[kSlots][3];
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_on >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_on, s)) continue;
             tile_store_i<T>(lds + s * T::kTileDw, rI[s], q, lane);
         }
         // the J tiles are requested now (vmcnt counts in order: the waits above were for the I tiles only)
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_j >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_j, s)) continue;
             tile_request<T::kJPairs>(rJ[s], g, level, pitch, slotJ, lv.tx0, lv.ty0, s, q_src, lane);
         }
         wave_lds_fence();
         LK_AT(1);                                // 0 -> 1: level control, I staging, J requests
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            pA[s][0] = pA[s][1] = pA[s][2] = 0;
-            if (!((m_on >> (16 * s)) & 1ull)) continue;
+            undefined_sums(pA[s][0], pA[s][1], pA[s][2]);      // dead slots: above
+            if (!slot_bit(m_on, s)) continue;
             const uint32_t qaddr = lds_base + (uint32_t)((s * T::kTileDw + __builtin_amdgcn_readlane(offI, 16 * s) * T::kColDw) * 4);
             const uint32_t W01s = __builtin_amdgcn_readlane(lv.WIa, 16 * s), W23s = __builtin_amdgcn_readlane(lv.WIb, 16 * s);
             const int ipxs = __builtin_amdgcn_readlane(lv.ipx, 16 * s), ipys = __builtin_amdgcn_readlane(lv.ipy, 16 * s);
@@ -225,7 +245,7 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         wave_lds_fence();                        // the J tiles reuse the I tiles' LDS
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_j >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_j, s)) continue;
             tile_store_j<T, false>(lds + s * T::kTileDw, rJ[s], q, lane);
         }
         wave_lds_fence();
@@ -249,17 +269,17 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         if (level > 0) request_I<T>(rI, g, level - 1, slotI, prevPt, live, q, lane);
         LK_AT(3);                                // 2 -> 3: J stores, A reduction, 2x2 set-up, next level's I requests
         float pdx = 0.f, pdy = 0.f;
-        bool it_on = lvl_on;
+        lanemask it_on = lvl_on;
         for (int j = 0; j < kLkMaxIter; j++) {
-            if (!__any(it_on)) break;
+            if (!it_on) break;
             LK_AT(4);
             const LkIter it = iter_begin<T>(lv.qx, lv.qy, w, h, level, lane, it_on, status, lv.tx0, lv.ty0);
             it_on = it.on;
-            const unsigned long long m_it = __ballot(it_on), m_rs = __ballot(it.restage);
+            const lanemask m_it = it_on, m_rs = it.restage;
             if (__builtin_expect(m_rs != 0, 0)) {     // a window drifted out of its tile
 #pragma unroll
                 for (int s = 0; s < kSlots; s++) {
-                    if (!((m_rs >> (16 * s)) & 1ull)) continue;
+                    if (!slot_bit(m_rs, s)) continue;
                     uint32_t r[3][2];
                     tile_request<T::kJPairs>(r, g, level, pitch, slotJ, lv.tx0, lv.ty0, s, q_src, lane);
                     tile_store_j<T, false>(lds + s * T::kTileDw, r, q, lane);
@@ -270,8 +290,8 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
             int pb[kSlots][2];
 #pragma unroll
             for (int s = 0; s < kSlots; s++) {
-                pb[s][0] = pb[s][1] = 0;
-                if (!((m_it >> (16 * s)) & 1ull)) continue;
+                undefined_sums(pb[s][0], pb[s][1]);                // dead slots: above
+                if (!slot_bit(m_it, s)) continue;
                 const int joffs = __builtin_amdgcn_readlane(it.joff, 16 * s);
                 const uint32_t Was = __builtin_amdgcn_readlane(it.Wa, 16 * s), Wbs = __builtin_amdgcn_readlane(it.Wb, 16 * s);
                 // byte address = workgroup array + slot part (SGPR) + lane part: one add, no re-alignment of an index
@@ -323,7 +343,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(3, 3))) 
     __shared__ uint32_t lds[W * kLdsDwPerWave];
     const int wave = W == 1 ? 0 : (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     uint32_t *my = lds + wave * kLdsDwPerWave;
-    lk_track_item<W>(a, wave, lane, [&](const uint8_t *sI, const uint8_t *sJ, float2 cur, float2 &nxt, int &st, bool live) {
+    lk_track_item<W>(a, wave, lane, [&](const uint8_t *sI, const uint8_t *sJ, float2 cur, float2 &nxt, lanemask &st, lanemask live) {
         lk_call4(a.g, sI, sJ, cur, nxt, st, live, my, lds, wave * (kLdsDwPerWave * 4), lane);
     });
 }

@@ -92,10 +92,37 @@ __device__ __forceinline__ PackedWeights bilinear_weights(float a, float b)
     return w;
 }
 
+// ---- flags as lane masks ------------------------------------------------------------------------------------------
+// Every per-slot flag of the control path (live, the level / iteration flags, re-stage, converged, status) is a
+// wave-uniform 64-bit LANE MASK in an SGPR pair: bit l = the flag of lane l, i.e. of slot l >> 4.  A mask comes straight
+// out of a vector compare (the builtins below write the compare's SGPR-pair result; no lane is ever masked off in the
+// callers, so a bit is the predicate of its lane and ~m is its negation), masks combine on the scalar unit (&, |, &~), a
+// ballot is the mask itself, an any-test is m != 0, and a mask is applied with ONE v_cndmask_b32 whose condition operand is
+// the SGPR pair.  A flag kept as a bool is a divergent i1: every ballot of it came out as v_cndmask_b32 v, 0, 1, s[..] +
+// v_cmp_ne_u32 (the compiler re-masks it with exec), and every "if (flag)" as an s_and_saveexec diamond.
+// The predicates are the ones of the bool form: "a < b" on floats is the ORDERED compare (false for a NaN), and a
+// negated flag is the mask's complement, which is true for a NaN exactly where "!(a < b)" is.
+typedef unsigned long long lanemask;
+enum { kIcmpUgt = 34, kIcmpUge = 35 };                                // llvm::CmpInst predicates of the compare builtins
+enum { kFcmpOgt = 2, kFcmpOlt = 4, kFcmpOle = 5 };
+__device__ __forceinline__ lanemask mask_ugt(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, kIcmpUgt); }
+__device__ __forceinline__ lanemask mask_uge(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, kIcmpUge); }
+// float compares: __builtin_amdgcn_fcmpf (the builtin without the f is the DOUBLE compare and converts its operands)
+__device__ __forceinline__ lanemask mask_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOlt); }
+__device__ __forceinline__ lanemask mask_le(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOle); }
+__device__ __forceinline__ lanemask mask_le(double a, double b) { return __builtin_amdgcn_fcmp(a, b, kFcmpOle); }
+__device__ __forceinline__ lanemask mask_gt(double a, double b) { return __builtin_amdgcn_fcmp(a, b, kFcmpOgt); }
+// m ? a : b per lane: v_cndmask_b32 d, b, a, s[m]
+__device__ __forceinline__ bool lane_of(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ int select(int a, int b, lanemask m) { return lane_of(m) ? a : b; }
+__device__ __forceinline__ float select(float a, float b, lanemask m) { return lane_of(m) ? a : b; }
+// slot s's bit of a mask (its control lanes all carry the same flag)
+__device__ __forceinline__ bool slot_bit(lanemask m, int s) { return (m >> (16 * s)) & 1ull; }
+
 // "ix < -win || ix >= w || iy < -win || iy >= h" with two unsigned compares
-__device__ __forceinline__ bool window_oob(int ix, int iy, int w, int h)
+__device__ __forceinline__ lanemask window_oob(int ix, int iy, int w, int h)
 {
-    return (unsigned)(ix + kWin) >= (unsigned)(w + kWin) || (unsigned)(iy + kWin) >= (unsigned)(h + kWin);
+    return mask_uge((unsigned)(ix + kWin), (unsigned)(w + kWin)) | mask_uge((unsigned)(iy + kWin), (unsigned)(h + kWin));
 }
 
 // ---- one iteration's pixel work for one slot --------------------------------------------------
@@ -270,18 +297,18 @@ template <class T> __device__ __forceinline__ int i_tile_x0(int ipx) { return T:
 // loop), so their latency is covered by the previous level's iterations.
 template <class T>
 __device__ __forceinline__ void request_I(uint32_t (&rI)[kSlots][3][2], const PyrGeom &g, int level, const uint8_t *slotI,
-                                          float2 prevPt, bool live, const StageLane &q, int lane)
+                                          float2 prevPt, lanemask live, const StageLane &q, int lane)
 {
     const float lscale = 1.f / (float)(1 << level);
     const int ipx = cv_floor(prevPt.x * lscale - kHalfWin), ipy = cv_floor(prevPt.y * lscale - kHalfWin);
     const int pitch = g.pitch[level];
-    const unsigned long long m = __ballot(live && !window_oob(ipx, ipy, g.w[level], g.h[level]));
+    const lanemask m = live & ~window_oob(ipx, ipy, g.w[level], g.h[level]);
     const int x0 = i_tile_x0<T>(ipx), y0 = ipy - 1;
     uint32_t src[3];
     stage_src(src, q, pitch);
 #pragma unroll
     for (int s = 0; s < kSlots; s++) {
-        if (!((m >> (16 * s)) & 1ull)) continue;
+        if (!slot_bit(m, s)) continue;
         tile_request<T::kQPairs>(rI[s], g, level, pitch, slotI, x0, y0, s, src, lane);
     }
 }
@@ -293,13 +320,15 @@ struct LkLevel {
     int w, h;
     int ipx, ipy;               // I window corner
     uint32_t WIa, WIb;          // I weights
-    bool on;                    // the slot iterates at this level
+    lanemask on;                // the slot iterates at this level
     float qx, qy;               // nextPt - halfWin
     int tx0, ty0;               // J tile origin; tx0 == kNoJTile: none staged
+    lanemask j_staged;          // the slot has a J tile at the level's start (tx0 != kNoJTile)
 };
+// (status: the mask of the slots whose status byte is still 1)
 template <class T>
-__device__ __forceinline__ LkLevel level_begin(const PyrGeom &g, int level, float2 prevPt, bool live, float &nx, float &ny,
-                                               int &status)
+__device__ __forceinline__ LkLevel level_begin(const PyrGeom &g, int level, float2 prevPt, lanemask live, float &nx, float &ny,
+                                               lanemask &status)
 {
     LkLevel v;
     v.w = g.w[level]; v.h = g.h[level];
@@ -309,97 +338,104 @@ __device__ __forceinline__ LkLevel level_begin(const PyrGeom &g, int level, floa
     else { nx = nx * 2.f; ny = ny * 2.f; }
     px -= kHalfWin; py -= kHalfWin;
     v.ipx = cv_floor(px); v.ipy = cv_floor(py);
-    const bool oob = window_oob(v.ipx, v.ipy, v.w, v.h);
-    if (live && oob && level == 0) status = 0;
-    v.on = live && !oob;
+    const lanemask oob = window_oob(v.ipx, v.ipy, v.w, v.h);
+    if (level == 0) status &= ~(live & oob);
+    v.on = live & ~oob;
     const PackedWeights wt = bilinear_weights(px - (float)v.ipx, py - (float)v.ipy);
     v.WIa = wt.Wa; v.WIb = wt.Wb;
     v.qx = nx - kHalfWin; v.qy = ny - kHalfWin;
-    v.tx0 = kNoJTile; v.ty0 = 0;
     const int inx = cv_floor(v.qx), iny = cv_floor(v.qy);
-    if (v.on && !window_oob(inx, iny, v.w, v.h)) { v.tx0 = inx - T::kJMargin; v.ty0 = iny - T::kJMargin; }
+    v.j_staged = v.on & ~window_oob(inx, iny, v.w, v.h);
+    v.tx0 = select(inx - T::kJMargin, kNoJTile, v.j_staged); v.ty0 = select(iny - T::kJMargin, 0, v.j_staged);
     return v;
 }
 
 // The 2x2 system of a level: a slot whose minimum eigenvalue or determinant is too small stops here (status 0 at
-// level 0).  Dinv = 1 / D; returns whether the slot goes on.  (Flags travel by value: a bool behind a reference becomes
-// a byte in a VGPR where the loops carry it, instead of a lane mask.)
-__device__ __forceinline__ bool level_solve_setup(float A11, float A12, float A22, int level, bool lvl_on, int &status, float &Dinv)
+// level 0).  Dinv = 1 / D; returns the slots that go on.  The sums of a slot that is not lvl_on are whatever its row
+// of the reduction held (lk.hip, "dead slots"): its D, minEig and Dinv are computed and never used -- `degenerate` acts
+// on status and on the returned mask only through "lvl_on &".
+__device__ __forceinline__ lanemask level_solve_setup(float A11, float A12, float A22, int level, lanemask lvl_on, lanemask &status,
+                                                      float &Dinv)
 {
     const float D = A11 * A22 - A12 * A12;
     const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
                          (float)(2 * kWin * kWin);
-    const bool degenerate = minEig < 0.001f || D < 1.1920929e-07f;
-    if (lvl_on && degenerate && level == 0) status = 0;
+    const lanemask degenerate = mask_lt(minEig, 0.001f) | mask_lt(D, 1.1920929e-07f);
+    if (level == 0) status &= ~(lvl_on & degenerate);
     Dinv = 1.f / D;
-    return lvl_on && !degenerate;
+    return lvl_on & ~degenerate;
 }
 
 // An iteration's start: the J window position and weights, the status rule for a window that left the level, and the
 // re-stage test: the tile holds kJMargin spare rows and columns on every side of the window it was staged for; a
 // window that drifted further gets a new tile around itself.
+// A slot that does not iterate computes all of this from a stale window position (iter_update); nothing of it is used:
+// status and restage carry "it_on &", the tile origin moves under restage only, and the weights and joff of a slot are
+// read by the pixel work of that slot alone, which runs under the slot's bit of `on`.
 struct LkIter {
-    bool on;                    // the slot still iterates
+    lanemask on;                // the slot still iterates
     uint32_t Wa, Wb;            // J weights
     int joff;                   // slot part of the J sample offset (bytes), tile position of the slot included
-    bool restage;
+    lanemask restage;
 };
 template <class T>
-__device__ __forceinline__ LkIter iter_begin(float qx, float qy, int w, int h, int level, int lane, bool it_on, int &status,
+__device__ __forceinline__ LkIter iter_begin(float qx, float qy, int w, int h, int level, int lane, lanemask it_on, lanemask &status,
                                              int &tx0, int &ty0)
 {
     LkIter it;
     const int inx = cv_floor(qx), iny = cv_floor(qy);
-    if (it_on && window_oob(inx, iny, w, h)) {
-        if (level == 0) status = 0;
-        it_on = false;
-    }
+    const lanemask oob = window_oob(inx, iny, w, h);
+    if (level == 0) status &= ~(it_on & oob);
+    it_on &= ~oob;
     const PackedWeights wj = bilinear_weights(qx - (float)inx, qy - (float)iny);
     it.Wa = wj.Wa; it.Wb = wj.Wb;
-    int cx = inx - tx0, cy = iny - ty0;
-    it.restage = it_on && ((unsigned)cx > (unsigned)(2 * T::kJMargin) || (unsigned)cy > (unsigned)(2 * T::kJMargin));
-    if (it.restage) { tx0 = inx - T::kJMargin; ty0 = iny - T::kJMargin; cx = T::kJMargin; cy = T::kJMargin; }
+    it.restage = it_on & (mask_ugt((unsigned)(inx - tx0), (unsigned)(2 * T::kJMargin)) |
+                          mask_ugt((unsigned)(iny - ty0), (unsigned)(2 * T::kJMargin)));
+    // a re-staged tile starts kJMargin before the window: cx = cy = kJMargin then fall out of the new origin
+    tx0 = select(inx - T::kJMargin, tx0, it.restage); ty0 = select(iny - T::kJMargin, ty0, it.restage);
+    const int cx = inx - tx0, cy = iny - ty0;
     it.joff = ((int)__umul24((unsigned)cx, T::kColDw) + cy + (lane >> 4) * T::kTileDw) * 4;
     it.on = it_on;
     return it;
 }
 
 // An iteration's end: the 2x2 solve, the step, the convergence and oscillation tests (a slot drops out when it
-// converges or oscillates); returns whether the slot goes on
-__device__ __forceinline__ bool iter_update(float A11, float A12, float A22, float Dinv, float b1f, float b2f, int j, bool it_on,
-                                            float &qx, float &qy, float &nx, float &ny, float &pdx, float &pdy)
+// converges or oscillates); returns the slots that go on.
+// nextPt (nx, ny) moves under the slot's flag.  The window position qx, qy and prevDelta are working values of the
+// iterations: they take the step in every lane, and a slot that has stopped (or whose b sums are what a dead row of the
+// reduction held, lk.hip "dead slots") only ever feeds them to iter_begin and to the tests below, where every use
+// carries "it_on &"; the next level recomputes qx, qy from nextPt and resets prevDelta.
+__device__ __forceinline__ lanemask iter_update(float A11, float A12, float A22, float Dinv, float b1f, float b2f, int j, lanemask it_on,
+                                                float &qx, float &qy, float &nx, float &ny, float &pdx, float &pdy)
 {
     const float dlx = (A12 * b2f - A22 * b1f) * Dinv;
     const float dly = (A12 * b1f - A11 * b2f) * Dinv;
     // "delta.ddot(delta) <= epsilon" is a double comparison upstream; float decides it unless
     // the sum lands within 1e-4 relative of epsilon (float error here < 2e-7 relative)
     const float dd = dlx * dlx + dly * dly;
-    bool conv = dd <= 0.9999e-4f;
-    if (__builtin_expect(__any(it_on && !conv && dd < 1.0001e-4f), 0)) {
+    lanemask conv = mask_le(dd, 0.9999e-4f);
+    if (__builtin_expect((it_on & ~conv & mask_lt(dd, 1.0001e-4f)) != 0, 0)) {
         asm volatile("" ::: "memory");               // a real branch: if-converted, the f64 path ran every iteration
-        conv = (double)dlx * (double)dlx + (double)dly * (double)dly <= 0.01 * 0.01;
+        conv = mask_le((double)dlx * (double)dlx + (double)dly * (double)dly, 0.01 * 0.01);
     }
-    if (it_on) {
-        qx += dlx; qy += dly;
-        nx = qx + kHalfWin; ny = qy + kHalfWin;
-        if (conv) it_on = false;
-        // "std::abs(delta.x + prevDelta.x) < 0.01" compares a float with the double 0.01; the
-        // largest float below 0.01 is 0.01f itself, so "<= 0.01f" in float is the same predicate
-        else if (j > 0 && fabsf(dlx + pdx) <= 0.01f && fabsf(dly + pdy) <= 0.01f) {
-            nx -= dlx * 0.5f; ny -= dly * 0.5f;
-            it_on = false;
-        }
-        pdx = dlx; pdy = dly;
-    }
-    return it_on;
+    qx += dlx; qy += dly;
+    // "std::abs(delta.x + prevDelta.x) < 0.01" compares a float with the double 0.01; the
+    // largest float below 0.01 is 0.01f itself, so "<= 0.01f" in float is the same predicate
+    const lanemask osc = j > 0 ? it_on & ~conv & mask_le(fabsf(dlx + pdx), 0.01f) & mask_le(fabsf(dly + pdy), 0.01f) : 0ull;
+    const float sx = qx + kHalfWin, sy = qy + kHalfWin;
+    nx = select(select(sx - dlx * 0.5f, sx, osc), nx, it_on);
+    ny = select(select(sy - dly * 0.5f, sy, osc), ny, it_on);
+    pdx = dlx; pdy = dly;
+    return it_on & ~conv & ~osc;
 }
 
 // err is requested by the reference: the final window must still be inside (A.4 step 7)
-__device__ __forceinline__ void final_window_check(float nx, float ny, int w, int h, int level, bool live, int &status)
+// (a slot that is not live, or whose status is 0 already, is not changed by clearing its bit again)
+__device__ __forceinline__ void final_window_check(float nx, float ny, int w, int h, int level, lanemask live, lanemask &status)
 {
-    if (live && status && level == 0) {
+    if (level == 0) {
         const int fx = cv_floor(nx - kHalfWin), fy = cv_floor(ny - kHalfWin);
-        if (window_oob(fx, fy, w, h)) status = 0;
+        status &= ~(live & window_oob(fx, fy, w, h));
     }
 }
 
@@ -450,35 +486,34 @@ __device__ __forceinline__ void lk_track_item(const LkArgs &a, int wave, int lan
         const int64_t po = (int64_t)b * a.pts_stride + (valid ? idx : first);
         const float2 p0 = a.pts_in[po];
         float2 cur = p0, nxt;
-        bool outside = p0.x < 0 || p0.y < 0, bad = false, noepi = false;
-        bool live = valid;
+        // the flags of the chain as lane masks (see "flags as lane masks" above)
+        lanemask outside = mask_lt(p0.x, 0.f) | mask_lt(p0.y, 0.f), bad = 0, noepi = 0;
+        lanemask live = __ballot(valid);
         float prev_y = p0.y;
 #pragma nounroll
         for (int c = 0; c < a.ncalls; c++) {
             const uint8_t *sI = a.prev[c] + (int64_t)b * a.slot_stride;
             const uint8_t *sJ = a.next[c] + (int64_t)b * a.slot_stride;
-            int st;
+            lanemask st;                                        // the slots with status 1
             lk_call(sI, sJ, cur, nxt, st, live);
-            if (writer && live) {
+            if (writer && lane_of(live)) {
                 a.pts_out[c][po] = nxt;
-                a.status[c][po] = (uint8_t)st;
+                a.status[c][po] = (uint8_t)select(1, 0, st);
             }
             // Tracking::deleteBadmatchFeatures terms (p0 = t1_left, p1 = t1_right, p2 = t2_right,
             // p3 = t2_left, p0_return = LK#4 output; call-site mapping src/tracking.cpp:619-620,
             // predicate :623-660)
-            if (live) {
-                outside = outside || nxt.x < 0 || nxt.y < 0;
-                bad = bad || st == 0;
-                if (c == 0 || c == 2) noepi = noepi || (double)fabsf(prev_y - nxt.y) > a.match_err;   // |y0-y1|, |y2-y3|
-                prev_y = nxt.y;
-                cur = nxt;
-            }
+            outside |= live & (mask_lt(nxt.x, 0.f) | mask_lt(nxt.y, 0.f));
+            bad |= live & ~st;
+            if (c == 0 || c == 2) noepi |= live & mask_gt((double)fabsf(prev_y - nxt.y), a.match_err);   // |y0-y1|, |y2-y3|
+            prev_y = select(nxt.y, prev_y, live);
+            cur.x = select(nxt.x, cur.x, live); cur.y = select(nxt.y, cur.y, live);
             // a rejected point can never be kept: the remaining calls of the circular chain only feed
             // the keep predicate (their pts_out/status entries are scratch in the fused mode)
-            if (a.ncalls == 4 && (outside || bad || noepi)) live = false;
-            if (!__any(live)) break;
+            if (a.ncalls == 4) live &= ~(outside | bad | noepi);
+            if (!live) break;
         }
-        if (a.ncalls == 4 && writer) a.keep[po] = !(outside || bad || noepi);
+        if (a.ncalls == 4 && writer) a.keep[po] = !lane_of(outside | bad | noepi);
         wave_lds_fence();                                      // the next chunk restages this wave's tiles
     }
 }

@@ -386,7 +386,7 @@ __device__ __forceinline__ float combine_a(float r)
 // lane = per slot lane >> 4, the rules they follow are lk_common.h's).
 template <bool LEGACY>
 __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *slotI, const uint8_t *slotJ, float2 prevPt,
-                                              float2 &outPt, int &status, bool live, uint32_t *lds, int lane,
+                                              float2 &outPt, lanemask &status, lanemask live, uint32_t *lds, int lane,
                                               const Sse2Lane &L)
 {
     typedef ChainTile T;
@@ -394,34 +394,34 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
     const StageLane q = stage_lane<T::kColDw>(lane);
     const uint32_t lds_base = (uint32_t)(size_t)(lds_cu32 *)lds;
     const int vround = j_sample_rounding();
-    status = 1;
+    status = ~0ull;
     float nx = 0.f, ny = 0.f;
     uint32_t rI[kSlots][3][2];
     request_I<T>(rI, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
     for (int level = g.nlevels - 1; level >= 0; --level) {
         LkLevel lv = level_begin<T>(g, level, prevPt, live, nx, ny, status);
-        bool lvl_on = lv.on;
+        lanemask lvl_on = lv.on;
         const int w = lv.w, h = lv.h, pitch = g.pitch[level];
-        const unsigned long long m_on = __ballot(lvl_on), m_j = __ballot(lv.tx0 != kNoJTile);
+        const lanemask m_on = lvl_on, m_j = lv.j_staged;
         uint32_t q_src[3];
         stage_src(q_src, q, pitch);
         uint32_t rJ[kSlots][3][2];
         // ---- I tiles as row-pair column words (the J tiles take their place afterwards)
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_on >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_on, s)) continue;
             tile_store_i<T>(lds + s * T::kTileDw, rI[s], q, lane);
         }
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_j >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_j, s)) continue;
             tile_request<T::kJPairs>(rJ[s], g, level, pitch, slotJ, lv.tx0, lv.ty0, s, q_src, lane);
         }
         wave_lds_fence();
         // ---- patches; their words Ix | Iy << 16 go to the chain staging in the order of the A chains
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_on >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_on, s)) continue;
             const uint32_t qaddr = lds_base + (uint32_t)(s * T::kTileDw * 4);
             const uint32_t W01s = __builtin_amdgcn_readlane(lv.WIa, 16 * s), W23s = __builtin_amdgcn_readlane(lv.WIb, 16 * s);
             const int ipxs = __builtin_amdgcn_readlane(lv.ipx, 16 * s), ipys = __builtin_amdgcn_readlane(lv.ipy, 16 * s);
@@ -437,7 +437,7 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
         wave_lds_fence();                        // the patch words are complete; the J tiles reuse the I tiles' LDS
 #pragma unroll
         for (int s = 0; s < kSlots; s++) {
-            if (!((m_j >> (16 * s)) & 1ull)) continue;
+            if (!slot_bit(m_j, s)) continue;
             tile_store_j<T, false>(lds + s * T::kTileDw, rJ[s], q, lane);
         }
         float A11, A12, A22;
@@ -455,16 +455,16 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
 
         if (level > 0) request_I<T>(rI, g, level - 1, slotI, prevPt, live, q, lane);
         float pdx = 0.f, pdy = 0.f;
-        bool it_on = lvl_on;
+        lanemask it_on = lvl_on;
         for (int j = 0; j < kLkMaxIter; j++) {
-            if (!__any(it_on)) break;
+            if (!it_on) break;
             const LkIter it = iter_begin<T>(lv.qx, lv.qy, w, h, level, lane, it_on, status, lv.tx0, lv.ty0);
             it_on = it.on;
-            const unsigned long long m_it = __ballot(it_on), m_rs = __ballot(it.restage);
+            const lanemask m_it = it_on, m_rs = it.restage;
             if (__builtin_expect(m_rs != 0, 0)) {     // a window drifted out of its tile
 #pragma unroll
                 for (int s = 0; s < kSlots; s++) {
-                    if (!((m_rs >> (16 * s)) & 1ull)) continue;
+                    if (!slot_bit(m_rs, s)) continue;
                     uint32_t r[3][2];
                     tile_request<T::kJPairs>(r, g, level, pitch, slotJ, lv.tx0, lv.ty0, s, q_src, lane);
                     tile_store_j<T, true>(lds + s * T::kTileDw, r, q, lane);
@@ -473,7 +473,7 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
             }
 #pragma unroll
             for (int s = 0; s < kSlots; s++) {
-                if (!((m_it >> (16 * s)) & 1ull)) continue;
+                if (!slot_bit(m_it, s)) continue;
                 const int joffs = __builtin_amdgcn_readlane(it.joff, 16 * s);
                 const uint32_t Was = __builtin_amdgcn_readlane(it.Wa, 16 * s), Wbs = __builtin_amdgcn_readlane(it.Wb, 16 * s);
                 lds_cu32 *pj = (lds_cu32 *)(size_t)(lds_base + (uint32_t)joffs + L.qoff);
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     __shared__ __attribute__((aligned(16))) uint32_t lds[LEGACY ? kLdsDwLegacy : kLdsDwSse2];
     const int lane = threadIdx.x & 63;
     const Sse2Lane L = make_lane<LEGACY>(lane, (uint32_t)(size_t)(lds_cu32 *)lds, a.accum == 2);
-    lk_track_item<1>(a, 0, lane, [&](const uint8_t *sI, const uint8_t *sJ, float2 cur, float2 &nxt, int &st, bool live) {
+    lk_track_item<1>(a, 0, lane, [&](const uint8_t *sI, const uint8_t *sJ, float2 cur, float2 &nxt, lanemask &st, lanemask live) {
         lk_call4_sse2<LEGACY>(a.g, sI, sJ, cur, nxt, st, live, lds, lane, L);
     });
 }
