@@ -26,6 +26,8 @@
 //   * the 16 partial sums of an iteration (4 slots x {b1,b2} x {low,high half}) are reduced with ONE
 //     reduce-scatter over the rows (v_permlane32/16_swap + add, then DPP inside the row) that leaves
 //     slot s's four sums in every quad of row s, exactly where that slot's control lanes need them;
+//     the twelve A sums of a level (4 slots x {A11, A12, A22}) go the same way in one twelve-value reduce-scatter
+//     (reduce_scatter12_rows, svo_device.h);
 //   * the flags of the control path (live, iterating at the level / in the loop, re-stage, converged, status) are
 //     wave-uniform LANE MASKS in SGPR pairs (lk_common.h): vector compares write them, the scalar unit combines them,
 //     a ballot is the mask itself and one v_cndmask_b32 applies it; a slot that sits an iteration out leaves its
@@ -163,9 +165,10 @@ __device__ __forceinline__ void mismatch_slot(const uint32_t (&C)[8], uint32_t W
 
 
 // Partial sums that are defined without an instruction.  DEAD SLOTS: a slot that does no pixel work in a pass (its bit
-// of m_on / it_on is clear) hands reduce_scatter8_rows whatever these registers hold instead of zeros (zero-filling cost
-// 8 v_mov per wave-iteration and 12 per level).  That garbage reaches neither a live slot nor a stored byte:
-//   * reduce_scatter8_rows never mixes slots: its two swap steps hand the values of slot s to row s of the wave and
+// of m_on / it_on is clear) hands the reduce-scatter (reduce_scatter8_rows for b, reduce_scatter12_rows for A) whatever
+// these registers hold instead of zeros (zero-filling cost 8 v_mov per wave-iteration and 12 per level).  That garbage
+// reaches neither a live slot nor a stored byte:
+//   * neither reduce-scatter mixes slots: the two swap steps hand the values of slot s to row s of the wave and
 //     every later step adds lanes of one row, so rows of live slots sum live values only (integer adds: no traps);
 //   * row s's results are read by slot s's control lanes alone, and every use of what they become is guarded by that
 //     slot's flag: A11, A12, A22, D, minEig, Dinv by "lvl_on &" in level_solve_setup and by it_on (a subset of lvl_on)
@@ -199,7 +202,8 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
     status = ~0ull;
     float nx = 0.f, ny = 0.f;                    // nextPts[i]
     uint32_t rI[kSlots][3][2];
-    request_I<T>(rI, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
+    uint32_t q_src[3], q_next[3];                // lane part of the tile source offsets at the level / at the next one
+    request_I<T>(rI, q_src, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
     for (int level = g.nlevels - 1; level >= 0; --level) {
         LK_AT(0);
         // ---- control: window position and weights of every slot, the J window of the first iteration
@@ -208,8 +212,6 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         const int w = lv.w, h = lv.h, pitch = g.pitch[level];
         const int offI = (lv.ipx - 1) - i_tile_x0<T>(lv.ipx);
         const lanemask m_on = lvl_on, m_j = lv.j_staged;
-        uint32_t q_src[3];                       // lane part of the tile source offsets at this level
-        stage_src(q_src, q, pitch);
         uint32_t rJ[kSlots][3][2];
         // ---- I tiles (as row-pair column words; all four fit the wave's LDS region, which the J tiles
         //      take over afterwards), patches + A sums
@@ -251,13 +253,8 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         wave_lds_fence();
         float A11, A12, A22;
         {
-            int v1[8], v2[8];
-#pragma unroll
-            for (int s = 0; s < kSlots; s++) {
-                v1[2 * s] = pA[s][0]; v1[2 * s + 1] = pA[s][1];
-                v2[2 * s] = pA[s][2]; v2[2 * s + 1] = 0;
-            }
-            const int r1 = reduce_scatter8_rows(v1, lane), r2 = reduce_scatter8_rows(v2, lane);
+            int r1, r2;                          // row s: {A11.lo, A12.lo, A11.hi, A12.hi}, {A22.lo, A22.lo, A22.hi, A22.hi} of slot s
+            reduce_scatter12_rows(pA, lane, r1, r2);
             A11 = wide_to_f32(quad_bcast<2>(r1), quad_bcast<0>(r1)) * kFltScale;
             A12 = wide_to_f32(quad_bcast<3>(r1), quad_bcast<1>(r1)) * kFltScale;
             A22 = wide_to_f32(quad_bcast<2>(r2), quad_bcast<0>(r2)) * kFltScale;
@@ -266,7 +263,7 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
         lvl_on = level_solve_setup(A11, A12, A22, level, lvl_on, status, Dinv);
 
         // ---- iterations (all slots in lockstep; a slot drops out when it converges or leaves)
-        if (level > 0) request_I<T>(rI, g, level - 1, slotI, prevPt, live, q, lane);
+        if (level > 0) request_I<T>(rI, q_next, g, level - 1, slotI, prevPt, live, q, lane);
         LK_AT(3);                                // 2 -> 3: J stores, A reduction, 2x2 set-up, next level's I requests
         float pdx = 0.f, pdy = 0.f;
         lanemask it_on = lvl_on;
@@ -315,6 +312,10 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
             LK_AT(7);                            // 6 -> 7: reduce-scatter, solve, convergence tests
         }
         final_window_check(nx, ny, w, h, level, live, status);
+        if (level > 0) {
+#pragma unroll
+            for (int t = 0; t < 3; t++) q_src[t] = q_next[t];
+        }
     }
     outPt = make_float2(nx, ny);
     LK_CALL_END(lane);

@@ -119,6 +119,11 @@ __device__ __forceinline__ float select(float a, float b, lanemask m) { return l
 // slot s's bit of a mask (its control lanes all carry the same flag)
 __device__ __forceinline__ bool slot_bit(lanemask m, int s) { return (m >> (16 * s)) & 1ull; }
 
+// 1 / (1 << level) of a pyramid level (wave-uniform): 2^-level is a normal float, so its bit pattern is the biased exponent
+// 127 - level alone -- one scalar shift for the IEEE division sequence (convert, two v_div_scale, v_rcp, five fma / mul,
+// v_div_fmas, v_div_fixup) that the quotient costs.  The value is the quotient's, exactly: every product with it rounds as before.
+__device__ __forceinline__ float level_scale(int level) { return __uint_as_float((uint32_t)(127 - level) << 23); }
+
 // "ix < -win || ix >= w || iy < -win || iy >= h" with two unsigned compares
 __device__ __forceinline__ lanemask window_oob(int ix, int iy, int w, int h)
 {
@@ -166,11 +171,13 @@ __device__ __forceinline__ StageLane stage_lane(int lane)
     }
     return q;
 }
-// lane part of the items' source offsets at a level
+// lane part of the items' source offsets at a level: one 24-bit multiply-add each (the 32-bit product came out as
+// v_mad_u64_u32).  Exact: pr <= 27 (26 among the items in use) and the pitch of every accepted frame size is far below 2^24 (svo_create refuses
+// widths above 16384; kMaxLkPitch in svo_device.h, asserted where the geometry is built), so neither operand loses a bit.
 __device__ __forceinline__ void stage_src(uint32_t (&src)[3], const StageLane &q, int pitch)
 {
 #pragma unroll
-    for (int t = 0; t < 3; t++) src[t] = (uint32_t)(q.pr[t] * pitch + q.dc4[t]);
+    for (int t = 0; t < 3; t++) src[t] = __umul24((unsigned)q.pr[t], (unsigned)pitch) + (uint32_t)q.dc4[t];
 }
 // A tile's source dwords for this lane: rows `rowA` (upper) and `rowB` = rowA + pitch of every item, at 32-bit
 // offsets from the slot's wave-uniform base (global_load with an SGPR base: scalar part per slot, lane part per level)
@@ -294,17 +301,17 @@ __device__ __forceinline__ void patch_samples(const uint32_t (&Q12)[NC], const u
 template <class T> __device__ __forceinline__ int i_tile_x0(int ipx) { return T::kAlignedI ? (ipx - 1) & ~3 : ipx - 1; }
 
 // The I tiles of a level depend on prevPt only: they are requested one level ahead (the top level's before the level
-// loop), so their latency is covered by the previous level's iterations.
+// loop), so their latency is covered by the previous level's iterations.  `src`: the lane part of the level's tile source
+// offsets (stage_src), which the pass over that level uses again for its J tiles instead of forming it a second time.
 template <class T>
-__device__ __forceinline__ void request_I(uint32_t (&rI)[kSlots][3][2], const PyrGeom &g, int level, const uint8_t *slotI,
-                                          float2 prevPt, lanemask live, const StageLane &q, int lane)
+__device__ __forceinline__ void request_I(uint32_t (&rI)[kSlots][3][2], uint32_t (&src)[3], const PyrGeom &g, int level,
+                                          const uint8_t *slotI, float2 prevPt, lanemask live, const StageLane &q, int lane)
 {
-    const float lscale = 1.f / (float)(1 << level);
+    const float lscale = level_scale(level);
     const int ipx = cv_floor(prevPt.x * lscale - kHalfWin), ipy = cv_floor(prevPt.y * lscale - kHalfWin);
     const int pitch = g.pitch[level];
     const lanemask m = live & ~window_oob(ipx, ipy, g.w[level], g.h[level]);
     const int x0 = i_tile_x0<T>(ipx), y0 = ipy - 1;
-    uint32_t src[3];
     stage_src(src, q, pitch);
 #pragma unroll
     for (int s = 0; s < kSlots; s++) {
@@ -332,7 +339,7 @@ __device__ __forceinline__ LkLevel level_begin(const PyrGeom &g, int level, floa
 {
     LkLevel v;
     v.w = g.w[level]; v.h = g.h[level];
-    const float lscale = 1.f / (float)(1 << level);
+    const float lscale = level_scale(level);
     float px = prevPt.x * lscale, py = prevPt.y * lscale;
     if (level == g.nlevels - 1) { nx = px; ny = py; }
     else { nx = nx * 2.f; ny = ny * 2.f; }
@@ -350,6 +357,15 @@ __device__ __forceinline__ LkLevel level_begin(const PyrGeom &g, int level, floa
     return v;
 }
 
+// The minEig test without its division.  Upstream tests minEig = num / (2 * win * win) < 0.001f with num = A22 + A11 - sqrt(..); the
+// kernel returns no err, so the quotient is used in that comparison alone.  Correctly rounded division by the positive constant
+// 882.f is monotone (non-decreasing) in num, so the floats whose quotient lies below 0.001f are exactly those below one float T:
+//   fl(num / 882.f) < 0.001f  <=>  num < kMinEigNumBelow,
+// with both sides false for a NaN and for +inf and true for every negative num.  T is the smallest float whose rounded quotient
+// reaches 0.001f = 0x3A83126F: 0x3F61CAC1 = 0x1.c39582p-1 (its predecessor's quotient rounds to 0x3A83126E), found by bisection over
+// the float32 bit patterns and checked around T and over random floats by tests/test_host_lk_mineig_threshold.py.
+constexpr float kMinEigNumBelow = 0x1.c39582p-1f;
+
 // The 2x2 system of a level: a slot whose minimum eigenvalue or determinant is too small stops here (status 0 at
 // level 0).  Dinv = 1 / D; returns the slots that go on.  The sums of a slot that is not lvl_on are whatever its row
 // of the reduction held (lk.hip, "dead slots"): its D, minEig and Dinv are computed and never used -- `degenerate` acts
@@ -358,9 +374,9 @@ __device__ __forceinline__ lanemask level_solve_setup(float A11, float A12, floa
                                                       float &Dinv)
 {
     const float D = A11 * A22 - A12 * A12;
-    const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
-                         (float)(2 * kWin * kWin);
-    const lanemask degenerate = mask_lt(minEig, 0.001f) | mask_lt(D, 1.1920929e-07f);
+    const float minEigNum = A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12);      // minEig * (2 * kWin * kWin)
+    static_assert(2 * kWin * kWin == 882, "kMinEigNumBelow is derived for the divisor 882");
+    const lanemask degenerate = mask_lt(minEigNum, kMinEigNumBelow) | mask_lt(D, 1.1920929e-07f);
     if (level == 0) status &= ~(lvl_on & degenerate);
     Dinv = 1.f / D;
     return lvl_on & ~degenerate;

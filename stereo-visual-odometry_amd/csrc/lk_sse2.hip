@@ -397,14 +397,13 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
     status = ~0ull;
     float nx = 0.f, ny = 0.f;
     uint32_t rI[kSlots][3][2];
-    request_I<T>(rI, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
+    uint32_t q_src[3], q_next[3];                // lane part of the tile source offsets at the level / at the next one
+    request_I<T>(rI, q_src, g, g.nlevels - 1, slotI, prevPt, live, q, lane);
     for (int level = g.nlevels - 1; level >= 0; --level) {
         LkLevel lv = level_begin<T>(g, level, prevPt, live, nx, ny, status);
         lanemask lvl_on = lv.on;
         const int w = lv.w, h = lv.h, pitch = g.pitch[level];
         const lanemask m_on = lvl_on, m_j = lv.j_staged;
-        uint32_t q_src[3];
-        stage_src(q_src, q, pitch);
         uint32_t rJ[kSlots][3][2];
         // ---- I tiles as row-pair column words (the J tiles take their place afterwards)
 #pragma unroll
@@ -453,7 +452,7 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
         float Dinv;
         lvl_on = level_solve_setup(A11, A12, A22, level, lvl_on, status, Dinv);
 
-        if (level > 0) request_I<T>(rI, g, level - 1, slotI, prevPt, live, q, lane);
+        if (level > 0) request_I<T>(rI, q_next, g, level - 1, slotI, prevPt, live, q, lane);
         float pdx = 0.f, pdy = 0.f;
         lanemask it_on = lvl_on;
         for (int j = 0; j < kLkMaxIter; j++) {
@@ -503,6 +502,10 @@ __device__ __forceinline__ void lk_call4_sse2(const PyrGeom &g, const uint8_t *s
             it_on = iter_update(A11, A12, A22, Dinv, b1f, b2f, j, it_on, lv.qx, lv.qy, nx, ny, pdx, pdy);
         }
         final_window_check(nx, ny, w, h, level, live, status);
+        if (level > 0) {
+#pragma unroll
+            for (int t = 0; t < 3; t++) q_src[t] = q_next[t];
+        }
     }
     outPt = make_float2(nx, ny);
 }

@@ -56,6 +56,10 @@ static void dev_release(svo_ctx *ctx)
 }
 }  // namespace svo
 
+constexpr int kMaxFrameSide = 16384;                // svo_create refuses larger frames
+// the LK kernels form tile offsets with 24-bit multiplies (lk_common.h, stage_src): the widest accepted pitch fits
+static_assert(kMaxFrameSide + 2 * kPad + 63 <= kMaxLkPitch, "pitch of the widest accepted frame exceeds the LK kernels' 24-bit multiply");
+
 // Pyramid geometry: buildOpticalFlowPyramid stops adding levels once the next one would not
 // exceed the 21-pixel window ("if (sz.width <= winSize.width || sz.height <= winSize.height)").
 static void make_geom(int w, int h, PyrGeom *g)
@@ -167,7 +171,7 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
     double t_phase = now_ms();
     *out = nullptr;
     if (cfg->width < 32 || cfg->height < 32 || cfg->max_keypoints < 64 || cfg->max_batch < 1 ||
-        cfg->num_slots < 4 || cfg->width > 16384 || cfg->height > 16384)
+        cfg->num_slots < 4 || cfg->width > kMaxFrameSide || cfg->height > kMaxFrameSide)
         return SVO_ERR_ARG;
     if (cfg->lk_accum != SVO_LK_ACCUM_EXACT && cfg->lk_accum != SVO_LK_ACCUM_SSE2 && cfg->lk_accum != SVO_LK_ACCUM_SIMD128 &&
         cfg->lk_accum != SVO_LK_ACCUM_SSE2_LEGACY) {

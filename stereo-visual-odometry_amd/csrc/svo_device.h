@@ -11,6 +11,8 @@ constexpr int kMaxLevels = 4;      // LK maxLevel 3 (reference src/tracking.cpp:
 constexpr int kWin = 21;           // LK window
 constexpr int kLkMaxIter = 30;
 
+constexpr int kMaxLkPitch = (1 << 24) - 1;   // the LK kernels multiply a row index by the pitch with a 24-bit multiply (lk_common.h, stage_src)
+
 // Geometry of one padded pyramid slot; identical for every image of a context.
 struct PyrGeom {
     int nlevels;
@@ -143,6 +145,42 @@ __device__ inline int reduce_scatter8_rows(const int (&v)[8], int lane)
     e += dpp_ror4(e);
     e += dpp_ror8(e);
     return e;
+}
+
+// Reduce-scatter of TWELVE per-lane values v[slot][t] (slot 0..3, t 0..2; each |v| < 2^28, totals may exceed 32 bits):
+// reduce_scatter8_rows for t = 0, 1 plus the third value of every slot, exchanging real values only (two calls of the
+// eight-value form with the odd places filled with zeros swapped, added and selected four constants).  The row exchanges
+// are the same swap + add steps, three value pairs wide instead of four.  t = 2 has no partner to share lane bit 0 with:
+// its 4-lane sums are added to the neighbour's in place (one DPP add, no selects), so both lanes of a pair carry the
+// 8-lane sum, the split and the scatter of the halves over lane bit 1 then count every pair once, and the quad adds
+// finish the row as before.  On return every quad of row `slot` holds that slot's
+//   r01 = {t0.lo, t1.lo, t0.hi, t1.hi}   (exactly reduce_scatter8_rows' result),   r2 = {t2.lo, t2.lo, t2.hi, t2.hi}
+// Integer adds in another order: the sums are the same numbers (no step overflows: 8-lane sums < 2^31, halves < 2^16).
+// 9 swaps instead of the 12 of two eight-value calls, and no select for t = 2.
+__device__ inline void reduce_scatter12_rows(const int (&v)[4][3], int lane, int &r01, int &r2)
+{
+    const bool b0 = lane & 1, b1 = lane & 2;
+    int c[3];
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        int a[2];
+#pragma unroll
+        for (int s0 = 0; s0 < 2; s0++) {                   // lanes 0-31 keep slots 0,1; lanes 32-63 slots 2,3
+            auto x = __builtin_amdgcn_permlane32_swap((unsigned)v[s0][t], (unsigned)v[s0 + 2][t], false, false);
+            a[s0] = (int)(x[0] + x[1]);
+        }
+        auto x = __builtin_amdgcn_permlane16_swap((unsigned)a[0], (unsigned)a[1], false, false);   // even rows keep the even slot
+        c[t] = (int)(x[0] + x[1]);
+    }
+    const int keep = b0 ? c[1] : c[0], give = b0 ? c[0] : c[1];
+    const int d = keep + dpp_xor1(give);                   // t = lane bit 0; sums of 8 lanes
+    const int d2 = c[2] + dpp_xor1(c[2]);                  // t = 2 in both lanes of the pair
+    const int keep2 = b1 ? d >> 16 : d & 0xFFFF, give2 = b1 ? d & 0xFFFF : d >> 16;
+    const int keep3 = b1 ? d2 >> 16 : d2 & 0xFFFF, give3 = b1 ? d2 & 0xFFFF : d2 >> 16;
+    int e = keep2 + dpp_xor2(give2), e2 = keep3 + dpp_xor2(give3);     // half = lane bit 1
+    e += dpp_ror4(e); e2 += dpp_ror4(e2);
+    e += dpp_ror8(e); e2 += dpp_ror8(e2);
+    r01 = e; r2 = e2;
 }
 
 // broadcast lane q of every quad to the whole quad
