@@ -528,6 +528,80 @@ int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int height, int
                     int max_corners, double quality_level, double min_distance,
                     svo_keypoint *out, float *strength, int cap, int *n_out);
 
+/* ---- robust two-view pose refinement after solvePnPRansac (additive; detected by symbol, the ABI version stays 9 and
+ * svo_config / svo_step_result are unchanged) -------------------------------------------------------------------------------
+ * The stage the reference's author prepared and never finished: Tracking::G2O_EstimatePose_PnP (src/tracking.cpp:384-426,
+ * include/lzb_vio/tracking.h:82; g2o found and linked at CMakeLists.txt:31,54, the body a copy of the OpenCV one, never
+ * called).  A motion-only bundle adjustment in the style of ORB-SLAM2's PoseOptimization: robust (Huber) Levenberg-Marquardt
+ * rounds on the reprojection error of BOTH cameras' observations at t2, a chi-square re-classification of the inliers after
+ * every round, and the 6 x 6 information matrix of the pose.  Off by default; with it off every record is byte for byte what
+ * it was.
+ *
+ * Arithmetic, all in double (the numpy twin is tests/_refine_ref.py):
+ *   R1 views.  View L projects with [K1 | 0], K1 = (fx, fy, cx, cy) taken from P1 as the PnP stage takes it (skew and 4th
+ *      column ignored); view R with the full 3 x 4 P2.  LK mode uses both (d = 4 residuals per point), ORB mode view L only
+ *      (d = 2; its t2_right is zeros and is not read); the stage call uses d = 4 when img_right is given, else d = 2.
+ *   R2 state (R, t), Y = R X + t; update (R, t) <- exp(xi) (R, t), xi = (rho, phi), closed-form SO(3) / SE(3) exponentials
+ *      (series form below |phi| < 1e-10).  The start is the PnP record's R, t.
+ *   R3 r_i stacks pi(P_v [Y; 1]) - x_v over the views; with M = P_v[:, :3], h = M Y + p4, u = h0 / h2, w = h1 / h2:
+ *      du/dY = (M0 - u M2) / h2, dw/dY = (M1 - w M2) / h2, dY/dxi = [I | -[Y]x].  A point is projectable when h2 > 1e-6 in
+ *      every view used; a point that is not has weight 0 and is never an inlier.
+ *   R4 c_i = |r_i|^2 / sigma^2; tau = 5.991 (d = 2) or 9.488 (d = 4), the chi-square 95 % points.
+ *   R5 `rounds` rounds of at most `iters` LM iterations.  The active set starts as ALL projectable points, not RANSAC's
+ *      inliers.  Rounds 0 and 1: Huber IRLS on the active set, w_i = 1 if c_i <= tau else sqrt(tau / c_i), cost = sum of c_i
+ *      or 2 sqrt(tau c_i) - tau; later rounds w_i = 1, cost = sum c_i.  After each round every projectable point is
+ *      re-classified: active iff c_i <= tau (re-admission allowed).  The estimate carries over between rounds.
+ *   R6 H = sum w_i J_i^T J_i / sigma^2, g = sum w_i J_i^T r_i / sigma^2; (H + lambda diag H) xi = -g by 6 x 6 Cholesky (fails
+ *      unless every pivot is > 0); lambda = 1e-4 at the start of each round.  Accepted when the round's cost decreases (the
+ *      cost is summed without rounding loss and compared as a (sum, remainder) pair: the decision does not depend on the order
+ *      of the additions) and no active point becomes non-projectable: lambda <- max(lambda / 10, 1e-12), the round ends if |xi| < 1e-10.  Rejected
+ *      otherwise or when the factorisation fails: lambda <- 10 lambda, the round ends if lambda > 1e10.  A rejected step
+ *      counts as an iteration.
+ *   R7 after the last re-classification info = sum over the active points of J_i^T J_i / sigma^2 at the final pose.  The
+ *      refined pose replaces the PnP pose iff the active count >= min_inliers, info is positive definite (its Cholesky
+ *      factorisation succeeds) and every output is finite: status SVO_REFINE_APPLIED.  Otherwise SVO_REFINE_KEPT_PNP and the
+ *      PnP pose stands.  A pair whose solvePnPRansac failed is not refined: SVO_REFINE_SKIPPED.
+ * svo_refine_result: rvec / tvec / R the pose that stands (refined or PnP's), pnp_rvec / pnp_tvec the PnP pose it started
+ *   from, info row-major 6 x 6 in the order of xi (translation first), cost_first / cost_last the cost at the start of round 0
+ *   and at the end of the last round (each in its round's own measure), n_points the points handed in, n_active the active
+ *   count after the last re-classification, iters the LM iterations run (rejected ones included; depends on rounding at
+ *   convergence -- report it, do not compare it), views 1 or 2.
+ *   svo_set_pose_refine : every fused entry point (svo_add_frame, svo_track_batch, svo_track_uploaded(_async),
+ *       svo_streams_step and their svo_ingest_* twins) then runs pose_refine_kernel between solvePnPRansac and the gates, on the
+ *       pose stage's stream: the gates, T_rel_inv and the pose chain see the refined pose; n_inliers, ransac_iters, lm_iters
+ *       and the RANSAC mask stay RANSAC's.  SVO_ERR_ARG (nothing changes): mode not OFF / REPROJ, rounds outside 1..16, iters
+ *       outside 1..100, sigma_px not finite or <= 0, min_inliers < 1.  The first call that enables the stage (or the first
+ *       svo_refine_pose) allocates ONE device block -- (max_batch + 1) records of 496 bytes + (max_batch + 1) x max_keypoints
+ *       flag bytes + 28 bytes x max_keypoints of stage-call scratch (256 pairs x 8192 points: 2.3 MB) -- and waits for the
+ *       device; a context that never enables it allocates nothing.
+ *   svo_get_pose_refine : what is set.  Any pointer may be NULL.
+ *   svo_refine_pose (stage API): the same kernel on a caller's points (n <= max_keypoints), with the CURRENT settings even
+ *       while the mode is OFF.  obj, img_left, img_right and active follow `mem`; res is a HOST struct; the call returns when
+ *       it is filled.  The start pose is (Rodrigues(rvec0), tvec0); pnp_rvec / pnp_tvec return them bit for bit.
+ *   svo_get_refine_result : the record and the active flags of pair `pair` of the most recent fused launch, addressed as
+ *       svo_get_batch_tracks addresses pairs (svo_add_frame: pair 0 is the last step; svo_streams_step: the item index);
+ *       waits for that launch's pose stage.  HOST pointers; *n_out = n_points; SVO_ERR_ARG when the stage was off for that
+ *       launch, pair is out of range or cap < n_points (active may be NULL: cap is ignored).  A capacity that is too small
+ *       leaves *res and active untouched and still sets *n_out, the size to come back with. */
+#define SVO_REFINE_OFF    0
+#define SVO_REFINE_REPROJ 1
+#define SVO_REFINE_APPLIED  0
+#define SVO_REFINE_KEPT_PNP 1
+#define SVO_REFINE_SKIPPED  2
+typedef struct {
+    double rvec[3], tvec[3], R[9];
+    double pnp_rvec[3], pnp_tvec[3];
+    double info[36];
+    double cost_first, cost_last;
+    int32_t n_points, n_active, iters, views, status, _pad;
+} svo_refine_result;
+int svo_set_pose_refine(svo_ctx *ctx, int mode, int rounds, int iters, double sigma_px, int min_inliers);
+int svo_get_pose_refine(const svo_ctx *ctx, int *mode, int *rounds, int *iters, double *sigma_px, int *min_inliers);
+int svo_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left, const svo_pt2f *img_right, int n,
+                    const double P1[12], const double P2[12], const double rvec0[3], const double tvec0[3],
+                    svo_refine_result *res, uint8_t *active, int mem);
+int svo_get_refine_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

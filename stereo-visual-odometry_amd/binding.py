@@ -43,6 +43,19 @@ class PnPResult(C.Structure):
                 ("lm_iters", C.c_int32), ("ok", C.c_int32), ("_pad", C.c_int32)]
 
 
+class RefineResult(C.Structure):
+    """svo_refine_result: the outcome of the pose refinement stage for one pair."""
+    _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("R", C.c_double * 9),
+                ("pnp_rvec", C.c_double * 3), ("pnp_tvec", C.c_double * 3), ("info", C.c_double * 36),
+                ("cost_first", C.c_double), ("cost_last", C.c_double),
+                ("n_points", C.c_int32), ("n_active", C.c_int32), ("iters", C.c_int32), ("views", C.c_int32),
+                ("status", C.c_int32), ("_pad", C.c_int32)]
+
+
+REFINE_OFF, REFINE_REPROJ = 0, 1                                       # svo_set_pose_refine
+REFINE_APPLIED, REFINE_KEPT_PNP, REFINE_SKIPPED = 0, 1, 2              # svo_refine_result.status
+
+
 class StepResult(C.Structure):
     _fields_ = [("ok", C.c_int32), ("fail_stage", C.c_int32), ("n_prev_kps", C.c_int32),
                 ("n_cur_kps", C.c_int32), ("n_tracked", C.c_int32), ("n_inliers", C.c_int32),
@@ -143,6 +156,12 @@ def load_library():
     lib.svo_min_eigen_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.svo_gftt_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.svo_set_pose_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
+    lib.svo_get_pose_refine.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    lib.svo_refine_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(RefineResult), C.c_void_p, C.c_int]
+    lib.svo_get_refine_result.argtypes = [C.c_void_p, C.c_int, C.POINTER(RefineResult), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     _LIB = lib
     return lib
 
@@ -421,6 +440,74 @@ class Context:
                     R=np.array(res.R).reshape(3, 3), n_inliers=res.n_inliers,
                     ransac_iters=res.ransac_iters, best_iter=res.best_iter, lm_iters=res.lm_iters,
                     mask=np.asarray(mask[:n]).copy())
+
+    # ---- robust two-view pose refinement after solvePnPRansac (svo_set_pose_refine) -----------
+    def set_pose_refine(self, mode, rounds=4, iters=10, sigma_px=1.0, min_inliers=6):
+        """"reproj": every fused entry point refines each pair's PnP pose on both cameras' t2 observations; "off": as before."""
+        names = {"off": REFINE_OFF, "none": REFINE_OFF, "reproj": REFINE_REPROJ}
+        m = names[mode] if isinstance(mode, str) and mode in names else mode
+        if isinstance(m, str):
+            raise SvoError(f"pose refinement mode must be 'reproj' or 'off', not {mode!r}")
+        self._check(self.lib.svo_set_pose_refine(self.h, int(m), int(rounds), int(iters), float(sigma_px), int(min_inliers)))
+
+    def pose_refine(self):
+        """(mode name, rounds, iters, sigma_px, min_inliers) as set."""
+        m, r, i, n = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        sg = C.c_double()
+        self._check(self.lib.svo_get_pose_refine(self.h, C.byref(m), C.byref(r), C.byref(i), C.byref(sg), C.byref(n)))
+        return ("reproj" if m.value == REFINE_REPROJ else "off"), r.value, i.value, sg.value, n.value
+
+    @staticmethod
+    def _refine_dict(res, active):
+        return dict(status=res.status, rvec=np.array(res.rvec), tvec=np.array(res.tvec), R=np.array(res.R).reshape(3, 3),
+                    pnp_rvec=np.array(res.pnp_rvec), pnp_tvec=np.array(res.pnp_tvec), info=np.array(res.info).reshape(6, 6),
+                    cost_first=res.cost_first, cost_last=res.cost_last, n_points=res.n_points, n_active=res.n_active,
+                    iters=res.iters, views=res.views, active=active)
+
+    def refine_pose(self, obj, img_left, img_right, P1, P2, rvec0, tvec0):
+        """svo_refine_pose: the refinement stage on a caller's points (numpy arrays, or cuda tensors) with the current settings;
+        img_right None: one view."""
+        P1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        P2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        r0 = np.ascontiguousarray(rvec0, np.float64).reshape(3)
+        t0 = np.ascontiguousarray(tvec0, np.float64).reshape(3)
+        if isinstance(obj, np.ndarray):
+            obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
+            img_left = np.ascontiguousarray(img_left, np.float32).reshape(-1, 2)
+            if img_right is not None:
+                img_right = np.ascontiguousarray(img_right, np.float32).reshape(-1, 2)
+            act = np.zeros(max(obj.shape[0], 1), np.uint8)
+        else:
+            import torch
+            for name, t, cols in (("obj", obj, 3), ("img_left", img_left, 2), ("img_right", img_right, 2)):
+                if t is None:
+                    continue
+                if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols and t.is_contiguous()
+                        and t.device == obj.device and t.shape[0] == obj.shape[0]):
+                    raise SvoError(f"refine_pose: {name} must be a contiguous float32 tensor of shape (n, {cols}) on the device of obj")
+            act = torch.zeros(max(obj.shape[0], 1), dtype=torch.uint8, device=obj.device)
+            self._order_in(act)
+        n = obj.shape[0]
+        if img_left.shape[0] != n or (img_right is not None and img_right.shape[0] != n):
+            raise SvoError("refine_pose: obj, img_left and img_right must have the same number of points")
+        res = RefineResult()
+        po, mem = _ptr(obj)
+        self._check(self.lib.svo_refine_pose(self.h, po, _ptr(img_left)[0], _ptr(img_right)[0], n, C.c_void_p(P1.ctypes.data),
+                                             C.c_void_p(P2.ctypes.data), C.c_void_p(r0.ctypes.data), C.c_void_p(t0.ctypes.data),
+                                             C.byref(res), _ptr(act)[0], mem))
+        if mem == MEM_DEVICE:
+            self._order_out(act)
+            act = act.cpu().numpy()
+        return self._refine_dict(res, np.asarray(act[:n]).copy())
+
+    def refine_result(self, pair=0, cap=None):
+        """svo_get_refine_result: the record and the active flags of pair `pair` of the most recent fused launch."""
+        res = RefineResult()
+        cap = int(self.cfg.max_keypoints) if cap is None else int(cap)      # a pair never has more points
+        act = np.zeros(max(cap, 1), np.uint8)
+        n = C.c_int(0)
+        self._check(self.lib.svo_get_refine_result(self.h, int(pair), C.byref(res), C.c_void_p(act.ctypes.data), cap, C.byref(n)))
+        return self._refine_dict(res, act[:n.value].copy())
 
     # ---- ORB path ---------------------------------------------------------------------------
     def orb_extract(self, img, cap=None):

@@ -96,10 +96,7 @@ __global__ __launch_bounds__(64) void triangulate_kernel(TriArgs a)
 //
 // Exactness: hypotheses, counts, winner, stop and mask are bit-identical to the oracle (same
 // expressions, IEEE f64); only the LM sums are associated differently (observed pose error <= 1e-9).
-struct PnpRecord {                 // device-side record of one solve
-    double rvec[3], tvec[3], R[9];
-    int n_inliers, ransac_iters, best_iter, lm_iters, ok, n;
-};
+// (struct PnpRecord, the device-side record of one solve, is in svo_kernels.h: the refinement stage reads and rewrites it)
 
 constexpr int kHypBlock = 64;                  // hypotheses per EPnP workgroup (one per lane)
 constexpr int kPhaseHyps = 512;                // capacity of a phase (hypotheses, counts, subsets, hand-over records per item)

@@ -31,7 +31,7 @@ static inline void mark(svo_ctx *ctx, const char *name) { timing_mark(ctx, name)
 
 static const char *kTMatch = "orb_match";
 static const char *kT0 = "start", *kTPyr = "pyramid", *kTFast = "fast", *kTLk = "lk", *kTCompact = "compact",
-                  *kTTri = "triangulate", *kTPnp = "pnp", *kTFin = "finalize";
+                  *kTTri = "triangulate", *kTPnp = "pnp", *kTRefine = "refine", *kTFin = "finalize";
 
 // Builds pyramids of `n_new` frames into frame slots [f0, f0+n_new) and runs FAST on their left
 // images.  L/R: device pointers to the first new frame.
@@ -296,6 +296,12 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
         launch_triangulate_batch(ctx, n_pairs, ctx->cfg.max_keypoints, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, nullptr, bs);
     launch_pnp_batch(ctx, n_pairs, ctx->cmp[3], ctx->m_out, 0, bs);
     if (!side) mark(ctx, kTPnp);
+    // svo_set_pose_refine: robust two-view refinement of every pair's PnP record in place, before the gates read it
+    ctx->refine_last_pairs = ctx->refine_mode != SVO_REFINE_OFF ? n_pairs : 0;
+    if (ctx->refine_last_pairs) {
+        launch_refine_batch(ctx, n_pairs, bs);
+        if (!side) mark(ctx, kTRefine);
+    }
     const int *ovf = ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->kp_n_snap + 2 * n_pairs : nullptr;
     if (ss) {
         // gates per pair, pose_s = pose_s * T_rel_inv per stream (no chain along the launch), init records

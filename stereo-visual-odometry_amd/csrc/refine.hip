@@ -1,0 +1,511 @@
+// refine.hip -- robust two-view pose refinement after solvePnPRansac for gfx950: what the reference's
+// Tracking::G2O_EstimatePose_PnP (src/tracking.cpp:384-426) was prepared to be and never became -- a motion-only bundle
+// adjustment in the style of ORB-SLAM2's PoseOptimization.  The arithmetic (rules R1-R7) is stated in include/svo_abi.h and
+// DESIGN.md section 5e; tests/_refine_ref.py is its numpy twin, and the expressions below keep its order of operations.
+//
+// pose_refine_kernel: ONE workgroup of four waves per pair.  Lanes stride the pair's points; every lane keeps 21 + 6 + 1
+// double partial sums (upper triangle of H, g, active count) and the cost as a pair; a wave reduction (refine_wave_allsum) and
+// a fixed-order sum of the four wave totals through LDS give EVERY thread the same numbers, so the 6 x 6 Cholesky solve, the SE(3) update and all the
+// accept / reject / round decisions are computed redundantly in registers and the control flow is workgroup-uniform: three
+// barriers per evaluation, none per solve.  The stage is a chain of about rounds x iters dependent evaluate-and-solve steps of
+// a few hundred kFLOP each: latency, not arithmetic, so a pair gets the four SIMDs of one CU and no more.
+// A point's active flag lives in device memory and is only ever touched by the lane that strides over it.
+#include <cmath>
+#include <cstring>
+#include "svo_ctx.h"
+
+namespace svo {
+
+constexpr int kRefineThreads = 256;
+constexpr int kRefAcc = 31;                    // cost, H (21, row-major upper triangle), g (6), active count, cost tail, bad count
+constexpr int kRefCount = 28, kRefCostLo = 29, kRefBad = 30;
+constexpr double kRefineMinDepth = 1e-6;
+
+struct RefineArgs {
+    const float *X3; const float2 *xl, *xr; int64_t stride;      // points of item b at + b * stride (xr: two-view launches only)
+    int n_fixed, cap;                                            // stage call: the point count; points per item at most
+    double ML[9], MR[9], p4R[3];                                 // view L: [K1 | 0]; view R: P2 = [MR | p4R]
+    int rounds, iters, min_inliers; double sigma;
+    PnpRecord *pnp;                                              // fused: the pairs' PnP records (start pose; rewritten when R7 says so)
+    double rvec0[3], tvec0[3];                                   // stage call (pnp null): the start pose
+    svo_refine_result *res; uint8_t *flags; int64_t flag_stride; // per item
+};
+
+__device__ inline double refine_wave_allsum(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// The cost of a round is carried as an unevaluated pair (s, e): TwoSum keeps what every addition rounds away.  "The cost
+// decreases" (R6) is decided on the pair, so the decision does not depend on the order the lanes add in (a plain sum of ~1000
+// terms carries ~1e-13 of order-dependent noise).  The terms' own rounding -- u - x cancels at ~1e2 px -- remains.
+__device__ inline void refine_dd_add(double &s, double &e, double bs, double be)
+{
+    const double t = s + bs, bb = t - s;
+    const double err = (s - (t - bb)) + (bs - bb);
+    s = t;
+    e = (e + be) + err;
+}
+
+__device__ inline void refine_mm3(const double A[9], const double B[9], double C[9])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = (A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j]) + A[i * 3 + 2] * B[6 + j];
+}
+__device__ inline void refine_mv3(const double A[9], const double v[3], double o[3])
+{
+    for (int i = 0; i < 3; i++) o[i] = (A[i * 3] * v[0] + A[i * 3 + 1] * v[1]) + A[i * 3 + 2] * v[2];
+}
+
+// exp(xi) of SE(3), xi = (rho, phi): E = exp([phi]x), Vr = V(phi) rho (R2)
+__device__ inline void refine_se3_exp(const double xi[6], double E[9], double Vr[3])
+{
+    const double *phi = xi + 3;
+    const double th2 = (phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2];
+    const double th = sqrt(th2);
+    double A = 1.0, B = 0.5, C = 1.0 / 6.0;
+    if (!(th < 1e-10)) {
+        const double sh = sin(0.5 * th), s = sin(th);
+        A = s / th;
+        B = 2.0 * sh * sh / th2;
+        C = (th - s) / (th2 * th);
+    }
+    const double K[9] = {0.0, -phi[2], phi[1], phi[2], 0.0, -phi[0], -phi[1], phi[0], 0.0};
+    double K2[9], V[9];
+    refine_mm3(K, K, K2);
+    for (int k = 0; k < 9; k++) {
+        const double I = (k % 4 == 0) ? 1.0 : 0.0;
+        E[k] = (I + A * K[k]) + B * K2[k];
+        V[k] = (I + B * K[k]) + C * K2[k];
+    }
+    refine_mv3(V, xi, Vr);
+}
+
+// cv::Rodrigues vector -> matrix
+__device__ inline void refine_rodrigues(const double r[3], double R[9])
+{
+    const double th = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    if (th < 2.220446049250313e-16) {
+        for (int k = 0; k < 9; k++) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+        return;
+    }
+    const double k0 = r[0] / th, k1 = r[1] / th, k2 = r[2] / th, kk[3] = {k0, k1, k2};
+    const double c = cos(th), s = sin(th), c1 = 1.0 - c;
+    const double Kx[9] = {0.0, -k2, k1, k2, 0.0, -k0, -k1, k0, 0.0};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R[i * 3 + j] = (c * (i == j ? 1.0 : 0.0) + c1 * (kk[i] * kk[j])) + s * Kx[i * 3 + j];
+}
+
+// rotation matrix -> rotation vector
+__device__ inline void refine_so3_log(const double R[9], double r[3])
+{
+    const double v[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+    const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+    const double th = atan2(s, c);
+    if (s >= 1e-5 || c > 0) {
+        const double f = s >= 1e-10 ? th / s : 1.0;
+        for (int i = 0; i < 3; i++) r[i] = v[i] * f;
+        return;
+    }
+    // near pi: the axis from the diagonal, signs from the off-diagonal sums (cv::Rodrigues)
+    double ax[3];
+    for (int i = 0; i < 3; i++) { const double q = (R[i * 4] + 1.0) * 0.5; ax[i] = sqrt(q > 0.0 ? q : 0.0); }
+    if (R[1] < 0) ax[1] = -ax[1];
+    if (R[2] < 0) ax[2] = -ax[2];
+    if (fabs(ax[0]) < fabs(ax[1]) && fabs(ax[0]) < fabs(ax[2]) && (R[5] > 0) != (ax[1] * ax[2] > 0)) ax[2] = -ax[2];
+    const double f = th / sqrt((ax[0] * ax[0] + ax[1] * ax[1]) + ax[2] * ax[2]);
+    for (int i = 0; i < 3; i++) r[i] = ax[i] * f;
+}
+
+// 6 x 6 Cholesky solve A x = b, row by row; fails unless every pivot is > 0 (R6, R7).  Registers only: every thread of the
+// workgroup solves the same system.
+__device__ inline bool refine_chol6(const double (&A)[36], const double (&b)[6], double (&x)[6])
+{
+    double L[21];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+            double s = A[i * 6 + j];
+#pragma unroll
+            for (int k = 0; k < j; k++) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+            if (i == j) {
+                ok = ok && s > 0.0;
+                L[i * (i + 1) / 2 + i] = sqrt(s);
+            } else {
+                L[i * (i + 1) / 2 + j] = s / L[j * (j + 1) / 2 + j];
+            }
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) s -= L[i * (i + 1) / 2 + k] * y[k];
+        y[i] = s / L[i * (i + 1) / 2 + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) s -= L[k * (k + 1) / 2 + i] * x[k];
+        x[i] = s / L[i * (i + 1) / 2 + i];
+    }
+    return ok;
+}
+
+// One evaluation of a pair's points at (R, t): residuals, c_i, Jacobians (R3, R4), the sums of R5 / R6 over the active set.
+//   mode 0: the active set becomes every projectable point (the start of round 0);
+//   mode 1: every point is re-classified first -- active iff projectable and c_i <= tau;
+//   mode 2: a trial step -- the flags stand; an active point that is no longer projectable is counted (the step is then
+//           rejected).
+// S (LDS, kRefAcc doubles, complete for every thread when the call returns) receives cost | sum w J^T J (upper triangle) |
+// sum w J^T r | the active count | the cost's tail | the count of active points that are not projectable -- H and g NOT yet
+// divided by sigma^2.  The totals live in LDS, not in registers: two sets of 31 doubles per thread (the accepted pose's and the
+// trial's) on top of the 31 partial sums and the Jacobian rows spilled the two-view kernel to scratch.
+enum { kRefInit = 0, kRefReclass = 1, kRefTrial = 2 };
+template <int V>
+__device__ void refine_pass(const RefineArgs &a, const float *X3, const float2 *xl, const float2 *xr, uint8_t *flags, int n,
+                            const double (&R)[9], const double (&t)[3], int mode, bool robust, double tau, double s2, double *red,
+                            double *S)
+{
+    double acc[kRefAcc];
+    for (int k = 0; k < kRefAcc; k++) acc[k] = 0.0;
+    for (int i = threadIdx.x; i < n; i += kRefineThreads) {
+        const double X = (double)X3[3 * i], Yp = (double)X3[3 * i + 1], Z = (double)X3[3 * i + 2];
+        double Y[3];
+        for (int k = 0; k < 3; k++) Y[k] = ((X * R[k * 3] + Yp * R[k * 3 + 1]) + Z * R[k * 3 + 2]) + t[k];
+        double r[2 * V], J[2 * V][6];
+        bool proj = true;
+#pragma unroll
+        for (int v = 0; v < V; v++) {
+            const double *M = v == 0 ? a.ML : a.MR;
+            const float2 o = v == 0 ? xl[i] : xr[i];
+            double h[3];
+            for (int k = 0; k < 3; k++) {
+                h[k] = (Y[0] * M[k * 3] + Y[1] * M[k * 3 + 1]) + Y[2] * M[k * 3 + 2];
+                if (v == 1) h[k] = h[k] + a.p4R[k];
+            }
+            const bool ok = h[2] > kRefineMinDepth;
+            proj = proj && ok;
+            const double h2 = ok ? h[2] : 1.0;
+            const double u = h[0] / h2, w = h[1] / h2;
+            r[2 * v] = u - (double)o.x;
+            r[2 * v + 1] = w - (double)o.y;
+            double da[3], db[3];
+            for (int k = 0; k < 3; k++) { da[k] = (M[k] - u * M[6 + k]) / h2; db[k] = (M[3 + k] - w * M[6 + k]) / h2; }
+            for (int k = 0; k < 3; k++) { J[2 * v][k] = da[k]; J[2 * v + 1][k] = db[k]; }
+            J[2 * v][3] = Y[1] * da[2] - Y[2] * da[1];     J[2 * v + 1][3] = Y[1] * db[2] - Y[2] * db[1];      // -a^T [Y]x = (Y x a)^T
+            J[2 * v][4] = Y[2] * da[0] - Y[0] * da[2];     J[2 * v + 1][4] = Y[2] * db[0] - Y[0] * db[2];
+            J[2 * v][5] = Y[0] * da[1] - Y[1] * da[0];     J[2 * v + 1][5] = Y[0] * db[1] - Y[1] * db[0];
+        }
+        double c = 0.0;
+        if (proj) {
+            c = r[0] * r[0];
+#pragma unroll
+            for (int k = 1; k < 2 * V; k++) c += r[k] * r[k];
+            c = c / s2;
+        }
+        bool act;
+        if (mode == kRefInit) act = proj;
+        else if (mode == kRefReclass) act = proj && c <= tau;
+        else act = flags[i] != 0;
+        if (mode != kRefTrial) flags[i] = act ? 1 : 0;
+        if (!act) continue;
+        if (!proj) { acc[kRefBad] += 1.0; continue; }
+        double w = 1.0, rho = c;
+        if (robust && c > tau) { w = sqrt(tau / c); rho = 2.0 * sqrt(tau * c) - tau; }
+        refine_dd_add(acc[0], acc[kRefCostLo], rho, 0.0);
+        acc[kRefCount] += 1.0;
+        int q = 1;
+#pragma unroll
+        for (int p = 0; p < 6; p++)
+#pragma unroll
+            for (int s = p; s < 6; s++) {
+                double jj = J[0][p] * J[0][s];
+#pragma unroll
+                for (int k = 1; k < 2 * V; k++) jj += J[k][p] * J[k][s];
+                acc[q++] += w * jj;
+            }
+#pragma unroll
+        for (int p = 0; p < 6; p++) {
+            double jr = J[0][p] * r[0];
+#pragma unroll
+            for (int k = 1; k < 2 * V; k++) jr += J[k][p] * r[k];
+            acc[q++] += w * jr;
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();                                        // `red` and S may still be read from the previous pass
+    for (int k = 1; k < kRefAcc; k++) {
+        if (k == kRefCostLo) continue;
+        const double ws = refine_wave_allsum(acc[k]);
+        if (lane == 0) red[wave * kRefAcc + k] = ws;
+    }
+    {
+        // the cost pair: the same butterfly with pair additions (TwoSum is symmetric, so every lane ends with the same pair)
+        double cs = acc[0], ce = acc[kRefCostLo];
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const double os = __shfl_xor(cs, m, 64), oe = __shfl_xor(ce, m, 64);
+            refine_dd_add(cs, ce, os, oe);
+        }
+        if (lane == 0) { red[wave * kRefAcc] = cs; red[wave * kRefAcc + kRefCostLo] = ce; }
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k >= 1 && k < kRefAcc && k != kRefCostLo) S[k] = ((red[k] + red[kRefAcc + k]) + red[2 * kRefAcc + k]) + red[3 * kRefAcc + k];
+    if (k == 0) {
+        double cs = red[0], ce = red[kRefCostLo];
+        for (int w = 1; w < 4; w++) refine_dd_add(cs, ce, red[w * kRefAcc], red[w * kRefAcc + kRefCostLo]);
+        const double hi = cs + ce;                          // normalised: hi the rounded sum, lo what is left
+        S[0] = hi;
+        S[kRefCostLo] = ce - (hi - cs);
+    }
+    __syncthreads();
+}
+
+__device__ inline bool refine_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }    // false for NaN and +-inf
+
+template <int V>
+__global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void pose_refine_kernel(RefineArgs a)
+{
+    __shared__ double red[4 * kRefAcc];
+    __shared__ double tot[2][kRefAcc];                      // the sums at the accepted pose and at the trial pose
+    const int tid = threadIdx.x, b = blockIdx.x;
+    svo_refine_result *res = a.res + b;
+    uint8_t *flags = a.flags + (int64_t)b * a.flag_stride;
+    const float *X3 = a.X3 + (int64_t)b * a.stride * 3;
+    const float2 *xl = a.xl + (int64_t)b * a.stride;
+    const float2 *xr = V == 2 ? a.xr + (int64_t)b * a.stride : nullptr;
+    double R[9], t[3], rv0[3];
+    int n = a.n_fixed;
+    bool skip = false;
+    if (a.pnp) {
+        const PnpRecord &q = a.pnp[b];
+        for (int i = 0; i < 9; i++) R[i] = q.R[i];
+        for (int i = 0; i < 3; i++) { t[i] = q.tvec[i]; rv0[i] = q.rvec[i]; }
+        n = q.n;
+        skip = q.ok == 0;                                   // solvePnPRansac failed (no model, or fewer points than one needs)
+    } else {
+        for (int i = 0; i < 3; i++) { t[i] = a.tvec0[i]; rv0[i] = a.rvec0[i]; }
+        refine_rodrigues(rv0, R);
+    }
+    n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+    if (skip) {
+        for (int i = tid; i < n; i += kRefineThreads) flags[i] = 0;
+        if (tid == 0) {
+            for (int i = 0; i < 3; i++) { res->rvec[i] = rv0[i]; res->tvec[i] = t[i]; res->pnp_rvec[i] = rv0[i]; res->pnp_tvec[i] = t[i]; }
+            for (int i = 0; i < 9; i++) res->R[i] = R[i];
+            for (int i = 0; i < 36; i++) res->info[i] = 0.0;
+            res->cost_first = 0.0; res->cost_last = 0.0;
+            res->n_points = n; res->n_active = 0; res->iters = 0; res->views = V; res->status = SVO_REFINE_SKIPPED; res->_pad = 0;
+        }
+        return;
+    }
+    const double tau = V == 2 ? 9.488 : 5.991;
+    const double s2 = a.sigma * a.sigma, is2 = 1.0 / s2;
+    double *S = tot[0], *Sn = tot[1];
+    int total = 0;
+    double cost_first = 0.0, cost = 0.0, cost_lo = 0.0;
+    for (int rd = 0; rd < a.rounds; rd++) {
+        const bool robust = rd < 2;
+        refine_pass<V>(a, X3, xl, xr, flags, n, R, t, rd == 0 ? kRefInit : kRefReclass, robust, tau, s2, red, S);
+        cost = S[0]; cost_lo = S[kRefCostLo];
+        if (rd == 0) cost_first = cost;
+        double lam = 1e-4;
+        for (int it = 0; it < a.iters; it++) {
+            total++;
+            double A[36], g[6], xi[6];
+            {
+                int q = 1;
+                for (int p = 0; p < 6; p++)
+                    for (int s = p; s < 6; s++) { const double h = S[q++] * is2; A[p * 6 + s] = h; A[s * 6 + p] = h; }
+                for (int p = 0; p < 6; p++) { g[p] = -(S[22 + p] * is2); A[p * 6 + p] = A[p * 6 + p] + lam * A[p * 6 + p]; }
+            }
+            bool accepted = false;
+            double Rn[9], tn[3];
+            if (refine_chol6(A, g, xi)) {
+                double E[9], Vr[3], Et[3];
+                refine_se3_exp(xi, E, Vr);
+                refine_mm3(E, R, Rn);
+                refine_mv3(E, t, Et);
+                for (int i = 0; i < 3; i++) tn[i] = Et[i] + Vr[i];
+                refine_pass<V>(a, X3, xl, xr, flags, n, Rn, tn, kRefTrial, robust, tau, s2, red, Sn);
+                accepted = Sn[kRefBad] == 0.0 && (Sn[0] < cost || (Sn[0] == cost && Sn[kRefCostLo] < cost_lo));
+            }
+            if (accepted) {
+                for (int i = 0; i < 9; i++) R[i] = Rn[i];
+                for (int i = 0; i < 3; i++) t[i] = tn[i];
+                { double *sw = S; S = Sn; Sn = sw; }         // the trial's sums are the accepted pose's now
+                cost = S[0]; cost_lo = S[kRefCostLo];
+                lam = lam / 10.0 > 1e-12 ? lam / 10.0 : 1e-12;
+                double nx = xi[0] * xi[0];
+                for (int i = 1; i < 6; i++) nx += xi[i] * xi[i];
+                if (sqrt(nx) < 1e-10) break;
+            } else {
+                lam *= 10.0;
+                if (lam > 1e10) break;
+            }
+        }
+    }
+    // R7: the last re-classification, the information matrix over the active set, the outcome
+    refine_pass<V>(a, X3, xl, xr, flags, n, R, t, kRefReclass, false, tau, s2, red, S);
+    double info[36], zero[6] = {0, 0, 0, 0, 0, 0}, dummy[6], rv[3];
+    {
+        int q = 1;
+        for (int p = 0; p < 6; p++)
+            for (int s = p; s < 6; s++) { const double h = S[q++] / s2; info[p * 6 + s] = h; info[s * 6 + p] = h; }
+    }
+    const int n_active = (int)S[kRefCount];
+    refine_so3_log(R, rv);
+    bool fin = refine_finite(cost_first) && refine_finite(cost);
+    for (int i = 0; i < 9; i++) fin = fin && refine_finite(R[i]);
+    for (int i = 0; i < 3; i++) fin = fin && refine_finite(t[i]) && refine_finite(rv[i]);
+    for (int i = 0; i < 36; i++) fin = fin && refine_finite(info[i]);
+    const bool pd = refine_chol6(info, zero, dummy);
+    const bool applied = n_active >= a.min_inliers && pd && fin;
+    if (tid == 0) {
+        // the start pose again, from where it came (kept in registers through the rounds it cost the two-view kernel its second wave per SIMD)
+        double R0[9], t0[3];
+        if (a.pnp) {
+            const PnpRecord &q = a.pnp[b];
+            for (int i = 0; i < 9; i++) R0[i] = q.R[i];
+            for (int i = 0; i < 3; i++) { t0[i] = q.tvec[i]; rv0[i] = q.rvec[i]; }
+        } else {
+            for (int i = 0; i < 3; i++) { t0[i] = a.tvec0[i]; rv0[i] = a.rvec0[i]; }
+            refine_rodrigues(rv0, R0);
+        }
+        for (int i = 0; i < 3; i++) {
+            res->pnp_rvec[i] = rv0[i]; res->pnp_tvec[i] = t0[i];
+            res->rvec[i] = applied ? rv[i] : rv0[i]; res->tvec[i] = applied ? t[i] : t0[i];
+        }
+        for (int i = 0; i < 9; i++) res->R[i] = applied ? R[i] : R0[i];
+        for (int i = 0; i < 36; i++) res->info[i] = info[i];
+        res->cost_first = cost_first; res->cost_last = cost;
+        res->n_points = n; res->n_active = n_active; res->iters = total; res->views = V;
+        res->status = applied ? SVO_REFINE_APPLIED : SVO_REFINE_KEPT_PNP; res->_pad = 0;
+        if (applied && a.pnp) {
+            // the gates, T_rel_inv and the chain (finalize_*_kernel) read the pair's PnP record: they see the refined pose
+            PnpRecord &q = a.pnp[b];
+            for (int i = 0; i < 3; i++) { q.rvec[i] = rv[i]; q.tvec[i] = t[i]; }
+            for (int i = 0; i < 9; i++) q.R[i] = R[i];
+        }
+    }
+}
+
+// ---- the stage's device block: [records x (B + 1)][flags x (B + 1) x cap][stage-call X, xl, xr x cap]; item B is the stage call's
+static size_t ral(size_t v) { return (v + 255) / 256 * 256; }
+static size_t roff_flags(const svo_config &c) { return ral(sizeof(svo_refine_result) * ((size_t)c.max_batch + 1)); }
+static size_t roff_X(const svo_config &c) { return ral(roff_flags(c) + ((size_t)c.max_batch + 1) * (size_t)c.max_keypoints); }
+static size_t roff_xl(const svo_config &c) { return ral(roff_X(c) + sizeof(float) * 3 * (size_t)c.max_keypoints); }
+static size_t roff_xr(const svo_config &c) { return ral(roff_xl(c) + sizeof(float2) * (size_t)c.max_keypoints); }
+static size_t roff_end(const svo_config &c) { return ral(roff_xr(c) + sizeof(float2) * (size_t)c.max_keypoints); }
+
+int refine_alloc(svo_ctx *ctx)
+{
+    if (ctx->refine_buf) return SVO_OK;
+    SVO_HIP(hipSetDevice(ctx->device));
+    uint8_t *p = nullptr;
+    SVO_HIP(hipMalloc((void **)&p, roff_end(ctx->cfg)));
+    if (hipMemset(p, 0, roff_end(ctx->cfg)) != hipSuccess) { (void)hipFree(p); ctx->err = "hipMemset of the refinement block failed"; return SVO_ERR_HIP; }
+    ctx->refine_buf = p;
+    return SVO_OK;
+}
+
+static void refine_fill(const svo_ctx *ctx, RefineArgs &a, const double P1[12], const double P2[12])
+{
+    // K1 = (fx, fy, cx, cy) of P1 as the PnP stage takes it; P2 whole
+    const double ML[9] = {P1[0], 0.0, P1[2], 0.0, P1[5], P1[6], 0.0, 0.0, 1.0};
+    for (int i = 0; i < 9; i++) a.ML[i] = ML[i];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) a.MR[i * 3 + j] = P2 ? P2[i * 4 + j] : 0.0;
+        a.p4R[i] = P2 ? P2[i * 4 + 3] : 0.0;
+    }
+    a.rounds = ctx->refine_rounds; a.iters = ctx->refine_iters; a.min_inliers = ctx->refine_min_inliers; a.sigma = ctx->refine_sigma;
+    a.cap = ctx->cfg.max_keypoints;
+    a.res = (svo_refine_result *)ctx->refine_buf;
+    a.flags = ctx->refine_buf + roff_flags(ctx->cfg);
+    a.flag_stride = ctx->cfg.max_keypoints;
+}
+
+void launch_refine_batch(svo_ctx *ctx, int n_pairs, hipStream_t st)
+{
+    RefineArgs a{};
+    refine_fill(ctx, a, ctx->cfg.P1, ctx->cfg.P2);
+    const bool two = ctx->cfg.track_mode == SVO_MODE_LK;       // ORB mode has no t2_right (zeros): view L only
+    a.X3 = ctx->X3; a.xl = ctx->cmp[3]; a.xr = two ? ctx->cmp[2] : nullptr; a.stride = ctx->cfg.max_keypoints;
+    a.pnp = (PnpRecord *)ctx->pnp_ws;
+    if (two) hipLaunchKernelGGL(pose_refine_kernel<2>, dim3(n_pairs), dim3(kRefineThreads), 0, st, a);
+    else hipLaunchKernelGGL(pose_refine_kernel<1>, dim3(n_pairs), dim3(kRefineThreads), 0, st, a);
+}
+
+int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left, const svo_pt2f *img_right, int n, const double P1[12],
+                      const double P2[12], const double rvec0[3], const double tvec0[3], svo_refine_result *res, uint8_t *active, int mem)
+{
+    SVO_ARG(P1 && rvec0 && tvec0 && res, "null pointer");
+    SVO_ARG(img_right == nullptr || P2 != nullptr, "img_right without P2");
+    SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "n exceeds max_keypoints");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
+    SVO_ARG(n == 0 || (obj && img_left), "null pointer");
+    const int rc = refine_alloc(ctx);
+    if (rc) return rc;
+    SVO_HIP(hipSetDevice(ctx->device));
+    const svo_config &c = ctx->cfg;
+    const int B = c.max_batch;
+    const bool two = img_right != nullptr;
+    RefineArgs a{};
+    refine_fill(ctx, a, P1, two ? P2 : nullptr);
+    a.res += B;
+    uint8_t *own_flags = a.flags + (size_t)B * c.max_keypoints;
+    a.flags = own_flags; a.flag_stride = 0; a.stride = 0; a.n_fixed = n; a.pnp = nullptr;
+    for (int i = 0; i < 3; i++) { a.rvec0[i] = rvec0[i]; a.tvec0[i] = tvec0[i]; }
+    if (mem == SVO_MEM_HOST) {
+        float *dX = (float *)(ctx->refine_buf + roff_X(c));
+        float2 *dl = (float2 *)(ctx->refine_buf + roff_xl(c)), *dr = (float2 *)(ctx->refine_buf + roff_xr(c));
+        if (n > 0) {
+            SVO_HIP(hipMemcpyAsync(dX, obj, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            SVO_HIP(hipMemcpyAsync(dl, img_left, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            if (two) SVO_HIP(hipMemcpyAsync(dr, img_right, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        }
+        a.X3 = dX; a.xl = dl; a.xr = two ? dr : nullptr;
+    } else {
+        a.X3 = (const float *)obj; a.xl = (const float2 *)img_left; a.xr = (const float2 *)img_right;
+        if (active) a.flags = active;
+    }
+    if (two) hipLaunchKernelGGL(pose_refine_kernel<2>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(pose_refine_kernel<1>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
+    SVO_HIP(hipGetLastError());
+    svo_refine_result *h = (svo_refine_result *)((char *)ctx->h_pinned + 256);
+    SVO_HIP(hipMemcpyAsync(h, a.res, sizeof(svo_refine_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (mem == SVO_MEM_HOST && active && n > 0) SVO_HIP(hipMemcpyAsync(active, own_flags, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(res, h, sizeof(*res));
+    return SVO_OK;
+}
+
+// the record and the flags of pair `pair` of the last fused launch; the caller has ordered the pose stage before the context's stream
+int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out)
+{
+    const svo_config &c = ctx->cfg;
+    svo_refine_result *h = (svo_refine_result *)((char *)ctx->h_pinned + 256);
+    SVO_HIP(hipMemcpyAsync(h, (const svo_refine_result *)ctx->refine_buf + pair, sizeof(*h), hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    const int n = h->n_points;
+    SVO_ARG(n >= 0 && n <= c.max_keypoints, "corrupt point count");
+    if (n_out) *n_out = n;                                  // also when the capacity is too small: what to size `active` for
+    SVO_ARG(active == nullptr || n <= cap, "flag capacity too small");     // nothing else has been written
+    if (res) memcpy(res, h, sizeof(*res));
+    if (active && n > 0) {
+        SVO_HIP(hipMemcpyAsync(active, ctx->refine_buf + roff_flags(c) + (size_t)pair * c.max_keypoints, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        SVO_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SVO_OK;
+}
+
+}  // namespace svo

@@ -136,6 +136,7 @@ static void free_all(svo_ctx *c)
     if (c->bucket_stage) (void)hipFree(c->bucket_stage);
     if (c->gftt_fused.base) (void)hipFree(c->gftt_fused.base);
     if (c->gftt_stage.base) (void)hipFree(c->gftt_stage.base);
+    if (c->refine_buf) (void)hipFree(c->refine_buf);
     if (c->ev_front) (void)hipEventDestroy(c->ev_front);
     if (c->ev_back) (void)hipEventDestroy(c->ev_back);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -1659,4 +1660,49 @@ extern "C" int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int 
         SVO_HIP(hipStreamSynchronize(ctx->stream));
     }
     return SVO_OK;
+}
+
+// ---- robust two-view pose refinement after solvePnPRansac (refine.hip: pose_refine_kernel) ----------------------------
+extern "C" int svo_set_pose_refine(svo_ctx *ctx, int mode, int rounds, int iters, double sigma_px, int min_inliers)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(mode == SVO_REFINE_OFF || mode == SVO_REFINE_REPROJ, "mode must be SVO_REFINE_OFF or SVO_REFINE_REPROJ");
+    SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
+    SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
+    SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
+    SVO_ARG(min_inliers >= 1, "min_inliers < 1");
+    if (mode != SVO_REFINE_OFF) { const int rc = refine_alloc(ctx); if (rc) return rc; }
+    ctx->refine_mode = mode; ctx->refine_rounds = rounds; ctx->refine_iters = iters;
+    ctx->refine_sigma = sigma_px; ctx->refine_min_inliers = min_inliers;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_pose_refine(const svo_ctx *ctx, int *mode, int *rounds, int *iters, double *sigma_px, int *min_inliers)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (mode) *mode = ctx->refine_mode;
+    if (rounds) *rounds = ctx->refine_rounds;
+    if (iters) *iters = ctx->refine_iters;
+    if (sigma_px) *sigma_px = ctx->refine_sigma;
+    if (min_inliers) *min_inliers = ctx->refine_min_inliers;
+    return SVO_OK;
+}
+
+extern "C" int svo_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left, const svo_pt2f *img_right, int n,
+                               const double P1[12], const double P2[12], const double rvec0[3], const double tvec0[3],
+                               svo_refine_result *res, uint8_t *active, int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return stage_refine_pose(ctx, obj, img_left, img_right, n, P1, P2, rvec0, tvec0, res, active, mem);
+}
+
+extern "C" int svo_get_refine_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->refine_last_pairs > 0 && ctx->refine_buf, "the refinement stage was off for the last launch (svo_set_pose_refine)");
+    SVO_ARG(pair >= 0 && pair < ctx->refine_last_pairs, "pair is not part of the last launch");
+    SVO_ARG(active == nullptr || cap >= 0, "negative capacity");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    return refine_read_result(ctx, pair, res, active, cap, n_out);
 }

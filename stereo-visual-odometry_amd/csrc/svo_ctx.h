@@ -173,6 +173,11 @@ struct svo_ctx {
     int gftt_max_corners = 0;
     double gftt_quality = 0.0, gftt_min_distance = 0.0;
     GfttBuf gftt_fused, gftt_stage;                      // scratch of the fused path (n_img images of the context's size) / of the stage calls
+    // ---- robust pose refinement after solvePnPRansac (svo_set_pose_refine / svo_refine_pose; off and nothing allocated until then)
+    int refine_mode = SVO_REFINE_OFF, refine_rounds = 4, refine_iters = 10, refine_min_inliers = 6;
+    double refine_sigma = 1.0;
+    uint8_t *refine_buf = nullptr;                       // ONE block: records, per-point flags, stage-call scratch (refine.hip)
+    int refine_last_pairs = 0;                           // pairs the stage refined in the most recent fused launch (0: it was off)
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -216,6 +221,12 @@ void launch_triangulate_batch(svo_ctx *ctx, int n_items, int max_pts, const floa
                               const int *n_pts, int n_fixed, const SnapSpec *snap = nullptr, hipStream_t st = nullptr);   // st null: the context's stream
 void launch_snap_counts(svo_ctx *ctx, int n_items, const SnapSpec &snap, hipStream_t st);
 void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n_pts, int n_fixed, hipStream_t st);
+// refine.hip: pose_refine_kernel, one workgroup per pair, on the records solvePnPRansac left in ctx->pnp_ws
+int refine_alloc(svo_ctx *ctx);                          // the stage's device block, on first use (waits for the device)
+void launch_refine_batch(svo_ctx *ctx, int n_pairs, hipStream_t st);
+int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left, const svo_pt2f *img_right, int n, const double P1[12],
+                      const double P2[12], const double rvec0[3], const double tvec0[3], svo_refine_result *res, uint8_t *active, int mem);
+int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out);
 // orb.hip
 int orb_alloc(svo_ctx *ctx);
 void orb_free(svo_ctx *ctx);

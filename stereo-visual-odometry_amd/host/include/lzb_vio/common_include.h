@@ -23,6 +23,11 @@ struct Point2f {
     Point2f() {}
     Point2f(float x_, float y_) : x(x_), y(y_) {}
 };
+struct Point3f {
+    float x = 0.f, y = 0.f, z = 0.f;
+    Point3f() {}
+    Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
+};
 
 struct Point2i {
     int x = 0, y = 0;

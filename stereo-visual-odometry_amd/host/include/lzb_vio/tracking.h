@@ -62,6 +62,23 @@ public:
     // quality level that is not a finite number > 0, a negative or non-finite distance, and gftt together with ORB mode, the
     // FAST buckets or fast_keep_strongest are refused (false + a message that names the key).  Applied right after svo_create.
     static bool ReadLkDetector(int *detector, int *max_corners, double *quality_level, double *min_distance, std::string *err);
+    // additive YAML keys pose_refine: none | reproj (absent: none), pose_refine_rounds (4), pose_refine_iters (10),
+    // pose_refine_sigma (1.0 px) and pose_refine_min_inliers (6): the robust two-view pose refinement after solvePnPRansac
+    // (svo_set_pose_refine, include/svo_abi.h).  ReadPoseRefine reads and checks them for the loaded YAML: an unknown mode,
+    // rounds outside 1..16, iterations outside 1..100, a sigma that is not a finite number > 0, min_inliers < 1 -> false, *err
+    // names the key.  The values are checked even while the mode is none.
+    static bool ReadPoseRefine(int *mode, int *rounds, int *iters, double *sigma_px, int *min_inliers, std::string *err);
+    // The stage the reference declares as Tracking::G2O_EstimatePose_PnP (include/lzb_vio/tracking.h:82; its body there is a copy
+    // of the OpenCV one and it is never called): here it does what its name says, through svo_refine_pose -- a robust motion-only
+    // bundle adjustment of (rotation, translation) on the points' t2 observations in the left and, when pointsRight_t2 is not null,
+    // the right camera, with this object's pose_refine_* settings.  rotation (a rotation VECTOR) and translation go in as the
+    // start and come out refined; false: the start pose stands (too few inliers, degenerate, or no device).  result, when not
+    // null, receives the stage's record (information matrix, active count, status).  NOTE: nothing in host/ calls it -- the fused
+    // path refines inside svo_add_frame / svo_track_* -- and no test exercises it; what it wraps, svo_refine_pose, is held against
+    // the numpy reference by tests/test_gpu_refine.py.
+    bool G2O_EstimatePose_PnP(const double projMatrl[12], const double projMatrr[12], const std::vector<cv::Point2f> &pointsLeft_t2,
+                              const std::vector<cv::Point2f> *pointsRight_t2, const std::vector<cv::Point3f> &points3D_t0,
+                              double rotation[3], double translation[3], svo_refine_result *result = nullptr);
     bool Ingest() const { return image_scale_ < 1.0; }
     double ImageScale() const { return image_scale_; }
     int ImageInterp() const { return image_interp_; }
@@ -111,6 +128,8 @@ private:
     int bucket_w_ = 0, bucket_h_ = 0, bucket_keep_ = 0;      // additive YAML keys fast_bucket_width / _height / _keep (keep 0 = off)
     int lk_detector_ = SVO_DETECTOR_FAST, gftt_num_ = 500;    // additive YAML keys lk_detector: fast (default) | gftt, num_features
     double gftt_quality_ = 0.01, gftt_min_distance_ = 20.0;  // additive YAML keys gftt_quality_level, gftt_min_distance
+    int pose_refine_ = SVO_REFINE_OFF, pose_refine_rounds_ = 4, pose_refine_iters_ = 10, pose_refine_min_inliers_ = 6;   // pose_refine*
+    double pose_refine_sigma_ = 1.0;
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128
     double image_scale_ = 1.0;                               // additive YAML key image_scale (1 = no ingest stage)
     int image_interp_ = SVO_INTERP_NEAREST;                  // additive YAML key image_interp: nearest (default) | linear

@@ -158,6 +158,9 @@ int RunInterleaved(const std::vector<std::string> &yamls, const std::vector<std:
         // ... and lk_detector / gftt_quality_level / gftt_min_distance
         int det, num; double q, md;
         if (!Tracking::ReadLkDetector(&det, &num, &q, &md, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
+        // ... and pose_refine / pose_refine_rounds / _iters / _sigma / _min_inliers
+        int rmode, rrounds, riters, rmin; double rsigma;
+        if (!Tracking::ReadPoseRefine(&rmode, &rrounds, &riters, &rsigma, &rmin, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
     }
     for (int s = 0; s < n; s++) {
         cv::Mat l, r;

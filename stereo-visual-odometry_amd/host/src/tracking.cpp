@@ -71,6 +71,48 @@ bool Tracking::ReadLkDetector(int *detector, int *max_corners, double *quality_l
     return true;
 }
 
+bool Tracking::ReadPoseRefine(int *mode, int *rounds, int *iters, double *sigma_px, int *min_inliers, std::string *err)
+{
+    *mode = SVO_REFINE_OFF; *rounds = 4; *iters = 10; *sigma_px = 1.0; *min_inliers = 6;
+    const std::string m = Config::Has("pose_refine") ? Config::Get<std::string>("pose_refine") : std::string("none");
+    // (a value that does not parse as a number reads as 0)
+    const int r = Config::Has("pose_refine_rounds") ? Config::Get<int>("pose_refine_rounds") : 4;
+    const int it = Config::Has("pose_refine_iters") ? Config::Get<int>("pose_refine_iters") : 10;
+    const double sg = Config::Has("pose_refine_sigma") ? Config::Get<double>("pose_refine_sigma") : 1.0;
+    const int mi = Config::Has("pose_refine_min_inliers") ? Config::Get<int>("pose_refine_min_inliers") : 6;
+    char msg[240] = "";
+    if (m != "none" && m != "reproj") snprintf(msg, sizeof(msg), "pose_refine: '%s' is neither 'none' nor 'reproj'", m.c_str());
+    else if (r < 1 || r > 16) snprintf(msg, sizeof(msg), "pose_refine_rounds: %d is outside 1..16", r);
+    else if (it < 1 || it > 100) snprintf(msg, sizeof(msg), "pose_refine_iters: %d is outside 1..100", it);
+    else if (!(std::isfinite(sg) && sg > 0.0)) snprintf(msg, sizeof(msg), "pose_refine_sigma: %g is not a finite number > 0", sg);
+    else if (mi < 1) snprintf(msg, sizeof(msg), "pose_refine_min_inliers: %d is < 1", mi);
+    if (msg[0]) { if (err) *err = msg; return false; }
+    *mode = m == "reproj" ? SVO_REFINE_REPROJ : SVO_REFINE_OFF;
+    *rounds = r; *iters = it; *sigma_px = sg; *min_inliers = mi;
+    return true;
+}
+
+bool Tracking::G2O_EstimatePose_PnP(const double projMatrl[12], const double projMatrr[12], const std::vector<cv::Point2f> &pointsLeft_t2,
+                                    const std::vector<cv::Point2f> *pointsRight_t2, const std::vector<cv::Point3f> &points3D_t0,
+                                    double rotation[3], double translation[3], svo_refine_result *result)
+{
+    const size_t n = points3D_t0.size();
+    if (!ctx_ || pointsLeft_t2.size() != n || (pointsRight_t2 && pointsRight_t2->size() != n)) return false;
+    static_assert(sizeof(cv::Point2f) == sizeof(svo_pt2f) && sizeof(cv::Point3f) == sizeof(svo_pt3f), "point layouts");
+    // the stage call runs with the context's settings whatever its mode: EnsureContext has applied this object's keys
+    svo_refine_result res;
+    const int rc = svo_refine_pose(ctx_, (const svo_pt3f *)points3D_t0.data(), (const svo_pt2f *)pointsLeft_t2.data(),
+                                   pointsRight_t2 ? (const svo_pt2f *)pointsRight_t2->data() : nullptr, (int)n, projMatrl, projMatrr, rotation,
+                                   translation, &res, nullptr, SVO_MEM_HOST);
+    if (rc != SVO_OK) {
+        LZB_LOG("ERROR", "svo_refine_pose failed (%d): %s", rc, svo_last_error(ctx_));
+        return false;
+    }
+    if (result) *result = res;
+    for (int i = 0; i < 3; i++) { rotation[i] = res.rvec[i]; translation[i] = res.tvec[i]; }
+    return res.status == SVO_REFINE_APPLIED;
+}
+
 Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensors)
 {
     sensors_ = sensors;
@@ -102,6 +144,13 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
     else if (lk_detector_ == SVO_DETECTOR_GFTT)
         LZB_LOG("INFO", "lk_detector: gftt (num_features %d, gftt_quality_level %g, gftt_min_distance %g)", gftt_num_, gftt_quality_,
                 gftt_min_distance_);
+    std::string refine_error;
+    if (!ReadPoseRefine(&pose_refine_, &pose_refine_rounds_, &pose_refine_iters_, &pose_refine_sigma_, &pose_refine_min_inliers_,
+                        &refine_error)) {
+        if (config_error_.empty()) config_error_ = refine_error;
+    } else if (pose_refine_ == SVO_REFINE_REPROJ)
+        LZB_LOG("INFO", "pose_refine: reproj (pose_refine_rounds %d, pose_refine_iters %d, pose_refine_sigma %g, pose_refine_min_inliers %d)",
+                pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_);
 }
 
 Tracking::~Tracking()
@@ -228,6 +277,15 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
         (rc = svo_set_lk_detector(ctx_, SVO_DETECTOR_GFTT, gftt_num_, gftt_quality_, gftt_min_distance_)) != SVO_OK) {
         LZB_LOG("ERROR", "svo_set_lk_detector (lk_detector gftt, num_features %d, gftt_quality_level %g, gftt_min_distance %g at %dx%d) "
                 "failed (%d): %s", gftt_num_, gftt_quality_, gftt_min_distance_, width, height, rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    // (also while the mode is none: svo_refine_pose, behind G2O_EstimatePose_PnP, runs with the context's settings; nothing is allocated then)
+    if ((rc = svo_set_pose_refine(ctx_, pose_refine_, pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_,
+                                  pose_refine_min_inliers_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_pose_refine (pose_refine %s, rounds %d, iters %d, sigma %g, min_inliers %d) failed (%d): %s",
+                pose_refine_ == SVO_REFINE_REPROJ ? "reproj" : "none", pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;
