@@ -602,6 +602,76 @@ int svo_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left,
                     svo_refine_result *res, uint8_t *active, int mem);
 int svo_get_refine_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out);
 
+/* ---- guided ORB matcher: epipolar stereo and sub-pixel refinement (additive; detected by symbol, the ABI version stays 9 and
+ * svo_config / svo_step_result are unchanged) -------------------------------------------------------------------------------
+ * The reference matches its ORB features by global brute force (Tracking::ORB_Robust_Find_MuliImage_MatchedFeatures); the
+ * extractor it carries comes from ORB-SLAM2, whose own matcher (Frame::ComputeStereoMatches) searches the epipolar row band,
+ * refines the disparity by an 11 x 11 SAD slide with a parabola fit and cuts outliers by the median SAD.  This is that matcher
+ * plus a temporal ratio-test match with a sub-pixel step, as a second ORB-mode matcher.  Off by default; with it off every
+ * record is byte for byte what it was.
+ *
+ * Arithmetic (restated from memory of ORB-SLAM2 and simplified where said, unpinned; every choice is listed in DESIGN.md
+ * section 2; the numpy twin is tests/_orbmatch_ref.py).  float32 with one rounding per operation.  scale[l] is the extractor's
+ * mvScaleFactor[l] (scale[0] = 1, scale[l] = float(scale[l-1] * double(orb_scale_factor))), inv[l] = 1.0f / scale[l];
+ * rnd(x) = (int)floorf(x + 0.5f); I_l is the UNBLURRED pyramid level l (what svo_orb_read_level returns), w_l x h_l; Hamming
+ * distances are integers over the 32 descriptor bytes.
+ *   Patch of a left keypoint i: o = octave, (pu, pv) = (rnd(x*inv[o]), rnd(y*inv[o])); valid iff 5 <= pu < w_o - 5 and
+ *      5 <= pv < h_o - 5.  T_i[dy][dx] = I_o[pv+dy][pu+dx] - I_o[pv][pu] (integers, dx, dy in [-5, 5]);
+ *      SAD(T, J, cu, cv) = sum |T[dy][dx] - (J[cv+dy][cu+dx] - J[cv][cu])|.  The 121 raw bytes are stored per left keypoint
+ *      (128-byte records) when the frame is ingested: ORB mode carries no pyramid from step to step.
+ *   Stage S (stereo, once per frame at ingest).  maxD = max_disparity, 0 meaning (float)P1[0].
+ *   S1 right keypoint j is a candidate of left keypoint i (uL, vL, oL) iff floorf(y_j - r_j) <= truncf(vL) <= ceilf(y_j + r_j)
+ *      with r_j = 2.0f*scale[octave_j], |octave_j - oL| <= 1 and uL - maxD <= x_j <= uL.
+ *   S2 the smallest Hamming distance among the candidates, ties to the lowest j; reject i when there is none or
+ *      best >= th_stereo.
+ *   S3 slide: sr = rnd(x_j*inv[oL]), J = the right image's I_oL; reject when the patch is invalid, sr - 10 < 0 or
+ *      sr + 11 >= w_oL; d[k] = SAD(T_i, J, sr + k, pv), k = -5..5; kb = the first minimum; reject when kb = +-5.
+ *   S4 parabola: d1, d2, d3 = (float)d[kb-1], d[kb], d[kb+1]; den = 2.0f*((d1 + d3) - 2.0f*d2); delta = den == 0 ? 0 :
+ *      (d1 - d3)/den; uR = scale[oL]*(((float)sr + (float)kb) + delta); disp = uL - uR; accept iff 0 <= disp < maxD; when
+ *      disp <= 0, uR = uL - 0.01f.
+ *   S5 median cut over the accepted keypoints of the frame: med = element n/2 of their SADs in ascending order; those with
+ *      (float)sad >= (1.5f*1.4f)*(float)med are dropped.
+ *   S6 per left keypoint: uR[i] (-1.0f: none) and sad[i] (-1: none); the right-image point of a stereo match is (uR[i], y_i).
+ *   Stage T (temporal, per pair: last frame -> current frame, left images).
+ *   T1 for each last-left i with uR[i] >= 0, current-left j is a candidate iff |octave_j - octave_i| <= 1 and, when
+ *      radius > 0, |x_j - x_i| <= radius and |y_j - y_i| <= radius (radius 0: the whole image).  b / s = the smallest / second
+ *      smallest distance over the candidates, ties to the lowest j; keep iff b <= th_track and (there is no second candidate
+ *      or (float)b < ratio*(float)s).
+ *   T2 uniqueness: of several i that keep the same j, the smallest b wins, ties to the lowest i.
+ *   T3 sub-pixel step: o = octave_i, (cu, cv) = (rnd(x_j*inv[o]), rnd(y_j*inv[o])), J = the current-left I_o; reject unless
+ *      7 <= cu < w_o - 7 and 7 <= cv < h_o - 7; D[dy][dx] = SAD(T_i, J, cu+dx, cv+dy), dx, dy in [-2, 2]; (by, bx) = the
+ *      first minimum in raster order; reject when it lies on the 5 x 5 border; the S4 parabola along each axis through the
+ *      minimum; t2 = (scale[o]*(((float)cu + (float)bx) + dx'), scale[o]*(((float)cv + (float)by) + dy')).
+ *   T4 emitted in ascending i: t1_left = (x_i, y_i), t1_right = (uR[i], y_i), t2_left = t2 -- the lists the brute matcher
+ *      writes.  Triangulation, solvePnPRansac, the refinement stage, the gates and SVO_FAIL_FEW_TRACKS
+ *      (n_tracked < num_features_tracking) are untouched.
+ *   svo_set_orb_matcher : ORB mode.  Applies to frames ingested by LATER calls on every fused entry point.  A frame stored
+ *       from before the switch to SVO_ORB_MATCHER_GUIDED (svo_add_frame's previous frame, a stream's stored frame, a carried
+ *       frame) has no patches and no stereo matches: its first pair ends as SVO_FAIL_FEW_TRACKS with n_tracked = 0, the next
+ *       pair is a regular one.  SVO_ERR_ARG (nothing changes): an LK-mode context; an unknown mode; th_stereo or th_track
+ *       outside 1..256; ratio outside (0, 1]; radius or max_disparity negative or not finite.  Memory: allocated by the first
+ *       call that selects SVO_ORB_MATCHER_GUIDED (or the first stage call), with cap = max_keypoints rounded up to 4: per
+ *       working frame (max_batch + 1 of them) and per stream of a stream set 16 + 136*cap bytes (the 128-byte patch, uR and
+ *       sad per keypoint), and 20*cap bytes per pair of max_batch (max_batch = 256, max_keypoints = 8192: 273 MB + 40 MB;
+ *       max_keypoints = 2048: 68 MB + 10 MB; 1 MB = 2^20 bytes).  A context that never selects it allocates and pays nothing.
+ *   svo_get_orb_matcher : what is set.  Any pointer may be NULL.
+ *   svo_orb_stereo_frame (stage API): extracts both images (HOST or DEVICE, one pitch) into stage slot `slot` in {0, 1} -- frame
+ *       slots 0 / 1 of the context: the online ring and a carried frame do not survive -- and runs stage S with the current
+ *       settings.  kps / uR / sad (HOST, each may be NULL) receive the left keypoints and S6, *n_out the count;
+ *       SVO_ERR_ARG when cap is too small.
+ *   svo_orb_track_frames (stage API): stage T from stage slot slot_prev to slot_cur (both filled by svo_orb_stereo_frame).
+ *       HOST outputs, each may be NULL: the three point lists and the keypoint indices of every track; *n_out the count.
+ *   svo_get_frame_stereo : S6 of the current frame of svo_add_frame (the left keypoints: svo_get_frame_keypoints). */
+#define SVO_ORB_MATCHER_BRUTE  0
+#define SVO_ORB_MATCHER_GUIDED 1
+int svo_set_orb_matcher(svo_ctx *ctx, int mode, int th_stereo, int th_track, double ratio, double radius, double max_disparity);
+int svo_get_orb_matcher(const svo_ctx *ctx, int *mode, int *th_stereo, int *th_track, double *ratio, double *radius, double *max_disparity);
+int svo_orb_stereo_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem, int slot,
+                         svo_keypoint *kps, float *uR, int32_t *sad, int cap, int *n_out);
+int svo_orb_track_frames(svo_ctx *ctx, int slot_prev, int slot_cur, svo_pt2f *t1_left, svo_pt2f *t1_right, svo_pt2f *t2_left,
+                         int32_t *idx_prev, int32_t *idx_cur, int cap, int *n_out);
+int svo_get_frame_stereo(svo_ctx *ctx, float *uR, int32_t *sad, int cap, int *n_out);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

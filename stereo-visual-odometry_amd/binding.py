@@ -52,6 +52,7 @@ class RefineResult(C.Structure):
                 ("status", C.c_int32), ("_pad", C.c_int32)]
 
 
+ORB_MATCHER_BRUTE, ORB_MATCHER_GUIDED = 0, 1                                               # svo_set_orb_matcher
 REFINE_OFF, REFINE_REPROJ = 0, 1                                       # svo_set_pose_refine
 REFINE_APPLIED, REFINE_KEPT_PNP, REFINE_SKIPPED = 0, 1, 2              # svo_refine_result.status
 
@@ -162,6 +163,15 @@ def load_library():
     lib.svo_refine_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.POINTER(RefineResult), C.c_void_p, C.c_int]
     lib.svo_get_refine_result.argtypes = [C.c_void_p, C.c_int, C.POINTER(RefineResult), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    # guided ORB matcher (additive entry points, like the stream sets)
+    lib.svo_set_orb_matcher.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
+    lib.svo_get_orb_matcher.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.svo_orb_stereo_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_orb_track_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.POINTER(C.c_int)]
+    lib.svo_get_frame_stereo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     _LIB = lib
     return lib
 
@@ -552,6 +562,61 @@ class Context:
         if mem == MEM_DEVICE:
             self._order_out(dist)
         return idx[:len(query)], dist[:len(query)]
+
+    # ---- guided ORB matcher (svo_set_orb_matcher / svo_orb_stereo_frame / svo_orb_track_frames) ----
+    def set_orb_matcher(self, mode, th_stereo=75, th_track=100, ratio=0.9, radius=0.0, max_disparity=0.0):
+        """ORB mode: the matcher of the frames ingested by later calls -- "brute" (the reference's, the default) or "guided":
+        epipolar stereo search with a sub-pixel SAD slide, temporal ratio-test match with a sub-pixel step (radius 0: the whole
+        image; max_disparity 0: P1[0])."""
+        if isinstance(mode, str):
+            if mode not in ("brute", "guided"):
+                raise ValueError(f"matcher must be 'brute' or 'guided', not {mode!r}")
+            mode = ORB_MATCHER_GUIDED if mode == "guided" else ORB_MATCHER_BRUTE
+        self._check(self.lib.svo_set_orb_matcher(self.h, int(mode), int(th_stereo), int(th_track), float(ratio), float(radius),
+                                                 float(max_disparity)))
+
+    def get_orb_matcher(self):
+        """("brute" | "guided", th_stereo, th_track, ratio, radius, max_disparity) as set."""
+        m, a, b = C.c_int(0), C.c_int(0), C.c_int(0)
+        r, rad, d = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._check(self.lib.svo_get_orb_matcher(self.h, C.byref(m), C.byref(a), C.byref(b), C.byref(r), C.byref(rad), C.byref(d)))
+        return ("guided" if m.value == ORB_MATCHER_GUIDED else "brute"), a.value, b.value, r.value, rad.value, d.value
+
+    def orb_stereo_frame(self, left, right, slot=0, cap=None):
+        """svo_orb_stereo_frame: extraction of both images into stage slot 0 / 1 + stage S.  Returns (left keypoints, uR float32,
+        sad int32); uR -1 / sad -1: no stereo match."""
+        cap = cap or self.cfg.max_keypoints
+        pl, pitch, mem = self._img(left)
+        pr, pitch_r, mem_r = self._img(right)
+        if pitch != pitch_r or mem != mem_r:
+            raise SvoError("orb_stereo_frame: left and right must share the row pitch and the memory kind")
+        kps = np.zeros(cap, dtype=KP_DTYPE)
+        uR = np.zeros(cap, np.float32)
+        sad = np.zeros(cap, np.int32)
+        n = C.c_int(0)
+        self._check(self.lib.svo_orb_stereo_frame(self.h, pl, pr, pitch, mem, int(slot), C.c_void_p(kps.ctypes.data),
+                                                  C.c_void_p(uR.ctypes.data), C.c_void_p(sad.ctypes.data), cap, C.byref(n)))
+        return kps[:n.value].copy(), uR[:n.value].copy(), sad[:n.value].copy()
+
+    def orb_track_frames(self, slot_prev=0, slot_cur=1, cap=None):
+        """svo_orb_track_frames: stage T between two stage slots.  Returns (t1_left, t1_right, t2_left (m, 2) float32,
+        idx_prev, idx_cur int32)."""
+        cap = cap or self.cfg.max_keypoints
+        pts = [np.zeros((cap, 2), np.float32) for _ in range(3)]
+        idx = [np.zeros(cap, np.int32) for _ in range(2)]
+        n = C.c_int(0)
+        self._check(self.lib.svo_orb_track_frames(self.h, int(slot_prev), int(slot_cur), *[C.c_void_p(a.ctypes.data) for a in pts + idx],
+                                                  cap, C.byref(n)))
+        return tuple(a[:n.value].copy() for a in pts + idx)
+
+    def get_frame_stereo(self, cap=None):
+        """svo_get_frame_stereo: (uR, sad) of the current frame of add_frame (its keypoints: get_frame_keypoints)."""
+        cap = cap or self.cfg.max_keypoints
+        uR = np.zeros(cap, np.float32)
+        sad = np.zeros(cap, np.int32)
+        n = C.c_int(0)
+        self._check(self.lib.svo_get_frame_stereo(self.h, C.c_void_p(uR.ctypes.data), C.c_void_p(sad.ctypes.data), cap, C.byref(n)))
+        return uR[:n.value].copy(), sad[:n.value].copy()
 
     # ---- FAST corner buckets (svo_set_fast_buckets / svo_bucket_corners) ---------------------------
     def set_fast_buckets(self, cell_w, cell_h, per_cell):

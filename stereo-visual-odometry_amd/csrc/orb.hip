@@ -2381,6 +2381,7 @@ int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int
         pitch >= g.w[0] + 16)
         z = OrbL0{img, img2, pitch, img_stride};
     ctx->orb_level0_in_slot = z.img == nullptr;
+    ctx->orb_l0 = z; ctx->orb_l0_slot0 = slot0;          // (the guided matcher reads the unblurred levels after the extraction)
     {
         const int n = n_img;
         uint8_t *sl = slots;

@@ -43,7 +43,10 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
         // frame f -> feature slots 2f (left), 2f+1 (right)
         // (orb_extract_batch records its own stage marks: orb_pyramid, orb_cellfast, orb_quadtree, orb_describe)
         // (level 0 read in place: the frames belong to the caller's batch / the context's staging until the step is done)
-        return orb_extract_batch(ctx, L, R, pitch, frame_stride, 2 * f0, 2 * n_new, ctx->stream, /*in_place*/ true);
+        const int rc = orb_extract_batch(ctx, L, R, pitch, frame_stride, 2 * f0, 2 * n_new, ctx->stream, /*in_place*/ true);
+        // svo_set_orb_matcher: stage S of the guided matcher while the levels are in the slots and the caller's frames are valid
+        if (rc == SVO_OK && ctx->orbm_mode == SVO_ORB_MATCHER_GUIDED) return orbm_stereo_frames(ctx, 2 * f0, n_new, ctx->stream);
+        return rc;
     }
     const PyrGeom &g = ctx->geom;
     PyrArgs p{};
@@ -91,7 +94,7 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
 // What a frame carries from one step to the next -- the list exists here only.  work[k]: the working array behind segment k (frame
 // slot f at work[k] + f * bytes[k]); is_count[k]: a count segment.  carry_last_frame moves them between frame slots, a stream
 // set keeps them per stream, in this order (streams_create sizes the store by them).
-static int stream_segments(svo_ctx *ctx, uint8_t *work[4], size_t bytes[4], int is_count[4])
+static int stream_segments(svo_ctx *ctx, uint8_t *work[kMaxSeg], size_t bytes[kMaxSeg], int is_count[kMaxSeg])
 {
     const size_t cap = (size_t)ctx->cfg.max_keypoints;
     if (ctx->cfg.track_mode == SVO_MODE_ORB) {
@@ -100,6 +103,11 @@ static int stream_segments(svo_ctx *ctx, uint8_t *work[4], size_t bytes[4], int 
         work[1] = ctx->orb_desc;                bytes[1] = 2 * kcap * 32;                   is_count[1] = 0;
         work[2] = (uint8_t *)ctx->orb_n;        bytes[2] = 2 * sizeof(int);                 is_count[2] = 1;
         work[3] = (uint8_t *)ctx->orb_overflow; bytes[3] = 2 * sizeof(int);                 is_count[3] = 1;
+        if (ctx->orbm_mode == SVO_ORB_MATCHER_GUIDED) {
+            // the guided matcher's frame block: stage S's uR / sad and the patches stage T compares against the next frame
+            work[4] = ctx->orbm_frames;         bytes[4] = ctx->orbm_frame_bytes;           is_count[4] = 0;
+            return 5;
+        }
     } else {
         work[0] = ctx->bslots;                  bytes[0] = (size_t)2 * ctx->geom.slot_bytes; is_count[0] = 0;
         work[1] = (uint8_t *)ctx->kp_xy;        bytes[1] = cap * sizeof(float2);            is_count[1] = 0;
@@ -112,8 +120,8 @@ static int stream_segments(svo_ctx *ctx, uint8_t *work[4], size_t bytes[4], int 
 // A micro-batch of a stream starts with the frame the previous one ended with: instead of building that frame's
 // pyramids and detecting its features again, what the pair needs of it is carried from frame slot `last` to slot 0
 // (LK mode: the two pyramid slots, the FAST keypoints + responses + count; ORB mode: both images' keypoints, descriptors,
-// counts and capacity flags) -- ONE launch, 16 bytes per thread.
-struct CarryArgs { uint8_t *dst[4]; const uint8_t *src[4]; size_t bytes[4]; int n; };
+// counts and capacity flags, and with the guided matcher the frame's stereo block) -- ONE launch, 16 bytes per thread.
+struct CarryArgs { uint8_t *dst[kMaxSeg]; const uint8_t *src[kMaxSeg]; size_t bytes[kMaxSeg]; int n; };
 __global__ __launch_bounds__(256) void carry_frame_kernel(CarryArgs a)
 {
     const int seg = blockIdx.y;
@@ -128,8 +136,8 @@ __global__ __launch_bounds__(256) void carry_frame_kernel(CarryArgs a)
 static void carry_last_frame(svo_ctx *ctx, int last)
 {
     CarryArgs c{};
-    uint8_t *work[4];
-    int is_count[4];
+    uint8_t *work[kMaxSeg];
+    int is_count[kMaxSeg];
     c.n = stream_segments(ctx, work, c.bytes, is_count);
     for (int k = 0; k < c.n; k++) { c.dst[k] = work[k]; c.src[k] = work[k] + (size_t)last * c.bytes[k]; }
     hipLaunchKernelGGL(carry_frame_kernel, dim3(64, c.n), dim3(256), 0, ctx->stream, c);
@@ -142,9 +150,9 @@ static void carry_last_frame(svo_ctx *ctx, int last)
 // zeroed (no keypoints: the pair tracks nothing and the pose stage writes the init record), the others are not touched.
 // Scatter (to_store = 1): slot -> store, every item.  16 bytes per lane where both ends are 16-byte aligned, else 4, else 1.
 struct StreamCopyArgs {
-    uint8_t *store[4], *work[4];
-    size_t bytes[4];
-    int is_count[4];
+    uint8_t *store[kMaxSeg], *work[kMaxSeg];
+    size_t bytes[kMaxSeg];
+    int is_count[kMaxSeg];
     int n_seg, n_items, slot0, to_store;
     StreamTable tab;
 };
@@ -220,7 +228,11 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
             SVO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_back, 0));
             ctx->back_pending = false;
         }
-        orb_match_pairs(ctx, n_pairs, fp0, fc0, fstep, ctx->stream);
+        if (ctx->orbm_mode == SVO_ORB_MATCHER_GUIDED) {          // svo_set_orb_matcher: stage T writes the same lists
+            const int rc = orbm_track_pairs(ctx, n_pairs, fp0, fc0, fstep, ctx->stream);
+            if (rc) return rc;
+        } else
+            orb_match_pairs(ctx, n_pairs, fp0, fc0, fstep, ctx->stream);
         mark(ctx, kTMatch);
         // + n_prev / n_cur = left keypoint counts of the two frames (feature slots 2f) and the capacity flags, frozen for the
         // pose stage by the pairs' begin workgroups
@@ -430,7 +442,7 @@ int pipeline_streams_create(svo_ctx *ctx, int n_streams)
     SVO_ARG(n_streams >= 1 && n_streams <= (1 << 20), "n_streams must be >= 1");
     SVO_HIP(hipSetDevice(ctx->device));
     if (ctx->cfg.track_mode == SVO_MODE_ORB) { const int rc = orb_alloc(ctx); if (rc) return rc; }
-    uint8_t *work[4]; int is_count[4];
+    uint8_t *work[kMaxSeg]; int is_count[kMaxSeg];
     ss.n_seg = stream_segments(ctx, work, ss.seg_bytes, is_count);
     for (int k = 0; k < ss.n_seg; k++) {
         // + 16: a segment whose size is not a multiple of 16 still ends inside its allocation for every access width

@@ -25,11 +25,12 @@ struct DevArena {
 // A stream set (svo_streams_create): n independent live stereo streams of one context.  What a stream keeps in HBM between
 // steps is the segments stream_segments() lists (pipeline.hip; carry_last_frame moves the same list) -- seg[k] + id * seg_bytes[k],
 // k < n_seg -- and its frame_pose_ (pose + 16 * id); the INITING / TRACKING state is host-side (steps are issued in host order).
+constexpr int kMaxSeg = 5;               // segments a frame carries at most (ORB mode with the guided matcher: the stereo block)
 struct StreamSet {
     int n = 0;
     int n_seg = 0;
-    uint8_t *seg[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t seg_bytes[4] = {0, 0, 0, 0};
+    uint8_t *seg[kMaxSeg] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t seg_bytes[kMaxSeg] = {0, 0, 0, 0, 0};
     double *pose = nullptr;
     std::vector<int> n_frames;        // frames fed since the stream's reset (0: INITING)
     std::vector<int> seen;            // call number a stream id was last named in (duplicate check)
@@ -129,6 +130,14 @@ struct svo_ctx {
     int *orb_sel = nullptr, *orb_sel_cnt = nullptr, *orb_overflow = nullptr;
     void *orb_kps = nullptr; uint8_t *orb_desc = nullptr; int *orb_n = nullptr; int orb_kp_cap = 0, orb_cand_cap = 0;
     int *orb_midx[2] = {nullptr, nullptr}; float *orb_mdist[2] = {nullptr, nullptr};
+    // ---- guided ORB matcher (svo_set_orb_matcher, orb_match.hip; off and nothing allocated until it is selected)
+    int orbm_mode = SVO_ORB_MATCHER_BRUTE, orbm_th_stereo = 75, orbm_th_track = 100;
+    double orbm_ratio = 0.9, orbm_radius = 0.0, orbm_max_disparity = 0.0;     // (the kernels take them as floats)
+    int orbm_epoch = 0;                                  // selection count: a frame block written under another epoch has no stereo data
+    int orbm_kc = 0; size_t orbm_frame_bytes = 0;        // keypoints per block (orb_kp_cap rounded up to 4), bytes of a frame's block
+    uint8_t *orbm_frames = nullptr;                      // per frame slot: header, uR, sad, 128-byte patches
+    float2 *orbm_t2 = nullptr; int *orbm_mj = nullptr; unsigned *orbm_mkey = nullptr, *orbm_win = nullptr;    // per pair x orbm_kc
+    svo::OrbL0 orb_l0{}; int orb_l0_slot0 = 0;           // where the last extraction read level 0 in place (img null: it copied), its first image slot
     // ---- pinned host scratch: counts and small read-backs at the front, step records from kPinnedRecords on
     void *h_pinned = nullptr; size_t h_pinned_bytes = 0;
     // ---- overlap mode (svo_set_overlap): the pose stage of batch k runs on side_stream while
@@ -238,6 +247,10 @@ int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int
                       int n_img, hipStream_t st, bool in_place = false);
 int orb_match_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hipStream_t st);
 void orb_launch_match_fixed(svo_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, hipStream_t st);
+// orb_match.hip: the guided ORB matcher
+int orbm_alloc(svo_ctx *ctx);                            // its device blocks, on first use
+int orbm_stereo_frames(svo_ctx *ctx, int slot0, int n_frames, hipStream_t st);      // stage S on frames just extracted into image slots slot0 ..
+int orbm_track_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hipStream_t st, int *idx_prev = nullptr, int *idx_cur = nullptr);
 // resize.hip
 int resize_plan(svo_ctx *ctx, int sw, int sh, int dw, int dh, int interp, double fx, double fy, int *tab);
 // n_frames images per eye (eye 1 may be null), frame f at base + f * stride; one launch

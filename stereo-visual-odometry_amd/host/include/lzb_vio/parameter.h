@@ -17,7 +17,9 @@ public:
     Parameter();                               // reads every key of the table from Config
 
 #define LZB_KEY(member, key, type) type member;
+#define LZB_KEY_OPT(member, key, type, dflt) type member = dflt;
 #include "lzb_vio/parameter_keys.def"
+#undef LZB_KEY_OPT
 #undef LZB_KEY
 
     // derived from the keys above plus t_lr0..2 / R_lr0..8

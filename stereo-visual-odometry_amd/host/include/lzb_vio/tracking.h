@@ -68,6 +68,13 @@ public:
     // rounds outside 1..16, iterations outside 1..100, a sigma that is not a finite number > 0, min_inliers < 1 -> false, *err
     // names the key.  The values are checked even while the mode is none.
     static bool ReadPoseRefine(int *mode, int *rounds, int *iters, double *sigma_px, int *min_inliers, std::string *err);
+    // additive YAML keys orb_matcher: brute | guided (absent: brute, the reference's matcher), orb_match_th_stereo (75),
+    // orb_match_th_track (100), orb_match_ratio (0.9), orb_match_radius (0: the whole image) and orb_max_disparity (0: P1[0]):
+    // the guided ORB matcher (svo_set_orb_matcher, include/svo_abi.h); Parameter carries them.  ReadOrbMatcher reads and checks
+    // them for the loaded YAML: an unknown matcher, a threshold outside 1..256, a ratio outside (0, 1], a negative or
+    // non-finite radius / disparity, and guided without track_mode ORB_stereof2f_pnp are refused (false + a message that
+    // names the key).  Applied right after svo_create.
+    static bool ReadOrbMatcher(int *mode, int *th_stereo, int *th_track, double *ratio, double *radius, double *max_disparity, std::string *err);
     // The stage the reference declares as Tracking::G2O_EstimatePose_PnP (include/lzb_vio/tracking.h:82; its body there is a copy
     // of the OpenCV one and it is never called): here it does what its name says, through svo_refine_pose -- a robust motion-only
     // bundle adjustment of (rotation, translation) on the points' t2 observations in the left and, when pointsRight_t2 is not null,
@@ -130,6 +137,8 @@ private:
     double gftt_quality_ = 0.01, gftt_min_distance_ = 20.0;  // additive YAML keys gftt_quality_level, gftt_min_distance
     int pose_refine_ = SVO_REFINE_OFF, pose_refine_rounds_ = 4, pose_refine_iters_ = 10, pose_refine_min_inliers_ = 6;   // pose_refine*
     double pose_refine_sigma_ = 1.0;
+    int orb_matcher_ = SVO_ORB_MATCHER_BRUTE, orb_match_th_stereo_ = 75, orb_match_th_track_ = 100;                     // orb_matcher / orb_match_*
+    double orb_match_ratio_ = 0.9, orb_match_radius_ = 0.0, orb_max_disparity_ = 0.0;
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128
     double image_scale_ = 1.0;                               // additive YAML key image_scale (1 = no ingest stage)
     int image_interp_ = SVO_INTERP_NEAREST;                  // additive YAML key image_interp: nearest (default) | linear

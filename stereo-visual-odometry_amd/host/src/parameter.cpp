@@ -28,7 +28,9 @@ void projection(const double K[9], const double R[9], const double t[3], double 
 Parameter::Parameter()
 {
 #define LZB_KEY(member, key, type) member = Config::Get<type>(key);
+#define LZB_KEY_OPT(member, key, type, dflt) if (Config::Has(key)) member = Config::Get<type>(key);
 #include "lzb_vio/parameter_keys.def"
+#undef LZB_KEY_OPT
 #undef LZB_KEY
 
     char name[16];

@@ -92,6 +92,31 @@ bool Tracking::ReadPoseRefine(int *mode, int *rounds, int *iters, double *sigma_
     return true;
 }
 
+bool Tracking::ReadOrbMatcher(int *mode, int *th_stereo, int *th_track, double *ratio, double *radius, double *max_disparity, std::string *err)
+{
+    *mode = SVO_ORB_MATCHER_BRUTE; *th_stereo = 75; *th_track = 100; *ratio = 0.9; *radius = 0.0; *max_disparity = 0.0;
+    const std::string m = Config::Has("orb_matcher") ? Config::Get<std::string>("orb_matcher") : std::string("brute");
+    // (a value that does not parse as a number reads as 0)
+    const int ts = Config::Has("orb_match_th_stereo") ? Config::Get<int>("orb_match_th_stereo") : 75;
+    const int tt = Config::Has("orb_match_th_track") ? Config::Get<int>("orb_match_th_track") : 100;
+    const double ra = Config::Has("orb_match_ratio") ? Config::Get<double>("orb_match_ratio") : 0.9;
+    const double rd = Config::Has("orb_match_radius") ? Config::Get<double>("orb_match_radius") : 0.0;
+    const double md = Config::Has("orb_max_disparity") ? Config::Get<double>("orb_max_disparity") : 0.0;
+    char msg[240] = "";
+    if (m != "brute" && m != "guided") snprintf(msg, sizeof(msg), "orb_matcher: '%s' is neither 'brute' nor 'guided'", m.c_str());
+    else if (ts < 1 || ts > 256) snprintf(msg, sizeof(msg), "orb_match_th_stereo: %d is outside 1..256", ts);
+    else if (tt < 1 || tt > 256) snprintf(msg, sizeof(msg), "orb_match_th_track: %d is outside 1..256", tt);
+    else if (!(std::isfinite(ra) && ra > 0.0 && ra <= 1.0)) snprintf(msg, sizeof(msg), "orb_match_ratio: %g is outside (0, 1]", ra);
+    else if (!(std::isfinite(rd) && rd >= 0.0)) snprintf(msg, sizeof(msg), "orb_match_radius: %g is not a finite number >= 0", rd);
+    else if (!(std::isfinite(md) && md >= 0.0)) snprintf(msg, sizeof(msg), "orb_max_disparity: %g is not a finite number >= 0", md);
+    else if (m == "guided" && !(Config::Has("track_mode") && Config::Get<std::string>("track_mode") == "ORB_stereof2f_pnp"))
+        snprintf(msg, sizeof(msg), "orb_matcher: guided without track_mode ORB_stereof2f_pnp (the matcher switch is an ORB-mode option)");
+    if (msg[0]) { if (err) *err = msg; return false; }
+    *mode = m == "guided" ? SVO_ORB_MATCHER_GUIDED : SVO_ORB_MATCHER_BRUTE;
+    *th_stereo = ts; *th_track = tt; *ratio = ra; *radius = rd; *max_disparity = md;
+    return true;
+}
+
 bool Tracking::G2O_EstimatePose_PnP(const double projMatrl[12], const double projMatrr[12], const std::vector<cv::Point2f> &pointsLeft_t2,
                                     const std::vector<cv::Point2f> *pointsRight_t2, const std::vector<cv::Point3f> &points3D_t0,
                                     double rotation[3], double translation[3], svo_refine_result *result)
@@ -151,6 +176,13 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
     } else if (pose_refine_ == SVO_REFINE_REPROJ)
         LZB_LOG("INFO", "pose_refine: reproj (pose_refine_rounds %d, pose_refine_iters %d, pose_refine_sigma %g, pose_refine_min_inliers %d)",
                 pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_);
+    std::string matcher_error;
+    if (!ReadOrbMatcher(&orb_matcher_, &orb_match_th_stereo_, &orb_match_th_track_, &orb_match_ratio_, &orb_match_radius_,
+                        &orb_max_disparity_, &matcher_error)) {
+        if (config_error_.empty()) config_error_ = matcher_error;
+    } else if (orb_matcher_ == SVO_ORB_MATCHER_GUIDED)
+        LZB_LOG("INFO", "orb_matcher: guided (orb_match_th_stereo %d, orb_match_th_track %d, orb_match_ratio %g, orb_match_radius %g, "
+                "orb_max_disparity %g)", orb_match_th_stereo_, orb_match_th_track_, orb_match_ratio_, orb_match_radius_, orb_max_disparity_);
 }
 
 Tracking::~Tracking()
@@ -286,6 +318,15 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
                                   pose_refine_min_inliers_)) != SVO_OK) {
         LZB_LOG("ERROR", "svo_set_pose_refine (pose_refine %s, rounds %d, iters %d, sigma %g, min_inliers %d) failed (%d): %s",
                 pose_refine_ == SVO_REFINE_REPROJ ? "reproj" : "none", pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_, rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    if (orb_matcher_ == SVO_ORB_MATCHER_GUIDED &&
+        (rc = svo_set_orb_matcher(ctx_, SVO_ORB_MATCHER_GUIDED, orb_match_th_stereo_, orb_match_th_track_, orb_match_ratio_, orb_match_radius_,
+                                  orb_max_disparity_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_orb_matcher (orb_matcher guided, th_stereo %d, th_track %d, ratio %g, radius %g, max_disparity %g) failed (%d): %s",
+                orb_match_th_stereo_, orb_match_th_track_, orb_match_ratio_, orb_match_radius_, orb_max_disparity_, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;

@@ -191,6 +191,16 @@ int main(int argc, char **argv)
                interp == SVO_INTERP_LINEAR ? "linear" : "nearest", ok && scale < 1.0 ? 1 : 0);
         if (!ok) printf("image_scale_error=%s\n", err.c_str());
     }
+    {
+        // additive keys orb_matcher / orb_match_* / orb_max_disparity: what Parameter carries and what Tracking makes of them
+        int mode, ts, tt; double ra, rd, md; std::string err;
+        const bool ok = lzb_vio::Tracking::ReadOrbMatcher(&mode, &ts, &tt, &ra, &rd, &md, &err);
+        printf("orb_matcher_param=%s %d %d %.17g %.17g %.17g\n", p.orb_matcher_.c_str(), p.orb_match_th_stereo_, p.orb_match_th_track_,
+               p.orb_match_ratio_, p.orb_match_radius_, p.orb_max_disparity_);
+        printf("orb_matcher_ok=%d\norb_matcher=%s %d %d %.17g %.17g %.17g\n", ok ? 1 : 0, mode == SVO_ORB_MATCHER_GUIDED ? "guided" : "brute", ts, tt,
+               ra, rd, md);
+        if (!ok) printf("orb_matcher_error=%s\n", err.c_str());
+    }
     for (int i = 2; i < argc; i++) {
         cv::Mat m;
         bool ok = lzb_vio::ReadImageGray(argv[i], m);
