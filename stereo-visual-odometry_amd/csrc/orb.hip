@@ -2120,8 +2120,6 @@ __global__ __launch_bounds__(256) void orb_filter_kernel(OrbFilterArgs a)
 }
 
 // ---- host side --------------------------------------------------------------------------------
-static int align_up_i(int v, int a) { return (v + a - 1) / a * a; }
-
 // ORBextractor::ORBextractor + ComputePyramid geometry (all float/double expressions as the
 // reference evaluates them)
 int orb_make_geom(const svo_config &cfg, OrbGeom *g)
@@ -2164,7 +2162,7 @@ int orb_make_geom(const svo_config &cfg, OrbGeom *g)
         g->w[l] = (int)lrintf((float)cfg.width * inv_scale[l]);
         g->h[l] = (int)lrintf((float)cfg.height * inv_scale[l]);
         if (g->w[l] < 1 || g->h[l] < 1) return SVO_ERR_ARG;
-        g->pitch[l] = align_up_i(g->w[l] + 2 * kPad, 64);
+        g->pitch[l] = (int)align_up(g->w[l] + 2 * kPad, 64);
         g->origin[l] = off + (int64_t)kPad * g->pitch[l] + kPad;
         off += (int64_t)g->pitch[l] * (g->h[l] + 2 * kPad);
         off = (off + 255) / 256 * 256;
@@ -2358,7 +2356,14 @@ int orb_alloc(svo_ctx *ctx)
     return SVO_OK;
 }
 
-void orb_free(svo_ctx *) {}        // the ORB buffers belong to the context's arena (or its lazy extras): freed with it
+// An image never holds more keypoints than the per-level quotas allow (+ the extractor's slack): what sizes the grids of
+// the describe and match kernels, not the capacity of the buffers.
+int orb_max_keypoints(const svo_ctx *ctx)
+{
+    int max_kp = 0;
+    for (int l = 0; l < ctx->orb_geom.nlevels; l++) max_kp += ctx->orb_geom.quota[l] + 8;
+    return max_kp > ctx->orb_kp_cap ? ctx->orb_kp_cap : max_kp;
+}
 
 // ORBextractor::operator() on `n_img` images (image b at img + b*img_stride, or interleaved L/R
 // when img2 != null) into output slots [slot0, slot0 + n_img).
@@ -2481,10 +2486,7 @@ int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int
     e.lvl_cand = lvl_cand; e.cand_cap = kCandCap; e.sel = d.sel; e.sel_cnt = d.sel_cnt; e.sel_cap = ctx->orb_node_cap;
     e.kps = (svo_keypoint *)ctx->orb_kps + (size_t)slot0 * ctx->orb_kp_cap; e.desc = ctx->orb_desc + (size_t)slot0 * ctx->orb_kp_cap * 32;
     e.n_out = ctx->orb_n + slot0; e.out_cap = ctx->orb_kp_cap; e.overflow = ovf;
-    int max_kp = 0;
-    for (int l = 0; l < L; l++) max_kp += g.quota[l] + 8;
-    if (max_kp > ctx->orb_kp_cap) max_kp = ctx->orb_kp_cap;
-    e.blocks_per_img = (max_kp + 7) / 8; e.n_img = n_img;
+    e.blocks_per_img = (orb_max_keypoints(ctx) + 7) / 8; e.n_img = n_img;
     hipLaunchKernelGGL(orb_describe_kernel, dim3(e.blocks_per_img * n_img), blk, 0, st, e);    // two keypoints per wave
     timing_mark(ctx, "orb_describe");
     return SVO_OK;
@@ -2505,11 +2507,8 @@ int orb_match_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hipS
     const int *N = ctx->orb_n;
     const svo_keypoint *K = (const svo_keypoint *)ctx->orb_kps;
     const int64_t fs = (int64_t)fstep * 2;                         // image slots per pair step
-    // an image never holds more keypoints than the per-level quotas allow (+ the extractor's slack): the grid is sized
-    // by that, not by the capacity of the buffers (three quarters of the workgroups were launched to return at once)
-    int max_kp = 0;
-    for (int l = 0; l < ctx->orb_geom.nlevels; l++) max_kp += ctx->orb_geom.quota[l] + 8;
-    if (max_kp > cap) max_kp = cap;
+    // (sized by the buffers' capacity, three quarters of the workgroups were launched to return at once)
+    const int max_kp = orb_max_keypoints(ctx);
     const bool small = (int64_t)n_pairs * ((max_kp + 255) / 256) < 256;              // fewer workgroups than CUs: latency shape
     const int qblocks = small ? (max_kp + 127) / 128 : (max_kp + 255) / 256, qthreads = small ? 256 : 512;
     auto kern = small ? orb_match_kernel<4> : orb_match_kernel<8>;

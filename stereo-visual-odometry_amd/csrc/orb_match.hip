@@ -406,14 +406,6 @@ __global__ __launch_bounds__(256) void orbm_emit_kernel(OrbmTrackArgs a)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static int orbm_max_kp(const svo_ctx *ctx)
-{
-    // an image never holds more keypoints than the per-level quotas allow (+ the extractor's slack), as orb_match_pairs sizes its grid
-    int max_kp = 0;
-    for (int l = 0; l < ctx->orb_geom.nlevels; l++) max_kp += ctx->orb_geom.quota[l] + 8;
-    return max_kp > ctx->orb_kp_cap ? ctx->orb_kp_cap : max_kp;
-}
-
 int orbm_alloc(svo_ctx *ctx)
 {
     int rc = orb_alloc(ctx);
@@ -457,7 +449,7 @@ int orbm_stereo_frames(svo_ctx *ctx, int slot0, int n_frames, hipStream_t st)
     a.frame_bytes = (int64_t)ctx->orbm_frame_bytes; a.kc = ctx->orbm_kc;
     a.frames = ctx->orbm_frames + (size_t)(slot0 / 2) * ctx->orbm_frame_bytes;
     a.maxd = orbm_maxd(ctx); a.th = ctx->orbm_th_stereo; a.epoch = ctx->orbm_epoch;
-    a.wg_per_frame = (orbm_max_kp(ctx) + kOrbmSWaves - 1) / kOrbmSWaves;
+    a.wg_per_frame = (orb_max_keypoints(ctx) + kOrbmSWaves - 1) / kOrbmSWaves;
     hipLaunchKernelGGL(orbm_stereo_kernel, dim3(a.wg_per_frame * n_frames), dim3(64 * kOrbmSWaves), 0, st, a);
     const OrbmMedianArgs m{a.frames, a.frame_bytes, a.kc};
     hipLaunchKernelGGL(orbm_median_kernel, dim3(n_frames), dim3(256), 0, st, m);
@@ -479,7 +471,7 @@ int orbm_track_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hip
     a.mj = ctx->orbm_mj; a.mkey = ctx->orbm_mkey; a.win = ctx->orbm_win; a.t2 = ctx->orbm_t2; a.m_stride = ctx->orbm_kc;
     a.t1l = ctx->cmp[0]; a.t1r = ctx->cmp[1]; a.t2l = ctx->cmp[3]; a.out_stride = ctx->cfg.max_keypoints; a.m_out = ctx->m_out;
     a.idx_prev = idx_prev; a.idx_cur = idx_cur;
-    a.wg_per_pair = (orbm_max_kp(ctx) + kOrbmWaves - 1) / kOrbmWaves;
+    a.wg_per_pair = (orb_max_keypoints(ctx) + kOrbmWaves - 1) / kOrbmWaves;
     SVO_HIP(hipMemsetAsync(a.win, 0xFF, sizeof(unsigned) * (size_t)a.m_stride * n_pairs, st));
     hipLaunchKernelGGL(orbm_search_kernel, dim3(a.wg_per_pair * n_pairs), dim3(64 * kOrbmWaves), 0, st, a);
     hipLaunchKernelGGL(orbm_subpix_kernel, dim3(a.wg_per_pair * n_pairs), dim3(64 * kOrbmWaves), 0, st, a);

@@ -20,7 +20,7 @@ void timing_mark(svo_ctx *ctx, const char *name)
     if (ctx->ev_used >= 16384) return;                 // bounded log
     if (ctx->ev_used == ctx->ev_pool.size()) {
         hipEvent_t ev = nullptr;
-        if (hipEventCreate(&ev) != hipSuccess) return;
+        if (dev_event(ctx, &ev, hipEventDefault) != SVO_OK) return;      // (timing-enabled, unlike every other event of the context)
         ctx->ev_pool.push_back(ev);
     }
     hipEvent_t ev = ctx->ev_pool[ctx->ev_used++];
@@ -78,7 +78,7 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
         k.w = a.w; k.h = a.h; k.cw = ctx->bucket_w; k.ch = ctx->bucket_h; k.per_cell = ctx->bucket_keep;
         k.cols = (a.w + k.cw - 1) / k.cw; k.ncells = k.cols * ((a.h + k.ch - 1) / k.ch);
         k.cells_stride = (int64_t)4 * k.ncells;
-        k.cells = ctx->bucket_cells ? ctx->bucket_cells + (size_t)f0 * k.cells_stride : nullptr;
+        k.cells = ctx->bucket_cells.base ? (int *)ctx->bucket_cells.base + (size_t)f0 * k.cells_stride : nullptr;
         launch_fast_buckets(k, n_new, ctx->stream);
     }
     launch_fast_keep_strongest(a, n_new, ctx->cfg.fast_keep_strongest, ctx->stream);

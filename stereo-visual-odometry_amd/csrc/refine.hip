@@ -400,20 +400,27 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
 }
 
 // ---- the stage's device block: [records x (B + 1)][flags x (B + 1) x cap][stage-call X, xl, xr x cap]; item B is the stage call's
-static size_t ral(size_t v) { return (v + 255) / 256 * 256; }
-static size_t roff_flags(const svo_config &c) { return ral(sizeof(svo_refine_result) * ((size_t)c.max_batch + 1)); }
-static size_t roff_X(const svo_config &c) { return ral(roff_flags(c) + ((size_t)c.max_batch + 1) * (size_t)c.max_keypoints); }
-static size_t roff_xl(const svo_config &c) { return ral(roff_X(c) + sizeof(float) * 3 * (size_t)c.max_keypoints); }
-static size_t roff_xr(const svo_config &c) { return ral(roff_xl(c) + sizeof(float2) * (size_t)c.max_keypoints); }
-static size_t roff_end(const svo_config &c) { return ral(roff_xr(c) + sizeof(float2) * (size_t)c.max_keypoints); }
+struct RefineCut { size_t flags, X, xl, xr, end; };
+static RefineCut refine_cut(const svo_config &c)
+{
+    const size_t items = (size_t)c.max_batch + 1, cap = (size_t)c.max_keypoints;
+    BlockCut cut;
+    cut.add(sizeof(svo_refine_result) * items);             // the records, at the front
+    RefineCut r;
+    r.flags = cut.add(items * cap); r.X = cut.add(sizeof(float) * 3 * cap);
+    r.xl = cut.add(sizeof(float2) * cap); r.xr = cut.add(sizeof(float2) * cap); r.end = cut.total();
+    return r;
+}
 
 int refine_alloc(svo_ctx *ctx)
 {
     if (ctx->refine_buf) return SVO_OK;
     SVO_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = refine_cut(ctx->cfg).end;
     uint8_t *p = nullptr;
-    SVO_HIP(hipMalloc((void **)&p, roff_end(ctx->cfg)));
-    if (hipMemset(p, 0, roff_end(ctx->cfg)) != hipSuccess) { (void)hipFree(p); ctx->err = "hipMemset of the refinement block failed"; return SVO_ERR_HIP; }
+    if (dev_alloc(ctx, &p, bytes) != SVO_OK) return SVO_ERR_HIP;
+    // (a block that could not be cleared is not used: it stays the context's, to be freed with it)
+    if (hipMemset(p, 0, bytes) != hipSuccess) { ctx->err = "hipMemset of the refinement block failed"; return SVO_ERR_HIP; }
     ctx->refine_buf = p;
     return SVO_OK;
 }
@@ -430,7 +437,7 @@ static void refine_fill(const svo_ctx *ctx, RefineArgs &a, const double P1[12], 
     a.rounds = ctx->refine_rounds; a.iters = ctx->refine_iters; a.min_inliers = ctx->refine_min_inliers; a.sigma = ctx->refine_sigma;
     a.cap = ctx->cfg.max_keypoints;
     a.res = (svo_refine_result *)ctx->refine_buf;
-    a.flags = ctx->refine_buf + roff_flags(ctx->cfg);
+    a.flags = ctx->refine_buf + refine_cut(ctx->cfg).flags;
     a.flag_stride = ctx->cfg.max_keypoints;
 }
 
@@ -466,8 +473,9 @@ int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_lef
     a.flags = own_flags; a.flag_stride = 0; a.stride = 0; a.n_fixed = n; a.pnp = nullptr;
     for (int i = 0; i < 3; i++) { a.rvec0[i] = rvec0[i]; a.tvec0[i] = tvec0[i]; }
     if (mem == SVO_MEM_HOST) {
-        float *dX = (float *)(ctx->refine_buf + roff_X(c));
-        float2 *dl = (float2 *)(ctx->refine_buf + roff_xl(c)), *dr = (float2 *)(ctx->refine_buf + roff_xr(c));
+        const RefineCut o = refine_cut(c);
+        float *dX = (float *)(ctx->refine_buf + o.X);
+        float2 *dl = (float2 *)(ctx->refine_buf + o.xl), *dr = (float2 *)(ctx->refine_buf + o.xr);
         if (n > 0) {
             SVO_HIP(hipMemcpyAsync(dX, obj, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
             SVO_HIP(hipMemcpyAsync(dl, img_left, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -502,7 +510,7 @@ int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *
     SVO_ARG(active == nullptr || n <= cap, "flag capacity too small");     // nothing else has been written
     if (res) memcpy(res, h, sizeof(*res));
     if (active && n > 0) {
-        SVO_HIP(hipMemcpyAsync(active, ctx->refine_buf + roff_flags(c) + (size_t)pair * c.max_keypoints, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        SVO_HIP(hipMemcpyAsync(active, ctx->refine_buf + refine_cut(c).flags + (size_t)pair * c.max_keypoints, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         SVO_HIP(hipStreamSynchronize(ctx->stream));
     }
     return SVO_OK;

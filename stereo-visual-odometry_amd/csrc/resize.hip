@@ -334,20 +334,6 @@ extern "C" int svo_scale_projection(const double P[12], double inv_x, double inv
     return SVO_OK;
 }
 
-// grows one of svo_resize's two device scratch buffers (host sources / destinations)
-static int resize_scratch(svo_ctx *ctx, int k, size_t bytes)
-{
-    if (ctx->resize_scratch_bytes[k] >= bytes) return SVO_OK;
-    if (ctx->resize_scratch[k]) {
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-        SVO_HIP(hipFree(ctx->resize_scratch[k]));
-        ctx->resize_scratch[k] = nullptr; ctx->resize_scratch_bytes[k] = 0;
-    }
-    SVO_HIP(hipMalloc((void **)&ctx->resize_scratch[k], bytes));
-    ctx->resize_scratch_bytes[k] = bytes;
-    return SVO_OK;
-}
-
 extern "C" int svo_resize(svo_ctx *ctx, const uint8_t *src, int sw, int sh, int spitch, int64_t sstride,
                           uint8_t *dst, int dw, int dh, int dpitch, int64_t dstride, int n_frames,
                           int interp, double fx, double fy, int mem)
@@ -367,16 +353,17 @@ extern "C" int svo_resize(svo_ctx *ctx, const uint8_t *src, int sw, int sh, int 
     // host images: tight 16-byte-aligned device copies of both sides; the destination's bytes beyond dw are never written
     const int sp = (sw + 15) & ~15, dp = (dw + 15) & ~15;
     const size_t sbytes = (size_t)sp * sh, dbytes = (size_t)dp * dh;
-    if ((rc = resize_scratch(ctx, 0, sbytes * (size_t)n_frames)) != SVO_OK) return rc;
-    if ((rc = resize_scratch(ctx, 1, dbytes * (size_t)n_frames)) != SVO_OK) return rc;
+    if ((rc = dev_reserve(ctx, &ctx->resize_scratch[0], sbytes * (size_t)n_frames)) != SVO_OK) return rc;
+    if ((rc = dev_reserve(ctx, &ctx->resize_scratch[1], dbytes * (size_t)n_frames)) != SVO_OK) return rc;
+    uint8_t *d_src = ctx->resize_scratch[0].base, *d_dst = ctx->resize_scratch[1].base;
     for (int f = 0; f < n_frames; f++)
-        SVO_HIP(hipMemcpy2DAsync(ctx->resize_scratch[0] + f * sbytes, (size_t)sp, src + (n_frames > 1 ? f * sstride : 0), (size_t)spitch,
+        SVO_HIP(hipMemcpy2DAsync(d_src + f * sbytes, (size_t)sp, src + (n_frames > 1 ? f * sstride : 0), (size_t)spitch,
                                  (size_t)sw, (size_t)sh, hipMemcpyHostToDevice, ctx->stream));
-    rc = resize_launch(ctx, tab, ctx->resize_scratch[0], nullptr, sp, (int64_t)sbytes, ctx->resize_scratch[1], nullptr, dp,
+    rc = resize_launch(ctx, tab, d_src, nullptr, sp, (int64_t)sbytes, d_dst, nullptr, dp,
                        (int64_t)dbytes, n_frames, ctx->stream);
     if (rc) return rc;
     for (int f = 0; f < n_frames; f++)
-        SVO_HIP(hipMemcpy2DAsync(dst + (n_frames > 1 ? f * dstride : 0), (size_t)dpitch, ctx->resize_scratch[1] + f * dbytes, (size_t)dp,
+        SVO_HIP(hipMemcpy2DAsync(dst + (n_frames > 1 ? f * dstride : 0), (size_t)dpitch, d_dst + f * dbytes, (size_t)dp,
                                  (size_t)dw, (size_t)dh, hipMemcpyDeviceToHost, ctx->stream));
     SVO_HIP(hipStreamSynchronize(ctx->stream));
     return SVO_OK;

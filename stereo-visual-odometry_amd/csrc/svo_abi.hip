@@ -11,8 +11,6 @@
 
 using namespace svo;
 
-static int align_up(int v, int a) { return (v + a - 1) / a * a; }
-
 namespace svo {
 int dev_alloc_raw(svo_ctx *ctx, void **out, size_t bytes)
 {
@@ -20,7 +18,7 @@ int dev_alloc_raw(svo_ctx *ctx, void **out, size_t bytes)
     if (bytes == 0) bytes = 1;
     if (ctx->arena.planning) {
         ctx->arena.plan.emplace_back(out, ctx->arena.planned);
-        ctx->arena.planned += (bytes + 255) / 256 * 256;
+        ctx->arena.planned += align_up(bytes, kDevAlign);
         return SVO_OK;
     }
     SVO_HIP(hipMalloc(out, bytes));
@@ -47,14 +45,48 @@ static int dev_commit(svo_ctx *ctx)
     return SVO_OK;
 }
 
+int dev_reserve(svo_ctx *ctx, DevScratch *s, size_t bytes)
+{
+    if (s->base && bytes <= s->bytes) return SVO_OK;
+    uint8_t *grown = nullptr;
+    SVO_HIP(hipMalloc((void **)&grown, bytes ? bytes : 1));
+    uint8_t *old = s->base;
+    if (!old) ctx->arena.scratch.push_back(s);                 // its first block: the context frees it from now on
+    s->base = grown; s->bytes = bytes;
+    if (old) (void)hipFree(old);
+    return SVO_OK;
+}
+
+int dev_event(svo_ctx *ctx, hipEvent_t *ev, unsigned flags)
+{
+    if (*ev) return SVO_OK;
+    SVO_HIP(hipEventCreateWithFlags(ev, flags));
+    ctx->arena.events.push_back(*ev);
+    return SVO_OK;
+}
+
+int dev_stream(svo_ctx *ctx, hipStream_t *st)
+{
+    if (*st) return SVO_OK;
+    SVO_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    ctx->arena.streams.push_back(*st);
+    return SVO_OK;
+}
+
 static void dev_release(svo_ctx *ctx)
 {
-    for (void *p : ctx->arena.extra) if (p) (void)hipFree(p);
-    ctx->arena.extra.clear();
-    if (ctx->arena.base) (void)hipFree(ctx->arena.base);
-    ctx->arena.base = nullptr;
+    DevArena &a = ctx->arena;
+    for (DevScratch *s : a.scratch) { (void)hipFree(s->base); *s = DevScratch(); }
+    a.scratch.clear();
+    for (void *p : a.extra) if (p) (void)hipFree(p);
+    a.extra.clear();
+    if (a.base) (void)hipFree(a.base);
+    a.base = nullptr;
 }
 }  // namespace svo
+
+static int frame_buffers(svo_ctx *ctx);              // the lazily made sets of an online-sized context, which svo_create makes
+static int async_ring(svo_ctx *ctx);                 // for a batch context
 
 constexpr int kMaxFrameSide = 16384;                // svo_create refuses larger frames
 // the LK kernels form tile offsets with 24-bit multiplies (lk_common.h, stage_src): the widest accepted pitch fits
@@ -77,7 +109,7 @@ static void make_geom(int w, int h, PyrGeom *g)
         g->pitch[l] = align_up(lw + 2 * kPad, 64);
         g->origin[l] = off + (int64_t)kPad * g->pitch[l] + kPad;
         off += (int64_t)g->pitch[l] * (lh + 2 * kPad);
-        off = (off + 255) / 256 * 256;
+        off = (int64_t)align_up((size_t)off, kDevAlign);
         g->nlevels = l + 1;
     }
     g->slot_bytes = off;
@@ -129,31 +161,13 @@ extern "C" void svo_default_config(svo_config *cfg, int width, int height)
 
 static void free_all(svo_ctx *c)
 {
-    dev_release(c);                                   // every device buffer: the arena + the lazy extras
-    for (int k = 0; k < 2; k++) if (c->resize_scratch[k]) (void)hipFree(c->resize_scratch[k]);
-    if (c->ingest.src_stage) (void)hipFree(c->ingest.src_stage);
-    if (c->bucket_cells) (void)hipFree(c->bucket_cells);
-    if (c->bucket_stage) (void)hipFree(c->bucket_stage);
-    if (c->gftt_fused.base) (void)hipFree(c->gftt_fused.base);
-    if (c->gftt_stage.base) (void)hipFree(c->gftt_stage.base);
-    if (c->refine_buf) (void)hipFree(c->refine_buf);
-    if (c->ev_front) (void)hipEventDestroy(c->ev_front);
-    if (c->ev_back) (void)hipEventDestroy(c->ev_back);
-    if (c->ev_order) (void)hipEventDestroy(c->ev_order);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-    for (int k = 0; k < 2; k++) {
-        if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
-        if (c->ev_fb_free[k]) (void)hipEventDestroy(c->ev_fb_free[k]);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (int k = 0; k < 2; k++)
-        if (c->ev_async[k]) (void)hipEventDestroy(c->ev_async[k]);
-    if (c->fetch_stream) (void)hipStreamDestroy(c->fetch_stream);
+    dev_release(c);                                   // every device buffer: the arena, the lazy extras, the growable scratch
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
-    for (int k = 0; k < 2; k++) if (c->ev_stage[k]) (void)hipEventDestroy(c->ev_stage[k]);
-    for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    DevArena &a = c->arena;
+    for (hipEvent_t e : a.events) (void)hipEventDestroy(e);
+    for (size_t k = a.streams.size(); k-- > 0;) (void)hipStreamDestroy(a.streams[k]);      // the context's own stream last
+    a.events.clear(); a.streams.clear();
 }
 
 // SVO_TIMING=1: milliseconds of svo_create's phases on stderr (where a short run's start-up goes)
@@ -201,9 +215,10 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
     }
     PHASE("hipGetDeviceCount (HIP runtime start)");
     auto fail = [&](int code) { free_all(ctx); delete ctx; return code; };
-#define CK(call) do { if ((call) != hipSuccess) { fprintf(stderr, "svo_create: %s failed\n", #call); return fail(SVO_ERR_HIP); } } while (0)
+    // (HIP calls and the context's own helpers alike: hipSuccess and SVO_OK are both 0)
+#define CK(call) do { if ((call) != 0) { fprintf(stderr, "svo_create: %s failed\n", #call); return fail(SVO_ERR_HIP); } } while (0)
     CK(hipSetDevice(device));
-    CK(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+    CK(dev_stream(ctx, &ctx->own_stream));
     ctx->stream = ctx->own_stream;
     PHASE("hipSetDevice + stream");
     make_geom(cfg->width, cfg->height, &ctx->geom);
@@ -263,22 +278,16 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
     if (dev_commit(ctx) != SVO_OK) { fprintf(stderr, "svo_create: device memory (%zu MB): %s\n", ctx->arena.planned >> 20, ctx->err.c_str()); return fail(SVO_ERR_HIP); }
     PHASE("one device allocation + deferred initialisation");
     CK(hipHostMalloc(&ctx->h_stage, (size_t)ctx->stage_pitch * h * 2, hipHostMallocDefault));
-    for (int k = 0; k < 2; k++) CK(hipEventCreateWithFlags(&ctx->ev_stage[k], hipEventDisableTiming));
+    for (int k = 0; k < 2; k++) CK(dev_event(ctx, &ctx->ev_stage[k]));
     // (a high-priority side stream was measured in round 6: no difference, 5.80 against 5.80 ms per ORB step and 14.32 against
     // 14.34 per LK step -- what holds a pose-stage kernel back beside the next front end is free LDS and wave slots on a CU, not
     // the queue's place at the dispatcher)
-    CK(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-    CK(hipEventCreateWithFlags(&ctx->ev_front, hipEventDisableTiming));
-    CK(hipEventCreateWithFlags(&ctx->ev_back, hipEventDisableTiming));
-    if (B > 1) {
-        for (int k = 0; k < 2; k++) {
-            CK(hipEventCreateWithFlags(&ctx->ev_up[k], hipEventDisableTiming));
-            CK(hipEventCreateWithFlags(&ctx->ev_fb_free[k], hipEventDisableTiming));
-            CK(hipEventCreateWithFlags(&ctx->ev_async[k], hipEventDisableTiming));
-        }
-        CK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        CK(hipStreamCreateWithFlags(&ctx->fetch_stream, hipStreamNonBlocking));
-        ctx->async_ready = true;
+    CK(dev_stream(ctx, &ctx->side_stream));
+    CK(dev_event(ctx, &ctx->ev_front));
+    CK(dev_event(ctx, &ctx->ev_back));
+    if (B > 1) {                                      // (their device memory came with the arena)
+        CK(frame_buffers(ctx));
+        CK(async_ring(ctx));
     }
     ctx->h_pinned_bytes = kPinnedRecords + sizeof(svo_step_result) * (size_t)B +
                           (size_t)cap * (sizeof(svo_keypoint) + 32) + sizeof(int) * 64;
@@ -347,7 +356,7 @@ extern "C" int svo_wait_stream(svo_ctx *ctx, void *hip_stream)
     hipStream_t other = (hipStream_t)hip_stream;
     if (other == ctx->stream) return SVO_OK;                     // same queue: already ordered
     SVO_HIP(hipSetDevice(ctx->device));
-    if (!ctx->ev_order) SVO_HIP(hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
+    if (dev_event(ctx, &ctx->ev_order) != SVO_OK) return SVO_ERR_HIP;
     SVO_HIP(hipEventRecord(ctx->ev_order, other));
     SVO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_order, 0));
     return SVO_OK;
@@ -361,7 +370,7 @@ extern "C" int svo_signal_stream(svo_ctx *ctx, void *hip_stream)
     // the pose stage of an overlap-mode batch ends on the side stream: its event first (kept pending for the context's own waits)
     if (ctx->back_pending && other != ctx->side_stream) SVO_HIP(hipStreamWaitEvent(other, ctx->ev_back, 0));
     if (other == ctx->stream) return SVO_OK;
-    if (!ctx->ev_order) SVO_HIP(hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
+    if (dev_event(ctx, &ctx->ev_order) != SVO_OK) return SVO_ERR_HIP;
     SVO_HIP(hipEventRecord(ctx->ev_order, ctx->stream));
     SVO_HIP(hipStreamWaitEvent(other, ctx->ev_order, 0));
     return SVO_OK;
@@ -375,7 +384,7 @@ extern "C" int svo_signal_stream_inputs(svo_ctx *ctx, void *hip_stream)
     hipStream_t other = (hipStream_t)hip_stream;
     if (other == ctx->stream) return SVO_OK;
     SVO_HIP(hipSetDevice(ctx->device));
-    if (!ctx->ev_order) SVO_HIP(hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
+    if (dev_event(ctx, &ctx->ev_order) != SVO_OK) return SVO_ERR_HIP;
     SVO_HIP(hipEventRecord(ctx->ev_order, ctx->stream));
     SVO_HIP(hipStreamWaitEvent(other, ctx->ev_order, 0));
     return SVO_OK;
@@ -837,23 +846,15 @@ static int ingest_stage_host(svo_ctx *ctx, const uint8_t **left, const uint8_t *
 {
     Ingest &g = ctx->ingest;
     const size_t fbytes = src_frame_bytes(ctx);
-    if (g.src_stage_frames < n) {
-        if (g.src_stage) {
-            SVO_HIP(hipStreamSynchronize(ctx->stream));
-            SVO_HIP(hipFree(g.src_stage));
-            g.src_stage = nullptr; g.src_stage_frames = 0;
-        }
-        SVO_HIP(hipMalloc((void **)&g.src_stage, 2 * fbytes * (size_t)n));
-        g.src_stage_frames = n;
-    }
+    if (dev_reserve(ctx, &g.src_stage, 2 * fbytes * (size_t)n) != SVO_OK) return SVO_ERR_HIP;
     const uint8_t *src[2] = {*left, *right};
     for (int eye = 0; eye < 2; eye++) {
-        const int rc = copy_host_frames(ctx, g.src_stage + (size_t)eye * fbytes * (size_t)n, g.spitch, (int64_t)fbytes, src[eye], *pitch,
+        const int rc = copy_host_frames(ctx, g.src_stage.base + (size_t)eye * fbytes * (size_t)n, g.spitch, (int64_t)fbytes, src[eye], *pitch,
                                         *frame_stride, g.sw, g.sh, n, ctx->stream);
         if (rc) return rc;
     }
     SVO_HIP(hipStreamSynchronize(ctx->stream));
-    *left = g.src_stage; *right = g.src_stage + fbytes * (size_t)n;
+    *left = g.src_stage.base; *right = g.src_stage.base + fbytes * (size_t)n;
     *pitch = g.spitch; *frame_stride = (int64_t)fbytes;
     return SVO_OK;
 }
@@ -943,14 +944,24 @@ static int frame_buffers(svo_ctx *ctx)
 {
     if (ctx->copy_stream) return SVO_OK;
     const size_t per_cam = work_frame_bytes(ctx) * frame_slots(ctx);
-    // every resource behind its own guard: a call that failed half way leaves what it made for the next attempt
-    // (copy_stream, made last, is what marks the set complete)
+    // a call that failed half way leaves what it made for the next attempt (copy_stream, made last, is what marks the set complete)
     for (int k = 0; k < 2; k++) {
         if (!ctx->fb[k] && dev_alloc(ctx, &ctx->fb[k], 2 * per_cam) != SVO_OK) return SVO_ERR_HIP;
-        if (!ctx->ev_up[k]) SVO_HIP(hipEventCreateWithFlags(&ctx->ev_up[k], hipEventDisableTiming));
-        if (!ctx->ev_fb_free[k]) SVO_HIP(hipEventCreateWithFlags(&ctx->ev_fb_free[k], hipEventDisableTiming));
+        if (dev_event(ctx, &ctx->ev_up[k]) != SVO_OK || dev_event(ctx, &ctx->ev_fb_free[k]) != SVO_OK) return SVO_ERR_HIP;
     }
-    SVO_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    return dev_stream(ctx, &ctx->copy_stream);
+}
+
+// svo_track_uploaded_async's two record buffers, their events and the stream that fetches them
+static int async_ring(svo_ctx *ctx)
+{
+    if (ctx->async_ready) return SVO_OK;
+    for (int k = 0; k < 2; k++) {
+        if (!ctx->d_async[k] && dev_alloc(ctx, &ctx->d_async[k], sizeof(svo_step_result) * (size_t)ctx->cfg.max_batch) != SVO_OK) return SVO_ERR_HIP;
+        if (dev_event(ctx, &ctx->ev_async[k]) != SVO_OK) return SVO_ERR_HIP;
+    }
+    if (dev_stream(ctx, &ctx->fetch_stream) != SVO_OK) return SVO_ERR_HIP;
+    ctx->async_ready = true;
     return SVO_OK;
 }
 
@@ -1053,14 +1064,7 @@ extern "C" int svo_track_uploaded_async(svo_ctx *ctx, int buf, int n_frames, con
     SVO_ARG(ctx->async_tail - ctx->async_head < 2, "two batches are already outstanding: collect one first");
     SVO_HIP(hipSetDevice(ctx->device));
     const int r = (int)(ctx->async_tail & 1), n_pairs = n_frames - 1;
-    if (!ctx->async_ready) {                       // an online-sized context (max_batch 1) sets the ring up on first use
-        for (int k = 0; k < 2; k++) {
-            if (!ctx->d_async[k] && dev_alloc(ctx, &ctx->d_async[k], sizeof(svo_step_result) * (size_t)ctx->cfg.max_batch) != SVO_OK) return SVO_ERR_HIP;
-            if (!ctx->ev_async[k]) SVO_HIP(hipEventCreateWithFlags(&ctx->ev_async[k], hipEventDisableTiming));
-        }
-        if (!ctx->fetch_stream) SVO_HIP(hipStreamCreateWithFlags(&ctx->fetch_stream, hipStreamNonBlocking));
-        ctx->async_ready = true;
-    }
+    if (async_ring(ctx) != SVO_OK) return SVO_ERR_HIP;       // an online-sized context (max_batch 1) sets the ring up on first use
     SVO_ARG((continue_chain & ~(SVO_CONTINUE_CHAIN | SVO_CONTINUE_CARRY_FRAME)) == 0, "unknown continue_chain bits");
     SVO_ARG(!(continue_chain & SVO_CONTINUE_CARRY_FRAME) || (continue_chain & SVO_CONTINUE_CHAIN),
             "SVO_CONTINUE_CARRY_FRAME without SVO_CONTINUE_CHAIN: the carried frame belongs to the chain being continued");
@@ -1392,14 +1396,8 @@ extern "C" int svo_set_fast_buckets(svo_ctx *ctx, int cell_w, int cell_h, int pe
     SVO_HIP(hipSetDevice(ctx->device));
     if (ncells > fast_bucket_lds_cells()) {
         // the per-cell words of such a grid live in device memory: every image slot of the context its own
-        const size_t bytes = sizeof(int) * 4 * (size_t)ncells * (size_t)ctx->n_img;
-        if (bytes > ctx->bucket_cells_bytes) {
-            if (ctx->bucket_cells) SVO_HIP(hipFree(ctx->bucket_cells));      // (waits for the launches that still use it)
-            ctx->bucket_cells = nullptr; ctx->bucket_cells_bytes = 0;
-            ctx->bucket_keep = 0;
-            SVO_HIP(hipMalloc((void **)&ctx->bucket_cells, bytes));
-            ctx->bucket_cells_bytes = bytes;
-        }
+        // (a call that cannot get them leaves the buckets as they were)
+        if (dev_reserve(ctx, &ctx->bucket_cells, sizeof(int) * 4 * (size_t)ncells * (size_t)ctx->n_img) != SVO_OK) return SVO_ERR_HIP;
     }
     ctx->bucket_w = cell_w; ctx->bucket_h = cell_h; ctx->bucket_keep = per_cell;
     return SVO_OK;
@@ -1426,19 +1424,14 @@ extern "C" int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, i
     const int64_t ncells = bucket_cell_count(width, height, cell_w, cell_h);
     SVO_ARG(ncells <= kMaxBucketCells, "more than 16384 cells");
     SVO_HIP(hipSetDevice(ctx->device));
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const bool host = mem == SVO_MEM_HOST, dev_cells = ncells > fast_bucket_lds_cells();
-    const size_t o_xy = 256, o_resp = o_xy + up(sizeof(float2) * (size_t)n), o_cells = o_resp + up(sizeof(float) * (size_t)n),
-                 o_in = o_cells + (dev_cells ? up(sizeof(int) * 4 * (size_t)ncells) : 0),
-                 o_out = o_in + (host ? up(sizeof(svo_keypoint) * (size_t)n) : 0),
-                 bytes = o_out + (host ? up(sizeof(svo_keypoint) * (size_t)n) : 0);
-    if (bytes > ctx->bucket_stage_bytes) {
-        if (ctx->bucket_stage) SVO_HIP(hipFree(ctx->bucket_stage));
-        ctx->bucket_stage = nullptr; ctx->bucket_stage_bytes = 0;
-        SVO_HIP(hipMalloc((void **)&ctx->bucket_stage, bytes));
-        ctx->bucket_stage_bytes = bytes;
-    }
-    uint8_t *s = ctx->bucket_stage;
+    BlockCut cut;
+    cut.add(256);                                           // the two counts
+    const size_t o_xy = cut.add(sizeof(float2) * (size_t)n), o_resp = cut.add(sizeof(float) * (size_t)n),
+                 o_cells = cut.add(dev_cells ? sizeof(int) * 4 * (size_t)ncells : 0),
+                 o_in = cut.add(host ? sizeof(svo_keypoint) * (size_t)n : 0), o_out = cut.add(host ? sizeof(svo_keypoint) * (size_t)n : 0);
+    if (dev_reserve(ctx, &ctx->bucket_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+    uint8_t *s = ctx->bucket_stage.base;
     int *d_n = (int *)s, *d_nout = host ? (int *)s + 1 : n_out;
     float2 *xy = (float2 *)(s + o_xy);
     float *resp = (float *)(s + o_resp);
@@ -1471,28 +1464,21 @@ extern "C" int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, i
 static int gftt_cell_of(double min_distance) { return min_distance >= 1.0 ? (int)nearbyint(min_distance) : 0; }   // cvRound: half to even
 
 // Scratch for n images of w x h pixels with `cap` candidates each and a grid of ncells cells (+ `extra` bytes at the end,
-// returned in *extra_at): allocated when it has to grow (that call waits for the device), cut up on every call.
+// returned in *extra_at): reserved (a call that has to grow it waits for the device), cut up on every call.
 // with_lists false: the per-image words only (svo_min_eigen_map writes its map where the caller says).
 static int gftt_plan(svo_ctx *ctx, GfttBuf &g, int w, int h, int n, int cap, int64_t ncells, size_t extra, uint8_t **extra_at,
                      bool with_lists = true)
 {
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     int64_t ks = 64;
     while (ks < cap) ks <<= 1;
     const int mpitch = align_up(w, 64);
     const bool dev_cells = ncells > gftt_lds_cells();
-    const size_t o_max = 0, o_cnt = up(sizeof(unsigned) * (size_t)n), o_map = o_cnt + up(sizeof(int) * (size_t)n),
-                 o_keys = o_map + (with_lists ? up(sizeof(float) * (size_t)mpitch * h * n) : 0),
-                 o_cells = o_keys + (with_lists ? up(sizeof(unsigned long long) * (size_t)ks * n) : 0),
-                 o_extra = o_cells + (dev_cells ? up(sizeof(int) * 4 * (size_t)ncells * n) : 0), bytes = o_extra + up(extra);
-    if (bytes > g.bytes) {
-        // the larger block first: a call that cannot get it leaves the scratch, and with it the context, as it was
-        uint8_t *grown = nullptr;
-        SVO_HIP(hipMalloc((void **)&grown, bytes));
-        uint8_t *old = g.base;
-        g.base = grown; g.bytes = bytes;
-        if (old) (void)hipFree(old);                           // (waits for the launches that still use it; the new block is in place either way)
-    }
+    BlockCut cut;
+    const size_t o_max = cut.add(sizeof(unsigned) * (size_t)n), o_cnt = cut.add(sizeof(int) * (size_t)n),
+                 o_map = cut.add(with_lists ? sizeof(float) * (size_t)mpitch * h * n : 0),
+                 o_keys = cut.add(with_lists ? sizeof(unsigned long long) * (size_t)ks * n : 0),
+                 o_cells = cut.add(dev_cells ? sizeof(int) * 4 * (size_t)ncells * n : 0), o_extra = cut.add(extra);
+    if (dev_reserve(ctx, &g, cut.total()) != SVO_OK) return SVO_ERR_HIP;
     g.maxkey = (unsigned *)(g.base + o_max); g.n_cand = (int *)(g.base + o_cnt);
     g.map = with_lists ? (float *)(g.base + o_map) : nullptr; g.mpitch = mpitch; g.map_stride = (int64_t)mpitch * h;
     g.keys = with_lists ? (unsigned long long *)(g.base + o_keys) : nullptr; g.keys_stride = ks;
@@ -1617,16 +1603,16 @@ extern "C" int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int 
     const int64_t ncells = gftt_cell_count(width, height, min_distance);
     SVO_ARG(ncells <= kMaxBucketCells, "min_distance gives more than 16384 grid cells");
     SVO_HIP(hipSetDevice(ctx->device));
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const bool host = mem == SVO_MEM_HOST;
     const int dpitch = align_up(width, 256);
     const size_t ncap = (size_t)(cap > 0 ? cap : 1);
-    const size_t o_n = 0, o_xy = 256, o_resp = o_xy + up(sizeof(float2) * ncap), o_str = o_resp + up(sizeof(float) * ncap),
-                 o_rec = o_str + up(sizeof(float) * ncap), o_img = o_rec + (host ? up(sizeof(svo_keypoint) * ncap) : 0),
-                 extra = o_img + (host ? (size_t)dpitch * height : 0);
+    BlockCut cut;                                           // the stage call's own ranges, behind the detector's scratch
+    const size_t o_n = cut.add(256), o_xy = cut.add(sizeof(float2) * ncap), o_resp = cut.add(sizeof(float) * ncap),
+                 o_str = cut.add(sizeof(float) * ncap), o_rec = cut.add(host ? sizeof(svo_keypoint) * ncap : 0),
+                 o_img = cut.add(host ? (size_t)dpitch * height : 0);
     uint8_t *x = nullptr;
     GfttBuf &g = ctx->gftt_stage;
-    int rc = gftt_plan(ctx, g, width, height, 1, cap, ncells, extra, &x);
+    int rc = gftt_plan(ctx, g, width, height, 1, cap, ncells, cut.total(), &x);
     if (rc) return rc;
     GfttArgs a{};
     gftt_params(a, g, width, height, cap, max_corners, quality_level, min_distance);

@@ -6,13 +6,26 @@
 #include <utility>
 #include <vector>
 #include "../../include/svo_abi.h"
+#include "block_cut.h"
 #include "svo_kernels.h"
 
-// Every device buffer of a context comes out of ONE hipMalloc (svo_create: ~30 separate allocations were a fifth of a
-// short run's start-up): while `planning`, dev_alloc only records (where the pointer goes, size); dev_commit allocates
-// the sum, hands the pointers out and runs the initialisations that were waiting for them (dev_defer).  Allocations made
-// after the commit (lazy paths: ORB buffers of an LK context, frame buffers of an online context) are separate and
-// remembered in `extra`.
+// A block of device memory that appears when a feature is first used and grows with the largest request: dev_reserve.
+struct DevScratch {
+    uint8_t *base = nullptr;
+    size_t bytes = 0;
+};
+
+// What a context owns on the device, all of it released by free_all() (svo_abi.hip) and by nothing else.  Device memory has
+// three lifetimes, and one function each:
+//   - planned in svo_create: dev_alloc while `planning` only records (where the pointer goes, size); dev_commit makes ONE
+//     hipMalloc of the sum (~30 separate allocations were a fifth of a short run's start-up), hands the pointers out and
+//     runs the initialisations that were waiting for them (dev_defer);
+//   - made on first use at a fixed size (ORB buffers of an LK context, frame buffers of an online-sized context, stream
+//     stores, resize tables, matcher and refinement blocks): dev_alloc after the commit, an allocation of its own,
+//     remembered in `extra`;
+//   - made on first use and growable (the scratch of stage calls, staging of host frames, per-cell words): dev_reserve on a
+//     DevScratch, remembered in `scratch` from its first allocation on.
+// Events and streams are made by dev_event / dev_stream, in svo_create or on first use, and remembered in `events` / `streams`.
 struct DevArena {
     char *base = nullptr;
     size_t planned = 0;
@@ -20,6 +33,9 @@ struct DevArena {
     std::vector<std::pair<void **, size_t>> plan;
     std::vector<std::function<int()>> after;
     std::vector<void *> extra;
+    std::vector<DevScratch *> scratch;
+    std::vector<hipEvent_t> events;
+    std::vector<hipStream_t> streams;      // in the order they were made: the context's own stream first
 };
 
 // A stream set (svo_streams_create): n independent live stereo streams of one context.  What a stream keeps in HBM between
@@ -55,16 +71,14 @@ struct Ingest {
     int sw = 0, sh = 0, tab = -1;
     int spitch = 0;                   // row pitch of the source-size staging (16-byte aligned)
     uint8_t *work = nullptr;          // working-size frames: 2 eyes x (max_batch + 1) slots, stage_pitch rows
-    uint8_t *src_stage = nullptr;     // source-size staging of HOST frames (svo_ingest_add_frame / _streams_step), grown on demand
-    int src_stage_frames = 0;
+    DevScratch src_stage;             // source-size staging of HOST frames (svo_ingest_add_frame / _streams_step): 2 eyes x the call's frames
     uint8_t *up_stage[2] = {nullptr, nullptr};   // source-size staging behind fb[0] / fb[1] (svo_ingest_upload_frames_at), first use
 };
 
-// Scratch of the Shi-Tomasi detector (gftt.hip) for n images of w x h pixels: ONE device allocation cut into the candidate
+// Scratch of the Shi-Tomasi detector (gftt.hip) for n images of w x h pixels: ONE growable block cut into the candidate
 // map, the per-image words, the candidate keys, the cell words of a grid too large for LDS and (stage calls) the staged image
 // and the output lists.
-struct GfttBuf {
-    uint8_t *base = nullptr; size_t bytes = 0;
+struct GfttBuf : DevScratch {
     float *map = nullptr; int mpitch = 0; int64_t map_stride = 0;
     unsigned *maxkey = nullptr; int *n_cand = nullptr;
     unsigned long long *keys = nullptr; int64_t keys_stride = 0;
@@ -168,15 +182,12 @@ struct svo_ctx {
     StreamSet streams;
     // ---- cv::resize (svo_resize) and the ingest stage (svo_ingest_*); nothing is allocated until they are used
     std::vector<ResizeTab> resize_tabs;
-    uint8_t *resize_scratch[2] = {nullptr, nullptr};     // device copies of svo_resize's HOST source / destination
-    size_t resize_scratch_bytes[2] = {0, 0};
+    DevScratch resize_scratch[2];                        // device copies of svo_resize's HOST source / destination
     Ingest ingest;
     // ---- FAST corner buckets (svo_set_fast_buckets; off and nothing allocated until then)
     int bucket_w = 0, bucket_h = 0, bucket_keep = 0;     // cell size in pixels, corners kept per cell (0: off)
-    int *bucket_cells = nullptr;                         // per-cell words of grids too large for LDS: 4 ints x cells x n_img
-    size_t bucket_cells_bytes = 0;
-    uint8_t *bucket_stage = nullptr;                     // svo_bucket_corners: the caller's list as structure of arrays (+ its cells)
-    size_t bucket_stage_bytes = 0;
+    DevScratch bucket_cells;                             // per-cell words of grids too large for LDS: 4 ints x cells x n_img
+    DevScratch bucket_stage;                             // svo_bucket_corners: the caller's list as structure of arrays (+ its cells)
     // ---- Shi-Tomasi detector (svo_set_lk_detector / svo_gftt_detect; off and nothing allocated until then)
     int lk_detector = SVO_DETECTOR_FAST;
     int gftt_max_corners = 0;
@@ -191,7 +202,7 @@ struct svo_ctx {
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
     bool timing = false;
-    std::vector<hipEvent_t> ev_pool;                               // every event ever created
+    std::vector<hipEvent_t> ev_pool;                               // every timing event made so far, reused after each query
     size_t ev_used = 0;
     std::vector<std::pair<const char *, hipEvent_t>> marks;        // log since the last query
     std::vector<std::pair<const char *, float>> last_times;
@@ -213,10 +224,17 @@ struct svo_ctx {
 
 namespace svo {
 constexpr size_t kPinnedRecords = 4096;                 // byte offset of the step records in svo_ctx::h_pinned
-// svo_abi.hip: the context's device memory
+// svo_abi.hip: the context's device memory, events and streams (DevArena)
 int dev_alloc_raw(svo_ctx *ctx, void **out, size_t bytes);
 template <class T> inline int dev_alloc(svo_ctx *ctx, T **out, size_t bytes) { return dev_alloc_raw(ctx, (void **)out, bytes); }
 int dev_defer(svo_ctx *ctx, std::function<int()> fn);      // runs fn now, or after dev_commit while the arena is being planned
+// s holds at least `bytes` afterwards.  Growing allocates the larger block first, swaps it in and frees the old one (hipFree
+// waits for the launches that still read it; its contents are NOT carried over): a refused growth leaves s, and with it the
+// context, as it was, with ctx->err set.
+int dev_reserve(svo_ctx *ctx, DevScratch *s, size_t bytes);
+// make *ev / *st unless it exists already
+int dev_event(svo_ctx *ctx, hipEvent_t *ev, unsigned flags = hipEventDisableTiming);
+int dev_stream(svo_ctx *ctx, hipStream_t *st);
 // geometry.hip
 int geom_workspace_bytes(const svo_config &cfg, int n_items, size_t *bytes);
 int geom_workspace_init(svo_ctx *ctx);
@@ -238,7 +256,7 @@ int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_lef
 int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out);
 // orb.hip
 int orb_alloc(svo_ctx *ctx);
-void orb_free(svo_ctx *ctx);
+int orb_max_keypoints(const svo_ctx *ctx);             // what one image holds at most: the level quotas + 8 each, capped at orb_kp_cap
 void timing_mark(svo_ctx *ctx, const char *name);     // HIP event on the context's stream when timing is enabled
 const uint8_t *pnp_inlier_mask(const svo_ctx *ctx);
 int stage_chain_relative(svo_ctx *ctx, const double *T, const int32_t *ok, int n, const double *pose0_host, double *out, int mem);
