@@ -17,7 +17,7 @@
 //   chain_kernel       : frame_pose_ *= T^-1 over the batch, skipping failed steps.
 #include <cstring>
 #include <cstdlib>
-#include "svo_ctx.h"
+#include "abi_io.h"
 #include "geom_device.h"
 
 namespace svo {
@@ -1021,27 +1021,25 @@ int stage_chain_relative(svo_ctx *ctx, const double *T, const int32_t *ok, int n
     if (n == 0) return SVO_OK;
     Pose16 p0;                                     // travels as a kernel argument: no copy, no allocation
     for (int q = 0; q < 16; q++) p0.m[q] = pose0_host ? pose0_host[q] : (q % 5 == 0 ? 1.0 : 0.0);
-    if (mem == SVO_MEM_DEVICE) {                   // stream-ordered, nothing else to do
-        hipLaunchKernelGGL(chain_relative_kernel, dim3(1), dim3(64), 0, ctx->stream, T, (const int *)ok, n, p0, out);
-        SVO_HIP(hipGetLastError());
-        return SVO_OK;
-    }
-    // host operands: temporaries released on every exit path
+    // host operands: temporaries released on every exit path (device operands: stream-ordered, nothing allocated or waited for)
     struct DevBuf {
         void *p = nullptr;
         ~DevBuf() { if (p) (void)hipFree(p); }
     } bT, bOut, bOk;
-    SVO_HIP(hipMalloc(&bT.p, sizeof(double) * 16 * (size_t)n));
-    SVO_HIP(hipMalloc(&bOut.p, sizeof(double) * 16 * (size_t)n));
-    SVO_HIP(hipMalloc(&bOk.p, sizeof(int) * (size_t)n));
-    SVO_HIP(hipMemcpyAsync(bT.p, T, sizeof(double) * 16 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    SVO_HIP(hipMemcpyAsync(bOk.p, ok, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(chain_relative_kernel, dim3(1), dim3(64), 0, ctx->stream, (const double *)bT.p, (const int *)bOk.p, n, p0,
-                       (double *)bOut.p);
+    if (mem == SVO_MEM_HOST) {
+        SVO_HIP(hipMalloc(&bT.p, sizeof(double) * 16 * (size_t)n));
+        SVO_HIP(hipMalloc(&bOut.p, sizeof(double) * 16 * (size_t)n));
+        SVO_HIP(hipMalloc(&bOk.p, sizeof(int) * (size_t)n));
+    }
+    const double *dT;
+    const int *dOk;
+    SVO_TRY(to_device(ctx, T, (double *)bT.p, (size_t)16 * n, mem, &dT));
+    SVO_TRY(to_device(ctx, (const int *)ok, (int *)bOk.p, (size_t)n, mem, &dOk));
+    double *dOut = mem == SVO_MEM_HOST ? (double *)bOut.p : out;
+    hipLaunchKernelGGL(chain_relative_kernel, dim3(1), dim3(64), 0, ctx->stream, dT, dOk, n, p0, dOut);
     SVO_HIP(hipGetLastError());
-    SVO_HIP(hipMemcpyAsync(out, bOut.p, sizeof(double) * 16 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    SVO_TRY(from_device(ctx, out, (const double *)dOut, (size_t)16 * n, mem));
+    return io_done(ctx, mem);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1243,20 +1241,13 @@ int stage_triangulate(svo_ctx *ctx, const double P1[12], const double P2[12], co
     memcpy(a.P1, P1, sizeof(a.P1));
     memcpy(a.P2, P2, sizeof(a.P2));
     a.stride = 0; a.n_pts = nullptr; a.n_fixed = n;
-    if (mem == SVO_MEM_HOST) {
-        SVO_HIP(hipMemcpyAsync(ctx->cmp[0], x1, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        SVO_HIP(hipMemcpyAsync(ctx->cmp[1], x2, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        a.x1 = ctx->cmp[0]; a.x2 = ctx->cmp[1]; a.out3 = ctx->X3;
-    } else {
-        a.x1 = (const float2 *)x1; a.x2 = (const float2 *)x2; a.out3 = (float *)out;
-    }
+    SVO_TRY(to_device(ctx, (const float2 *)x1, ctx->cmp[0], (size_t)n, mem, &a.x1));
+    SVO_TRY(to_device(ctx, (const float2 *)x2, ctx->cmp[1], (size_t)n, mem, &a.x2));
+    a.out3 = mem == SVO_MEM_HOST ? ctx->X3 : (float *)out;
     hipLaunchKernelGGL(triangulate_kernel, dim3((n + 63) / 64, 1), dim3(64), 0, ctx->stream, a);
     SVO_HIP(hipGetLastError());
-    if (mem == SVO_MEM_HOST) {
-        SVO_HIP(hipMemcpyAsync(out, ctx->X3, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SVO_OK;
+    SVO_TRY(from_device(ctx, (float *)out, (const float *)a.out3, (size_t)3 * n, mem));                  // (device: the kernel wrote them)
+    return io_done(ctx, mem);
 }
 
 int stage_pnp_ransac(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img, int n, const double K[9],
@@ -1274,22 +1265,16 @@ int stage_pnp_ransac(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img, int
     a.iterations = iterations; a.reproj_err = reproj_err; a.confidence = confidence;
     a.first_cap = pnp_first_cap(ctx->cfg);                   // (the stage call of a context follows its track_mode too)
     uint8_t *ws_mask = (uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch);
-    if (mem == SVO_MEM_HOST) {
-        if (n > 0) {
-            SVO_HIP(hipMemcpyAsync(ctx->X3, obj, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            SVO_HIP(hipMemcpyAsync(ctx->cmp[3], img, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        }
-        a.X3 = ctx->X3; a.img = ctx->cmp[3]; a.mask = ws_mask;
-    } else {
-        a.X3 = (const float *)obj; a.img = (const float2 *)img; a.mask = inlier_mask ? inlier_mask : ws_mask;
-    }
+    SVO_TRY(to_device(ctx, (const float *)obj, ctx->X3, (size_t)3 * n, mem, &a.X3));
+    SVO_TRY(to_device(ctx, (const float2 *)img, ctx->cmp[3], (size_t)n, mem, &a.img));
+    a.mask = mem == SVO_MEM_DEVICE && inlier_mask ? inlier_mask : ws_mask;
     launch_pnp_pipeline(ctx, a, 1, n, ctx->stream);
     SVO_HIP(hipGetLastError());
-    PnpRecord *h = (PnpRecord *)((char *)ctx->h_pinned + 256);
-    SVO_HIP(hipMemcpyAsync(h, ctx->pnp_ws, sizeof(PnpRecord), hipMemcpyDeviceToHost, ctx->stream));
-    if (mem == SVO_MEM_HOST && inlier_mask && n > 0)
-        SVO_HIP(hipMemcpyAsync(inlier_mask, ws_mask, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    PnpRecord *h;                                            // the record comes back to the host in both memory kinds
+    SVO_TRY(pinned_block(ctx, sizeof(PnpRecord), &h));
+    SVO_TRY(from_device(ctx, h, (const PnpRecord *)ctx->pnp_ws, 1, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, inlier_mask, (const uint8_t *)a.mask, (size_t)n, mem));                     // (device: the kernels wrote it)
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     memcpy(res->rvec, h->rvec, sizeof(res->rvec));
     memcpy(res->tvec, h->tvec, sizeof(res->tvec));
     memcpy(res->R, h->R, sizeof(res->R));

@@ -23,7 +23,7 @@
 // frame block per stream.
 #include <cmath>
 #include <cstring>
-#include "svo_ctx.h"
+#include "abi_io.h"
 
 namespace svo {
 
@@ -519,23 +519,22 @@ extern "C" int svo_get_orb_matcher(const svo_ctx *ctx, int *mode, int *th_stereo
 // uR / sad of frame slot `frame`'s block and (kps != null) its left keypoints, to host memory
 static int orbm_read_frame(svo_ctx *ctx, int frame, svo_keypoint *kps, float *uR, int *sad, int cap, int *n_out)
 {
-    int *h = (int *)ctx->h_pinned;
+    enum { kEpoch = 0, kN = 1, kOverflow = 4 };              // positions in the pinned ints: the block's header (4 ints), the two eyes' flags
+    const int *h;
     const OrbmFrame fr = orbm_frame(ctx->orbm_frames, (int64_t)ctx->orbm_frame_bytes, ctx->orbm_kc, frame);
-    SVO_HIP(hipMemcpyAsync(h, fr.hdr, 16, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipMemcpyAsync(h + 4, ctx->orb_overflow + 2 * frame, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    SVO_ARG(h[0] == ctx->orbm_epoch, "the frame was stored before the guided matcher was selected: it has no stereo data");
-    SVO_ARG(!h[4] && !h[5], "ORB: keypoints / candidates exceed the context's capacity");
-    const int n = h[1];
+    SVO_TRY(count_fetch(ctx, kEpoch, fr.hdr, 4));
+    SVO_TRY(count_fetch(ctx, kOverflow, ctx->orb_overflow + 2 * frame, 2));
+    SVO_TRY(counts_wait(ctx, &h));
+    SVO_ARG(h[kEpoch] == ctx->orbm_epoch, "the frame was stored before the guided matcher was selected: it has no stereo data");
+    SVO_ARG(!h[kOverflow] && !h[kOverflow + 1], "ORB: keypoints / candidates exceed the context's capacity");
+    const int n = h[kN];
     *n_out = n;
     SVO_ARG(n <= cap, "capacity too small");
     if (n == 0) return SVO_OK;
-    if (kps) SVO_HIP(hipMemcpyAsync(kps, (const svo_keypoint *)ctx->orb_kps + (size_t)(2 * frame) * ctx->orb_kp_cap, sizeof(svo_keypoint) * (size_t)n,
-                                    hipMemcpyDeviceToHost, ctx->stream));
-    if (uR) SVO_HIP(hipMemcpyAsync(uR, fr.uR, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (sad) SVO_HIP(hipMemcpyAsync(sad, fr.sad, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    SVO_TRY(from_device(ctx, kps, (const svo_keypoint *)ctx->orb_kps + (size_t)(2 * frame) * ctx->orb_kp_cap, (size_t)n, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, uR, (const float *)fr.uR, (size_t)n, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, sad, (const int *)fr.sad, (size_t)n, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 extern "C" int svo_orb_stereo_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, int mem, int slot,
@@ -584,21 +583,16 @@ extern "C" int svo_orb_track_frames(svo_ctx *ctx, int slot_prev, int slot_cur, s
     int rc = orbm_track_pairs(ctx, 1, slot_prev, slot_cur, 0, ctx->stream, d_idx, d_idx + kc);
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
-    int *h = (int *)ctx->h_pinned;
-    SVO_HIP(hipMemcpyAsync(h, ctx->m_out, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    const int m = h[0];
-    *n_out = m;
+    SVO_TRY(count_read(ctx, ctx->m_out, n_out));
+    const int m = *n_out;
     SVO_ARG(m <= cap, "capacity too small");
     if (m == 0) return SVO_OK;
     svo_pt2f *dst[3] = {t1_left, t1_right, t2_left};
     const float2 *src[3] = {ctx->cmp[0], ctx->cmp[1], ctx->cmp[3]};
-    for (int k = 0; k < 3; k++)
-        if (dst[k]) SVO_HIP(hipMemcpyAsync(dst[k], src[k], sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    if (idx_prev) SVO_HIP(hipMemcpyAsync(idx_prev, d_idx, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    if (idx_cur) SVO_HIP(hipMemcpyAsync(idx_cur, d_idx + kc, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    for (int k = 0; k < 3; k++) SVO_TRY(from_device(ctx, (float2 *)dst[k], src[k], (size_t)m, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, idx_prev, (const int32_t *)d_idx, (size_t)m, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, idx_cur, (const int32_t *)d_idx + kc, (size_t)m, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 extern "C" int svo_get_frame_stereo(svo_ctx *ctx, float *uR, int32_t *sad, int cap, int *n_out)

@@ -10,7 +10,7 @@
 // sequential.  The online entry point (svo_add_frame) runs the same kernels with one pair on a
 // two-frame ring.
 #include <cstring>
-#include "svo_ctx.h"
+#include "abi_io.h"
 
 namespace svo {
 
@@ -336,15 +336,12 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
 
 int deliver_records(svo_ctx *ctx, const svo_step_result *d_src, int n, svo_step_result *out, int mem, hipStream_t st)
 {
-    const size_t bytes = sizeof(svo_step_result) * (size_t)n;
-    if (mem == SVO_MEM_DEVICE) {
-        if (out) SVO_HIP(hipMemcpyAsync(out, d_src, bytes, hipMemcpyDeviceToDevice, st));
-        return SVO_OK;
-    }
-    void *h = (char *)ctx->h_pinned + kPinnedRecords;
-    SVO_HIP(hipMemcpyAsync(h, d_src, bytes, hipMemcpyDeviceToHost, st));
-    SVO_HIP(hipStreamSynchronize(st));
-    memcpy(out, h, bytes);
+    if (mem == SVO_MEM_DEVICE) return from_device(ctx, out, d_src, (size_t)n, mem, st);
+    svo_step_result *h;
+    SVO_TRY(pinned_records(ctx, sizeof(svo_step_result) * (size_t)n, &h));
+    SVO_TRY(from_device(ctx, h, d_src, (size_t)n, mem, st));
+    SVO_TRY(io_done(ctx, mem, st));
+    memcpy(out, h, sizeof(svo_step_result) * (size_t)n);
     return SVO_OK;
 }
 
@@ -411,11 +408,8 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     memset(res, 0, sizeof(*res));
     if (ctx->online_frames == 0) {
         // StereoInit_f2f (:78-92): detect only
-        int *h_n = (int *)ctx->h_pinned;
-        const int *src_n = ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur;
-        SVO_HIP(hipMemcpyAsync(h_n, src_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-        res->ok = 1; res->n_cur_kps = *h_n;
+        SVO_TRY(count_read(ctx, ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur, &res->n_cur_kps));
+        res->ok = 1;
         for (int i = 0; i < 9; i++) res->R[i] = (i % 4 == 0) ? 1.0 : 0.0;
         for (int i = 0; i < 16; i++) { res->T_rel_inv[i] = (i % 5 == 0) ? 1.0 : 0.0; res->pose[i] = ctx->pose[i]; }
         ctx->online_frames = 1; ctx->online_cur = cur; ctx->online_tracked = 0;
@@ -489,9 +483,10 @@ int pipeline_streams_get_pose(svo_ctx *ctx, int id, double *pose)
     SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
     SVO_ARG(id >= 0 && id < ss.n && pose, "stream id out of range / null pose");
     SVO_HIP(hipSetDevice(ctx->device));
-    double *h = (double *)((char *)ctx->h_pinned + 256);
-    SVO_HIP(hipMemcpyAsync(h, ss.pose + (size_t)id * 16, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    double *h;
+    SVO_TRY(pinned_block(ctx, sizeof(double) * 16, &h));
+    SVO_TRY(from_device(ctx, h, (const double *)ss.pose + (size_t)id * 16, 16, SVO_MEM_HOST));
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     memcpy(pose, h, sizeof(double) * 16);
     return SVO_OK;
 }

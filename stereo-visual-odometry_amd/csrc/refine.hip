@@ -12,7 +12,7 @@
 // A point's active flag lives in device memory and is only ever touched by the lane that strides over it.
 #include <cmath>
 #include <cstring>
-#include "svo_ctx.h"
+#include "abi_io.h"
 
 namespace svo {
 
@@ -472,27 +472,19 @@ int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_lef
     uint8_t *own_flags = a.flags + (size_t)B * c.max_keypoints;
     a.flags = own_flags; a.flag_stride = 0; a.stride = 0; a.n_fixed = n; a.pnp = nullptr;
     for (int i = 0; i < 3; i++) { a.rvec0[i] = rvec0[i]; a.tvec0[i] = tvec0[i]; }
-    if (mem == SVO_MEM_HOST) {
-        const RefineCut o = refine_cut(c);
-        float *dX = (float *)(ctx->refine_buf + o.X);
-        float2 *dl = (float2 *)(ctx->refine_buf + o.xl), *dr = (float2 *)(ctx->refine_buf + o.xr);
-        if (n > 0) {
-            SVO_HIP(hipMemcpyAsync(dX, obj, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            SVO_HIP(hipMemcpyAsync(dl, img_left, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            if (two) SVO_HIP(hipMemcpyAsync(dr, img_right, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        }
-        a.X3 = dX; a.xl = dl; a.xr = two ? dr : nullptr;
-    } else {
-        a.X3 = (const float *)obj; a.xl = (const float2 *)img_left; a.xr = (const float2 *)img_right;
-        if (active) a.flags = active;
-    }
+    const RefineCut o = refine_cut(c);
+    SVO_TRY(to_device(ctx, (const float *)obj, (float *)(ctx->refine_buf + o.X), (size_t)3 * n, mem, &a.X3));
+    SVO_TRY(to_device(ctx, (const float2 *)img_left, (float2 *)(ctx->refine_buf + o.xl), (size_t)n, mem, &a.xl));
+    if (two) SVO_TRY(to_device(ctx, (const float2 *)img_right, (float2 *)(ctx->refine_buf + o.xr), (size_t)n, mem, &a.xr));
+    if (mem == SVO_MEM_DEVICE && active) a.flags = active;
     if (two) hipLaunchKernelGGL(pose_refine_kernel<2>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
     else hipLaunchKernelGGL(pose_refine_kernel<1>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
     SVO_HIP(hipGetLastError());
-    svo_refine_result *h = (svo_refine_result *)((char *)ctx->h_pinned + 256);
-    SVO_HIP(hipMemcpyAsync(h, a.res, sizeof(svo_refine_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (mem == SVO_MEM_HOST && active && n > 0) SVO_HIP(hipMemcpyAsync(active, own_flags, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    svo_refine_result *h;                                    // the record comes back to the host in both memory kinds
+    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
+    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)a.res, 1, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, active, (const uint8_t *)a.flags, (size_t)n, mem));                         // (device: the kernel wrote them)
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     memcpy(res, h, sizeof(*res));
     return SVO_OK;
 }
@@ -501,19 +493,18 @@ int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_lef
 int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out)
 {
     const svo_config &c = ctx->cfg;
-    svo_refine_result *h = (svo_refine_result *)((char *)ctx->h_pinned + 256);
-    SVO_HIP(hipMemcpyAsync(h, (const svo_refine_result *)ctx->refine_buf + pair, sizeof(*h), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    svo_refine_result *h;
+    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
+    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)ctx->refine_buf + pair, 1, SVO_MEM_HOST));
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     const int n = h->n_points;
     SVO_ARG(n >= 0 && n <= c.max_keypoints, "corrupt point count");
     if (n_out) *n_out = n;                                  // also when the capacity is too small: what to size `active` for
     SVO_ARG(active == nullptr || n <= cap, "flag capacity too small");     // nothing else has been written
     if (res) memcpy(res, h, sizeof(*res));
-    if (active && n > 0) {
-        SVO_HIP(hipMemcpyAsync(active, ctx->refine_buf + refine_cut(c).flags + (size_t)pair * c.max_keypoints, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SVO_OK;
+    if (!active || n == 0) return SVO_OK;
+    SVO_TRY(from_device(ctx, active, (const uint8_t *)ctx->refine_buf + refine_cut(c).flags + (size_t)pair * c.max_keypoints, (size_t)n, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 }  // namespace svo

@@ -1,13 +1,14 @@
 // svo_abi.hip -- host side of the C-ABI declared in include/svo_abi.h: context lifecycle, buffer
 // ownership (ctx owns every device buffer; no allocation in the steady state) and the stage /
 // fused entry points that launch the HIP kernels.  There is NO CPU fallback in this library.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <ctime>
 #include <new>
 #include <vector>
-#include "svo_ctx.h"
+#include "abi_io.h"
 
 using namespace svo;
 
@@ -289,9 +290,10 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
         CK(frame_buffers(ctx));
         CK(async_ring(ctx));
     }
-    ctx->h_pinned_bytes = kPinnedRecords + sizeof(svo_step_result) * (size_t)B +
-                          (size_t)cap * (sizeof(svo_keypoint) + 32) + sizeof(int) * 64;
-    CK(hipHostMalloc(&ctx->h_pinned, ctx->h_pinned_bytes, hipHostMallocDefault));
+    // (the fixed records read back through the block: PnpRecord, svo_refine_result, a stream's pose)
+    ctx->pinned = pinned_layout((size_t)cap, (size_t)B, sizeof(svo_keypoint), sizeof(svo_step_result),
+                                std::max({sizeof(PnpRecord), sizeof(svo_refine_result), sizeof(double) * 16}));
+    CK(hipHostMalloc(&ctx->h_pinned, ctx->pinned.total, hipHostMallocDefault));
     PHASE("events, streams, page-locked scratch");
     CK(hipStreamSynchronize(ctx->stream));
     PHASE("stream sync");
@@ -464,25 +466,20 @@ extern "C" int svo_fast_detect(svo_ctx *ctx, const uint8_t *img, int pitch, int 
     launch_fast(a, 1, ctx->stream);
     SVO_HIP(hipGetLastError());
     // D2H through pinned scratch: count, then xy + response
-    int *h_n = (int *)ctx->h_pinned;
-    SVO_HIP(hipMemcpyAsync(h_n, ctx->kp_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    int n = *h_n;
+    int n;
+    SVO_TRY(count_read(ctx, ctx->kp_n, &n));
     *n_out = n;
     if (n > ctx->cfg.max_keypoints) { ctx->err = "FAST: keypoints exceed max_keypoints"; return SVO_ERR_ARG; }
     if (n > cap) { ctx->err = "FAST: keypoints exceed caller capacity"; return SVO_ERR_ARG; }
     if (n == 0) return SVO_OK;
-    float2 *h_xy = (float2 *)((char *)ctx->h_pinned + 256);
+    float2 *h_xy;
+    SVO_TRY(pinned_block(ctx, (sizeof(float2) + sizeof(float)) * (size_t)ctx->cfg.max_keypoints, &h_xy));
     float *h_r = (float *)(h_xy + ctx->cfg.max_keypoints);
-    SVO_HIP(hipMemcpyAsync(h_xy, ctx->kp_xy, sizeof(float2) * n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipMemcpyAsync(h_r, ctx->kp_resp, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    // cv::KeyPoint(pt, 7.f, -1, response, 0, -1); always a HOST array (it is an array of structs
-    // for the caller's std::vector<cv::KeyPoint>)
-    for (int i = 0; i < n; i++) {
-        out[i].x = h_xy[i].x; out[i].y = h_xy[i].y; out[i].size = 7.f; out[i].angle = -1.f;
-        out[i].response = h_r[i]; out[i].octave = 0; out[i].class_id = -1;
-    }
+    SVO_TRY(from_device(ctx, h_xy, (const float2 *)ctx->kp_xy, (size_t)n, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, h_r, (const float *)ctx->kp_resp, (size_t)n, SVO_MEM_HOST));
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+    // always a HOST array (it is an array of structs for the caller's std::vector<cv::KeyPoint>)
+    format_keypoints(h_xy, h_r, n, out);
     return SVO_OK;
 }
 
@@ -529,16 +526,6 @@ extern "C" int svo_read_pyramid_level(svo_ctx *ctx, int slot, int level, uint8_t
     return SVO_OK;
 }
 
-// copies n items in (host) or aliases (device)
-template <typename T>
-static int to_device(svo_ctx *ctx, const T *src, T *scratch, int n, int mem, const T **d)
-{
-    if (mem == SVO_MEM_DEVICE) { *d = src; return SVO_OK; }
-    SVO_HIP(hipMemcpyAsync(scratch, src, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    *d = scratch;
-    return SVO_OK;
-}
-
 static void fill_lk_common(svo_ctx *ctx, LkArgs &a, int n)
 {
     a.g = ctx->geom;
@@ -562,8 +549,7 @@ extern "C" int svo_lk_track(svo_ctx *ctx, int slot_prev, int slot_next, const sv
     SVO_ARG(prev_pts && next_pts && status, "null pointer");
     SVO_HIP(hipSetDevice(ctx->device));
     const float2 *d_in;
-    int rc = to_device<float2>(ctx, (const float2 *)prev_pts, ctx->pts_in, n, mem, &d_in);
-    if (rc) return rc;
+    SVO_TRY(to_device(ctx, (const float2 *)prev_pts, ctx->pts_in, (size_t)n, mem, &d_in));
     LkArgs a{};
     fill_lk_common(ctx, a, n);
     a.ncalls = 1;
@@ -574,12 +560,9 @@ extern "C" int svo_lk_track(svo_ctx *ctx, int slot_prev, int slot_next, const sv
     a.status[0] = mem == SVO_MEM_DEVICE ? status : ctx->status[0];
     launch_lk(a, 1, n, ctx->stream);
     SVO_HIP(hipGetLastError());
-    if (mem == SVO_MEM_HOST) {
-        SVO_HIP(hipMemcpyAsync(next_pts, ctx->pts_out[0], sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipMemcpyAsync(status, ctx->status[0], (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SVO_OK;
+    SVO_TRY(from_device(ctx, (float2 *)next_pts, (const float2 *)a.pts_out[0], (size_t)n, mem));      // (device: the kernel wrote them)
+    SVO_TRY(from_device(ctx, status, (const uint8_t *)a.status[0], (size_t)n, mem));
+    return io_done(ctx, mem);
 }
 
 extern "C" int svo_circular_match(svo_ctx *ctx, int slot_prevL, int slot_prevR, int slot_curL, int slot_curR,
@@ -602,8 +585,7 @@ extern "C" int svo_circular_match(svo_ctx *ctx, int slot_prevL, int slot_prevR, 
     SVO_ARG(t1_left && out_t1_left && out_t1_right && out_t2_right && out_t2_left, "null pointer");
     SVO_HIP(hipSetDevice(ctx->device));
     const float2 *d_in;
-    int rc = to_device<float2>(ctx, (const float2 *)t1_left, ctx->pts_in, n, mem, &d_in);
-    if (rc) return rc;
+    SVO_TRY(to_device(ctx, (const float2 *)t1_left, ctx->pts_in, (size_t)n, mem, &d_in));
     auto S = [&](int s) { return ctx->slots + (size_t)s * ctx->geom.slot_bytes; };
     LkArgs a{};
     fill_lk_common(ctx, a, n);
@@ -625,16 +607,10 @@ extern "C" int svo_circular_match(svo_ctx *ctx, int slot_prevL, int slot_prevR, 
     c.m_out = ctx->m_out;
     launch_compact(c, 1, ctx->stream);
     SVO_HIP(hipGetLastError());
-    int *h_m = (int *)ctx->h_pinned;
-    SVO_HIP(hipMemcpyAsync(h_m, ctx->m_out, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    *m_out = *h_m;
-    if (mem == SVO_MEM_HOST && *h_m > 0) {
-        for (int i = 0; i < 4; i++)
-            SVO_HIP(hipMemcpyAsync(outs[i], ctx->cmp[i], sizeof(float2) * (size_t)*h_m, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SVO_OK;
+    SVO_TRY(count_read(ctx, ctx->m_out, m_out));
+    if (*m_out <= 0) return SVO_OK;
+    for (int i = 0; i < 4; i++) SVO_TRY(from_device(ctx, (float2 *)outs[i], (const float2 *)c.out[i], (size_t)*m_out, mem));
+    return io_done(ctx, mem);
 }
 
 extern "C" int svo_orb_extract(svo_ctx *ctx, const uint8_t *img, int pitch, int mem, svo_keypoint *kps, uint8_t *desc,
@@ -651,26 +627,28 @@ extern "C" int svo_orb_extract(svo_ctx *ctx, const uint8_t *img, int pitch, int 
     rc = orb_extract_batch(ctx, d, nullptr, dp, 0, 0, 1, ctx->stream);
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
-    int *h = (int *)ctx->h_pinned;        // [0] n, [1] overflow, [8..16) per-level counts, [32..) cell counts
-    SVO_HIP(hipMemcpyAsync(h, ctx->orb_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipMemcpyAsync(h + 1, ctx->orb_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipMemcpyAsync(h + 8, ctx->orb_sel_cnt, sizeof(int) * ctx->orb_geom.nlevels, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    const int n = h[0];
+    enum { kN = 0, kOverflow = 1, kPerLevel = 8 };           // positions in the pinned ints
+    const int *h;
+    SVO_TRY(count_fetch(ctx, kN, ctx->orb_n));
+    SVO_TRY(count_fetch(ctx, kOverflow, ctx->orb_overflow));
+    SVO_TRY(count_fetch(ctx, kPerLevel, ctx->orb_sel_cnt, ctx->orb_geom.nlevels));
+    SVO_TRY(counts_wait(ctx, &h));
+    const int n = h[kN];
     *n_out = n;
-    if (h[1]) {
-        ctx->err = (h[1] & 2) ? "ORB: FAST candidates exceed the per-cell (256) or per-level (4 * max_keypoints) capacity"
-                   : (h[1] & 1) ? "ORB quadtree node pool overflow" : "ORB: keypoints exceed max_keypoints";
+    if (h[kOverflow]) {
+        ctx->err = (h[kOverflow] & 2) ? "ORB: FAST candidates exceed the per-cell (256) or per-level (4 * max_keypoints) capacity"
+                   : (h[kOverflow] & 1) ? "ORB quadtree node pool overflow" : "ORB: keypoints exceed max_keypoints";
         return SVO_ERR_ARG;
     }
-    if (per_level) for (int l = 0; l < 8; l++) per_level[l] = l < ctx->orb_geom.nlevels ? h[8 + l] : 0;
+    if (per_level) for (int l = 0; l < 8; l++) per_level[l] = l < ctx->orb_geom.nlevels ? h[kPerLevel + l] : 0;
     if (n > cap) { ctx->err = "ORB: keypoints exceed caller capacity"; return SVO_ERR_ARG; }
     if (n == 0) return SVO_OK;
-    svo_keypoint *hk = (svo_keypoint *)((char *)ctx->h_pinned + 256);
+    svo_keypoint *hk;
+    SVO_TRY(pinned_block(ctx, (sizeof(svo_keypoint) + 32) * (size_t)ctx->orb_kp_cap, &hk));
     uint8_t *hd = (uint8_t *)(hk + ctx->orb_kp_cap);
-    SVO_HIP(hipMemcpyAsync(hk, ctx->orb_kps, sizeof(svo_keypoint) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipMemcpyAsync(hd, ctx->orb_desc, (size_t)32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    SVO_TRY(from_device(ctx, hk, (const svo_keypoint *)ctx->orb_kps, (size_t)n, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, hd, (const uint8_t *)ctx->orb_desc, (size_t)32 * n, SVO_MEM_HOST));
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     memcpy(kps, hk, sizeof(svo_keypoint) * (size_t)n);
     memcpy(desc, hd, (size_t)32 * n);
     return SVO_OK;
@@ -704,11 +682,12 @@ extern "C" int svo_orb_read_candidates(svo_ctx *ctx, int level, float *out4, int
     if (rc) return rc;
     SVO_ARG(level >= 0 && level < ctx->orb_geom.nlevels && out4 && n_out, "bad argument");
     int n = 0;
-    SVO_HIP(hipMemcpy(&n, ctx->orb_lvl_cnt + level, sizeof(int), hipMemcpyDeviceToHost));
+    SVO_TRY(count_read(ctx, ctx->orb_lvl_cnt + level, &n));
     *n_out = n;
     if (n > cap) n = cap;
-    if (n > 0) SVO_HIP(hipMemcpy(out4, ctx->orb_lvl_cand + (size_t)level * ctx->orb_cand_cap, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
-    return SVO_OK;
+    if (n <= 0) return SVO_OK;
+    SVO_TRY(from_device(ctx, (float4 *)out4, (const float4 *)ctx->orb_lvl_cand + (size_t)level * ctx->orb_cand_cap, (size_t)n, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 extern "C" int svo_match_hamming(svo_ctx *ctx, const uint8_t *query, int nq, const uint8_t *train, int nt,
@@ -723,24 +702,14 @@ extern "C" int svo_match_hamming(svo_ctx *ctx, const uint8_t *query, int nq, con
     if (nq == 0) return SVO_OK;
     SVO_ARG(query && train_idx && distance && (train || nt == 0), "null pointer");
     if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
-    const uint8_t *dq = query, *dt = train;
-    if (mem == SVO_MEM_HOST) {
-        // stage through the descriptor slots of image 0 / 1
-        SVO_HIP(hipMemcpyAsync(ctx->orb_desc, query, (size_t)32 * nq, hipMemcpyHostToDevice, ctx->stream));
-        if (nt > 0) SVO_HIP(hipMemcpyAsync(ctx->orb_desc + (size_t)32 * ctx->orb_kp_cap, train, (size_t)32 * nt, hipMemcpyHostToDevice, ctx->stream));
-        dq = ctx->orb_desc; dt = ctx->orb_desc + (size_t)32 * ctx->orb_kp_cap;
-    }
+    const uint8_t *dq, *dt;                                  // host descriptors: staged through the descriptor slots of image 0 / 1
+    SVO_TRY(to_device(ctx, query, ctx->orb_desc, (size_t)32 * nq, mem, &dq));
+    SVO_TRY(to_device(ctx, train, ctx->orb_desc + (size_t)32 * ctx->orb_kp_cap, (size_t)32 * nt, mem, &dt));
     orb_launch_match_fixed(ctx, dq, nq, dt, nt, ctx->stream);
     SVO_HIP(hipGetLastError());
-    if (mem == SVO_MEM_HOST) {
-        SVO_HIP(hipMemcpyAsync(train_idx, ctx->orb_midx[0], sizeof(int) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipMemcpyAsync(distance, ctx->orb_mdist[0], sizeof(float) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    } else {
-        SVO_HIP(hipMemcpyAsync(train_idx, ctx->orb_midx[0], sizeof(int) * (size_t)nq, hipMemcpyDeviceToDevice, ctx->stream));
-        SVO_HIP(hipMemcpyAsync(distance, ctx->orb_mdist[0], sizeof(float) * (size_t)nq, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    return SVO_OK;
+    SVO_TRY(from_device(ctx, train_idx, (const int32_t *)ctx->orb_midx[0], (size_t)nq, mem));
+    SVO_TRY(from_device(ctx, distance, (const float *)ctx->orb_mdist[0], (size_t)nq, mem));
+    return io_done(ctx, mem);
 }
 
 extern "C" int svo_triangulate(svo_ctx *ctx, const double P1[12], const double P2[12], const svo_pt2f *x1,
@@ -1275,17 +1244,13 @@ extern "C" int svo_get_frame_keypoints(svo_ctx *ctx, int side, svo_keypoint *kps
     if (ctx->cfg.track_mode == SVO_MODE_ORB) {
         const int slot = 2 * cur + side, kcap = ctx->orb_kp_cap;
         int n = 0;
-        SVO_HIP(hipMemcpyAsync(&n, ctx->orb_n + slot, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
+        SVO_TRY(count_read(ctx, ctx->orb_n + slot, &n));
         n = n < kcap ? n : kcap;
         SVO_ARG(n <= cap, "keypoint capacity too small");
         if (n > 0) {
-            SVO_HIP(hipMemcpyAsync(kps, (const svo_keypoint *)ctx->orb_kps + (size_t)slot * kcap, sizeof(svo_keypoint) * n,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-            if (descriptors)
-                SVO_HIP(hipMemcpyAsync(descriptors, ctx->orb_desc + (size_t)slot * kcap * 32, (size_t)32 * n, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-            SVO_HIP(hipStreamSynchronize(ctx->stream));
+            SVO_TRY(from_device(ctx, kps, (const svo_keypoint *)ctx->orb_kps + (size_t)slot * kcap, (size_t)n, SVO_MEM_HOST));
+            SVO_TRY(from_device(ctx, descriptors, (const uint8_t *)ctx->orb_desc + (size_t)slot * kcap * 32, (size_t)32 * n, SVO_MEM_HOST));
+            SVO_TRY(io_done(ctx, SVO_MEM_HOST));
         }
         *n_out = n;
         return SVO_OK;
@@ -1293,24 +1258,17 @@ extern "C" int svo_get_frame_keypoints(svo_ctx *ctx, int side, svo_keypoint *kps
     SVO_ARG(side == 0, "LK mode detects on the left image only (src/tracking.cpp:94-113)");
     const int kcap = ctx->cfg.max_keypoints;
     int n = 0;
-    SVO_HIP(hipMemcpyAsync(&n, ctx->kp_n + cur, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    SVO_TRY(count_read(ctx, ctx->kp_n + cur, &n));
     n = n < kcap ? n : kcap;
     SVO_ARG(n <= cap, "keypoint capacity too small");
     if (n > 0) {
         std::vector<float2> xy((size_t)n);
         std::vector<float> resp((size_t)n);
-        SVO_HIP(hipMemcpyAsync(xy.data(), ctx->kp_xy + (size_t)cur * kcap, sizeof(float2) * n, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipMemcpyAsync(resp.data(), ctx->kp_resp + (size_t)cur * kcap, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-        // the cv::KeyPoint cv::FAST produces (response = its score), or the one cv::GFTTDetector makes (size 3, response 0) where
-        // kp_resp carries the Shi-Tomasi tag, a value no FAST score takes (gftt.hip): a frame keeps the records of the detector
-        // that made them when svo_set_lk_detector switches between two frames
-        for (int i = 0; i < n; i++) {
-            const bool gftt = resp[i] == gftt_resp_tag();
-            kps[i].x = xy[i].x; kps[i].y = xy[i].y; kps[i].size = gftt ? 3.f : 7.f; kps[i].angle = -1.f;
-            kps[i].response = gftt ? 0.f : resp[i]; kps[i].octave = 0; kps[i].class_id = -1;
-        }
+        SVO_TRY(from_device(ctx, xy.data(), (const float2 *)ctx->kp_xy + (size_t)cur * kcap, (size_t)n, SVO_MEM_HOST));
+        SVO_TRY(from_device(ctx, resp.data(), (const float *)ctx->kp_resp + (size_t)cur * kcap, (size_t)n, SVO_MEM_HOST));
+        SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+        // (a frame keeps the records of the detector that made them when svo_set_lk_detector switches between two frames)
+        format_keypoints(xy.data(), resp.data(), n, kps);
     }
     *n_out = n;
     return SVO_OK;
@@ -1324,11 +1282,10 @@ static int read_tracks(svo_ctx *ctx, size_t offset, int n, svo_pt2f *t1_left, sv
     for (int k = 0; k < 4; k++) {
         if (!dst[k]) continue;
         if (k == 2 && ctx->cfg.track_mode == SVO_MODE_ORB) { memset(dst[k], 0, sizeof(svo_pt2f) * (size_t)n); continue; }
-        SVO_HIP(hipMemcpyAsync(dst[k], ctx->cmp[k] + offset, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        SVO_TRY(from_device(ctx, (float2 *)dst[k], (const float2 *)ctx->cmp[k] + offset, (size_t)n, SVO_MEM_HOST));
     }
-    if (inlier) SVO_HIP(hipMemcpyAsync(inlier, pnp_inlier_mask(ctx) + offset, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    SVO_TRY(from_device(ctx, inlier, pnp_inlier_mask(ctx) + offset, (size_t)n, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 // The same read-back for pair `pair` of the most recent svo_track_batch / svo_track_uploaded launch (ABI v6): what a
@@ -1341,10 +1298,8 @@ extern "C" int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, s
     SVO_ARG(pair >= 0 && pair < ctx->last_batch_pairs, "pair is not part of the last batch launch");
     SVO_HIP(hipSetDevice(ctx->device));
     if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
-    int *h_n = (int *)ctx->h_pinned;
-    SVO_HIP(hipMemcpyAsync(h_n, ctx->m_out + pair, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    const int n = *h_n;
+    int n;
+    SVO_TRY(count_read(ctx, ctx->m_out + pair, &n));
     SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "corrupt track count");
     SVO_ARG(n <= cap, "track capacity too small");
     *n_out = n;
@@ -1435,9 +1390,9 @@ extern "C" int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, i
     int *d_n = (int *)s, *d_nout = host ? (int *)s + 1 : n_out;
     float2 *xy = (float2 *)(s + o_xy);
     float *resp = (float *)(s + o_resp);
-    const svo_keypoint *d_in = host ? (const svo_keypoint *)(s + o_in) : in;
+    const svo_keypoint *d_in;
     svo_keypoint *d_out = host ? (svo_keypoint *)(s + o_out) : out;
-    if (host && n > 0) SVO_HIP(hipMemcpyAsync((void *)d_in, in, sizeof(svo_keypoint) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    SVO_TRY(to_device(ctx, in, (svo_keypoint *)(s + o_in), (size_t)n, mem, &d_in));
     launch_bucket_unpack(d_in, n, xy, resp, d_n, ctx->stream);
     BucketArgs k{};
     k.kp_xy = xy; k.kp_resp = resp; k.kp_stride = 0; k.n_out = d_n; k.cap = n;
@@ -1448,16 +1403,10 @@ extern "C" int svo_bucket_corners(svo_ctx *ctx, const svo_keypoint *in, int n, i
     launch_bucket_pack(xy, resp, d_n, n, d_out, d_nout, ctx->stream);
     SVO_HIP(hipGetLastError());
     if (!host) return SVO_OK;
-    int *h_n = (int *)ctx->h_pinned;
-    SVO_HIP(hipMemcpyAsync(h_n, d_nout, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    const int m = *h_n;
-    *n_out = m;
-    if (m > 0) {
-        SVO_HIP(hipMemcpyAsync(out, d_out, sizeof(svo_keypoint) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SVO_OK;
+    SVO_TRY(count_read(ctx, d_nout, n_out));
+    if (*n_out <= 0) return SVO_OK;
+    SVO_TRY(from_device(ctx, out, (const svo_keypoint *)d_out, (size_t)*n_out, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 // ---- Shi-Tomasi corners: cv::goodFeaturesToTrack as the LK-mode detector and as stage calls (gftt.hip) ----------------
@@ -1634,18 +1583,13 @@ extern "C" int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int 
     launch_gftt_pack(xy, d_n, cap, d_rec, host ? nullptr : n_out, ctx->stream);
     SVO_HIP(hipGetLastError());
     if (!host) return SVO_OK;
-    int *h_n = (int *)ctx->h_pinned;
-    SVO_HIP(hipMemcpyAsync(h_n, d_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP(hipStreamSynchronize(ctx->stream));
-    const int m = *h_n;
-    *n_out = m;
+    SVO_TRY(count_read(ctx, d_n, n_out));
+    const int m = *n_out;
     SVO_ARG(m <= cap, "more candidates than cap");
-    if (m > 0) {
-        SVO_HIP(hipMemcpyAsync(out, d_rec, sizeof(svo_keypoint) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (strength) SVO_HIP(hipMemcpyAsync(strength, a.strength, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        SVO_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SVO_OK;
+    if (m <= 0) return SVO_OK;
+    SVO_TRY(from_device(ctx, out, (const svo_keypoint *)d_rec, (size_t)m, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, strength, (const float *)a.strength, (size_t)m, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
 }
 
 // ---- robust two-view pose refinement after solvePnPRansac (refine.hip: pose_refine_kernel) ----------------------------

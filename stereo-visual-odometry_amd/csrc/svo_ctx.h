@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/svo_abi.h"
 #include "block_cut.h"
+#include "pinned_layout.h"
 #include "svo_kernels.h"
 
 // A block of device memory that appears when a feature is first used and grows with the largest request: dev_reserve.
@@ -152,8 +153,9 @@ struct svo_ctx {
     uint8_t *orbm_frames = nullptr;                      // per frame slot: header, uR, sad, 128-byte patches
     float2 *orbm_t2 = nullptr; int *orbm_mj = nullptr; unsigned *orbm_mkey = nullptr, *orbm_win = nullptr;    // per pair x orbm_kc
     svo::OrbL0 orb_l0{}; int orb_l0_slot0 = 0;           // where the last extraction read level 0 in place (img null: it copied), its first image slot
-    // ---- pinned host scratch: counts and small read-backs at the front, step records from kPinnedRecords on
-    void *h_pinned = nullptr; size_t h_pinned_bytes = 0;
+    // ---- pinned host scratch, cut up by pinned_layout() (pinned_layout.h): device counts, the block of list / record
+    //      read-backs, the step records.  Reached through abi_io.h only (count_fetch, pinned_block, pinned_records).
+    void *h_pinned = nullptr; svo::PinnedLayout pinned;
     // ---- overlap mode (svo_set_overlap): the pose stage of batch k runs on side_stream while
     //      the caller's stream already ingests / tracks batch k+1
     bool overlap = false;
@@ -217,13 +219,18 @@ struct svo_ctx {
         }                                                                                     \
     } while (0)
 
+#define SVO_TRY(call)                                                                         \
+    do {                                                                                      \
+        const int rc__ = (call);                                                              \
+        if (rc__ != SVO_OK) return rc__;                                                      \
+    } while (0)
+
 #define SVO_ARG(cond, msg)                                                                    \
     do {                                                                                      \
         if (!(cond)) { ctx->err = std::string("bad argument: ") + msg; return SVO_ERR_ARG; }   \
     } while (0)
 
 namespace svo {
-constexpr size_t kPinnedRecords = 4096;                 // byte offset of the step records in svo_ctx::h_pinned
 // svo_abi.hip: the context's device memory, events and streams (DevArena)
 int dev_alloc_raw(svo_ctx *ctx, void **out, size_t bytes);
 template <class T> inline int dev_alloc(svo_ctx *ctx, T **out, size_t bytes) { return dev_alloc_raw(ctx, (void **)out, bytes); }
@@ -298,6 +305,6 @@ int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t
 // svo_abi.hip: the Shi-Tomasi detector of the fused LK front end (svo_set_lk_detector), n_new left images into frame slots f0 ..
 int gftt_detect_frames(svo_ctx *ctx, const uint8_t *L, int pitch, int64_t frame_stride, int f0, int n_new);
 // n step records from device memory to `out`, in the order of stream `st`: SVO_MEM_DEVICE: one copy, nothing waited for
-// (out null: they stay where they are); SVO_MEM_HOST: through the pinned scratch, and `st` is synchronised.
+// (out null: they stay where they are); SVO_MEM_HOST: through the pinned records range, and `st` is synchronised.
 int deliver_records(svo_ctx *ctx, const svo_step_result *d_src, int n, svo_step_result *out, int mem, hipStream_t st);
 }  // namespace svo
