@@ -163,3 +163,23 @@ def test_orb_callees(oracle):
     m = cv2.BFMatcher(cv2.NORM_HAMMING).match(desc, desc2)
     idx, dist = oracle.match_hamming(desc, desc2)
     assert [x.trainIdx for x in m] == list(idx) and [x.distance for x in m] == list(dist)
+
+
+def test_epnp_and_ransac_on_an_exactly_planar_set(oracle):
+    """The restated EPnP returns NaN on five exactly coplanar points and solvePnPRansac then finds no model on a 257-point
+    wall (tests/test_pnp_cases.py).  A real OpenCV has to be no better off: its EPnP is non-finite
+    there, or reprojects the five points worse than the 0.5 px inlier threshold, and its RANSAC reports failure or no
+    inliers."""
+    import _pnp_cases as pc
+    X, x, r, t = pc.make("wall", 5, pc.SEED, 0)
+    ok, rvec, tvec = cv2.solvePnP(X.astype(np.float64).reshape(-1, 1, 3), x.astype(np.float64).reshape(-1, 1, 2), pc.K, None,
+                                  flags=cv2.SOLVEPNP_EPNP)
+    if ok and np.isfinite(rvec).all() and np.isfinite(tvec).all():
+        proj, _ = cv2.projectPoints(X.astype(np.float64).reshape(-1, 1, 3), rvec, tvec, pc.K, None)
+        assert np.linalg.norm(proj.reshape(-1, 2) - x, axis=1).max() > 0.5
+    X, x, r, t = pc.make("wall", 257, pc.SEED, 80)
+    assert oracle.pnp_ransac(X, x, pc.K)["ok"] == 0
+    rvec, tvec = np.zeros((3, 1)), np.zeros((3, 1))
+    ok, rvec, tvec, inl = cv2.solvePnPRansac(X.reshape(-1, 1, 3), x.reshape(-1, 1, 2), pc.K, None, rvec, tvec, True,
+                                             500, 0.5, 0.99, None, cv2.SOLVEPNP_ITERATIVE)
+    assert not ok or inl is None or len(inl) == 0
