@@ -62,14 +62,16 @@ def median_cut(sads):
     return sads.astype(F) < thr
 
 
-def stereo(kL, dL, kR, dR, levL, levR, max_disparity, th_stereo=TH_STEREO, scale_factor=1.2):
-    """Stage S.  Returns (uR float32 (n,), sad int32 (n,), patches uint8 (n, 121)); uR -1 / sad -1: no stereo match."""
+def stereo(kL, dL, kR, dR, levL, levR, max_disparity, th_stereo=TH_STEREO, scale_factor=1.2, return_j=False):
+    """Stage S.  Returns (uR float32 (n,), sad int32 (n,), patches uint8 (n, 121)); uR -1 / sad -1: no stereo match.  With
+    return_j also the chosen right index per left keypoint (the packed minimum's j, before any threshold; -1: no candidate)."""
     sc, inv = scales(scale_factor, len(levL))
     n = len(kL)
     maxD = F(max_disparity)
     uR = np.full(n, -1.0, F)
     sd = np.full(n, -1, np.int32)
     patches = np.zeros((n, 121), np.uint8)
+    jbest = np.full(n, -1, np.int32)
     xR, yR, oR = kR["x"].astype(F), kR["y"].astype(F), kR["octave"].astype(np.int64)
     rj = (F(2.0) * sc[oR]).astype(F)
     lo, hi = np.floor((yR - rj).astype(F)), np.ceil((yR + rj).astype(F))
@@ -88,6 +90,7 @@ def stereo(kL, dL, kR, dR, levL, levR, max_disparity, th_stereo=TH_STEREO, scale
         keys = (hamming(dL[i], dR[cand]).astype(np.int64) << 16) | jj[cand]
         key = int(keys.min())
         best, j = key >> 16, key & 0xFFFF
+        jbest[i] = j
         if best >= th_stereo:
             continue
         J = levR[oL]
@@ -111,7 +114,7 @@ def stereo(kL, dL, kR, dR, levL, levR, max_disparity, th_stereo=TH_STEREO, scale
     keep = median_cut(sd[acc])
     uR[acc[~keep]] = F(-1.0)
     sd[acc[~keep]] = -1
-    return uR, sd, patches
+    return (uR, sd, patches, jbest) if return_j else (uR, sd, patches)
 
 
 def track(kP, dP, uR, patches, kC, dC, levC, th_track=TH_TRACK, ratio=RATIO, radius=0.0, scale_factor=1.2):
@@ -176,28 +179,32 @@ def levels_of(oracle, img, scale_factor=1.2, nlevels=8):
     return [oracle.orb_pyramid_level(img, l, scale_factor=scale_factor, nlevels=nlevels) for l in range(nlevels)]
 
 
-def frame_stereo(oracle, left, right, max_disparity, th_stereo=TH_STEREO):
-    """Extraction + stage S of one frame: dict with the left / right features, the left levels and stage S's outputs."""
-    kL, dL, _ = oracle.orb_extract(left)
-    kR, dR, _ = oracle.orb_extract(right)
-    levL, levR = levels_of(oracle, left), levels_of(oracle, right)
-    uR, sd, patches = stereo(kL, dL, kR, dR, levL, levR, max_disparity, th_stereo)
-    return dict(kL=kL, dL=dL, kR=kR, dR=dR, levL=levL, uR=uR, sad=sd, patches=patches)
+def frame_stereo(oracle, left, right, max_disparity, th_stereo=TH_STEREO, orb=None):
+    """Extraction + stage S of one frame: dict with the left / right features, the left levels and stage S's outputs.
+    orb: oracle.orb_extract keywords (nfeatures, scale_factor, nlevels, ini_th, min_th) of a non-default extractor."""
+    orb = dict(orb or {})
+    sf, nl = orb.get("scale_factor", 1.2), orb.get("nlevels", 8)
+    kL, dL, _ = oracle.orb_extract(left, **orb)
+    kR, dR, _ = oracle.orb_extract(right, **orb)
+    levL, levR = levels_of(oracle, left, sf, nl), levels_of(oracle, right, sf, nl)
+    uR, sd, patches, j = stereo(kL, dL, kR, dR, levL, levR, max_disparity, th_stereo, scale_factor=sf, return_j=True)
+    return dict(kL=kL, dL=dL, kR=kR, dR=dR, levL=levL, levR=levR, uR=uR, sad=sd, patches=patches, j=j, scale_factor=sf)
 
 
 def pair_tracks(prev, cur, **kw):
+    kw.setdefault("scale_factor", cur.get("scale_factor", 1.2))
     return track(prev["kL"], prev["dL"], prev["uR"], prev["patches"], cur["kL"], cur["dL"], cur["levL"], **kw)
 
 
 def ref_sequence(oracle, seq, frames, minmove=0.05, maxmove=10.0, num_features_tracking=5, inlier_rate=0.01, pose0=None,
-                 first_has_stereo=True, **kw):
+                 first_has_stereo=True, orb=None, **kw):
     """The fused ORB step with the guided matcher, frame by frame: twin -> oracle.triangulate -> oracle.pnp_ransac ->
     oracle.gate_and_accumulate.  Returns ([(record dict, pose)], [per-frame stage S dicts])."""
     P1, P2 = seq.proj()
     K = np.asarray(P1, np.float64).reshape(3, 4)[:, :3]
     maxd = kw.pop("max_disparity", 0.0) or float(F(np.asarray(P1, np.float64).reshape(-1)[0]))
     th_stereo = kw.pop("th_stereo", TH_STEREO)
-    fr = [frame_stereo(oracle, L, R, maxd, th_stereo) for L, R in frames]
+    fr = [frame_stereo(oracle, L, R, maxd, th_stereo, orb) for L, R in frames]
     pose = np.eye(4) if pose0 is None else np.asarray(pose0, np.float64).reshape(4, 4).copy()
     out = []
     for t in range(1, len(frames)):

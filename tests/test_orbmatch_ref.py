@@ -4,6 +4,7 @@ the brute-force matcher's inliers on the synthetic sequences (the reason it exis
 import numpy as np
 import pytest
 
+import _orbmatch_cases as C
 import _orbmatch_ref as M
 
 F = np.float32
@@ -236,3 +237,142 @@ def test_guided_matcher_doubles_the_inliers(oracle, seq_832, small_seq, which):
               f"brute {len(b1l)} / {b['n_inliers']} / {b['ransac_iters']}: ratio {g['n_inliers'] / max(b['n_inliers'], 1):.1f}")
         assert len(t1l) > len(b1l)
         assert g["n_inliers"] >= 2 * b["n_inliers"] and b["n_inliers"] > 0
+
+
+# ---- the edge cases of tests/_orbmatch_cases.py reach the paths they are named after ------------------------------------------
+# (tests/test_gpu_orbmatch_edges.py compares the kernels with the twin on these inputs; a case that never crossed the chunk, never
+# tied or never cut anything would pass there and prove nothing.  The floors are conditions, far below the measured counts.)
+@pytest.mark.parametrize("orb", [C.CHUNK_ORB, C.CHUNK3_ORB], ids=["one_level", "three_levels"])
+def test_chunk_pair_crosses_the_chunk(oracle, orb):
+    fr = C.twin(oracle, "chunk", orb)
+    j, acc = fr[0]["j"], fr[0]["uR"] >= 0
+    lo, hi = C.stereo_candidates(fr[0], C.CHUNK_MAXD)
+    tr = M.pair_tracks(fr[0], fr[1])
+    print(f"chunk pair, {orb['nlevels']} level(s): {[len(f['kL']) for f in fr]} left / {[len(f['kR']) for f in fr]} right keypoints, "
+          f"{[C.accepted(f) for f in fr]} accepted, winners j >= 2048: {int((acc & (j >= 2048)).sum())}, below: {int((acc & (j < 2048)).sum())}, "
+          f"candidates in both chunks: {int(((lo > 0) & (hi > 0)).sum())}, {len(tr[0])} tracks, idx_cur >= 2048: "
+          f"{int((tr[4] >= 2048).sum())}, idx_prev >= 2048: {int((tr[3] >= 2048).sum())}")
+    assert all(len(f["kR"]) > 2048 and len(f["kL"]) > 2048 for f in fr)
+    assert (acc & (j >= 2048)).sum() >= 300 and (acc & (j >= 0) & (j < 2048)).sum() >= 300
+    assert ((lo > 0) & (hi > 0)).sum() >= 1000
+    assert (tr[4] >= 2048).sum() >= 100 and (tr[3] >= 2048).sum() >= 100
+    assert fr[0]["scale_factor"] == orb["scale_factor"] and len(fr[0]["levL"]) == orb["nlevels"]
+
+
+def test_return_j_is_optional_and_names_the_winner(oracle):
+    fr = C.twin(oracle, "shift")[0]
+    args = (fr["kL"], fr["dL"], fr["kR"], fr["dR"], fr["levL"], fr["levR"], 300.0)
+    three, four = M.stereo(*args), M.stereo(*args, return_j=True)
+    assert len(three) == 3 and len(four) == 4
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(three, four))
+    j = four[3]
+    assert j.dtype == np.int32 and j.shape == fr["uR"].shape and (j[fr["uR"] >= 0] >= 0).all() and (j == -1).any()
+    for i in np.nonzero(j >= 0)[0][:50]:                      # no candidate of a lower index is as close as the winner
+        d = M.hamming(fr["dL"][i], fr["dR"])
+        band = np.abs(fr["kR"]["y"] - fr["kL"]["y"][i]) <= 1.0          # inside every band (r_j >= 2)
+        near = band & (fr["kR"]["x"] <= fr["kL"]["x"][i]) & (fr["kR"]["x"] >= fr["kL"]["x"][i] - 299.0)
+        near &= fr["kR"]["octave"] == fr["kL"]["octave"][i]
+        assert not (near[:j[i]] & (d[:j[i]] <= d[j[i]])).any() and not (near & (d < d[j[i]])).any()
+
+
+def test_shift_pair_counts(oracle):
+    fr = C.twin(oracle, "shift")
+    tr = M.pair_tracks(fr[0], fr[1])
+    print(f"shift pair: {[len(f['kL']) for f in fr]} keypoints, {[C.accepted(f) for f in fr]} accepted, {len(tr[0])} tracks")
+    assert min(len(f["kL"]) for f in fr) >= 1000 and min(C.accepted(f) for f in fr) >= 400 and len(tr[0]) >= 200
+    # a frame against itself: every accepted keypoint tracks, to itself
+    me = M.pair_tracks(fr[0], fr[0])
+    assert len(me[0]) == C.accepted(fr[0]) and np.array_equal(me[3], me[4])
+    assert np.array_equal(me[3], np.nonzero(fr[0]["uR"] >= 0)[0])
+
+
+@pytest.mark.parametrize("name", sorted(C.SCALE_ORBS))
+def test_scale_tables_populate_their_octaves(oracle, name):
+    orb = C.SCALE_ORBS[name]
+    fr = C.twin(oracle, "shift", orb)
+    tr = M.pair_tracks(fr[0], fr[1])
+    per = np.bincount(fr[0]["kL"]["octave"], minlength=orb["nlevels"])
+    per_acc = np.bincount(fr[0]["kL"]["octave"][fr[0]["uR"] >= 0], minlength=orb["nlevels"])
+    print(f"scale table {name}: {len(fr[0]['kL'])} keypoints {per.tolist()}, accepted {per_acc.tolist()}, {len(tr[0])} tracks")
+    # (on this image the 1.5 table's extractor keeps keypoints on two octaves, the 1.1 table's on all eight)
+    assert (per > 0).sum() >= (8 if name == "8x1.1" else min(orb["nlevels"], 2))
+    assert (per_acc > 0).sum() >= min(orb["nlevels"], 2) and C.accepted(fr[0]) >= 100 and len(tr[0]) >= 50
+    sc, _ = M.scales(orb.get("scale_factor", 1.2), orb["nlevels"])
+    osc, _, _, _ = oracle.orb_setup(orb["nfeatures"], orb.get("scale_factor", 1.2), orb["nlevels"])
+    assert sc.tobytes() == osc[:orb["nlevels"]].tobytes()
+    if orb["nlevels"] > 1:                                   # the scale table matters: the default one gives other matches
+        other = M.stereo(fr[0]["kL"], fr[0]["dL"], fr[0]["kR"], fr[0]["dR"], fr[0]["levL"], fr[0]["levR"], 300.0,
+                         scale_factor=1.3 if orb["scale_factor"] != 1.3 else 1.2)
+        assert other[0].tobytes() != fr[0]["uR"].tobytes()
+
+
+def test_tiled_pair_contests_and_ties(oracle):
+    fr = C.twin(oracle, "tiled")
+    for kw, floor in ((dict(ratio=0.9), 300), (dict(ratio=1.0), 300), (dict(radius=20.0, ratio=1.0), 300)):
+        n, ties = C.contested(fr[0], fr[1], **kw)
+        tr = M.pair_tracks(fr[0], fr[1], **kw)
+        print(f"tiled pair {kw}: {[C.accepted(f) for f in fr]} accepted, {len(tr[0])} tracks, {n} contested current keypoints, {ties} at equal distance")
+        assert len(tr[0]) >= floor
+        if not kw.get("radius"):
+            assert n >= 20 and ties >= 10
+
+
+def test_small_radius_leaves_one_candidate_or_none(oracle):
+    fr = C.twin(oracle, "shift")
+    nc = C.track_candidates(fr[0], fr[1], 3.0)
+    n3, n05 = len(M.pair_tracks(fr[0], fr[1], radius=3.0)[0]), len(M.pair_tracks(fr[0], fr[1], radius=0.5)[0])
+    print(f"radius 3.0: {int((nc == 1).sum())} previous keypoints with one candidate, {int((nc == 0).sum())} with none, {n3} tracks; radius 0.5: {n05}")
+    assert (nc == 1).sum() >= 100 and (nc == 0).sum() >= 1 and n3 >= 100 and n05 == 0
+
+
+def test_threshold_settings_change_the_counts(oracle):
+    fr = C.twin(oracle, "shift")
+    base = C.accepted(fr[0])
+    got = [C.accepted(C.restereo(fr[0], md, th)) for th, md in C.STEREO_SETTINGS]
+    print(f"stage S accepted at {C.STEREO_SETTINGS}: {got}, default {base}")
+    assert all(g != base for g in got)
+    assert got[0] < base < got[1] and got[3] > 0 and got[4] == 0            # th_stereo orders the counts; max_disparity 11 < 12 cuts all
+    base_t = len(M.pair_tracks(fr[0], fr[1])[0])
+    got_t = [len(M.pair_tracks(fr[0], fr[1], **kw)[0]) for kw in C.TRACK_SETTINGS]
+    print(f"stage T tracks at {C.TRACK_SETTINGS}: {got_t}, default {base_t}")
+    assert all(g != base_t for g in got_t)
+    # the boundary settings: the largest accepted distance b* sits on either side of < (stage S) and <= (stage T)
+    bs = int(C.stereo_best(fr[0]).max())
+    at, above = C.restereo(fr[0], 300.0, bs), C.restereo(fr[0], 300.0, bs + 1)
+    assert bs + 1 <= M.TH_STEREO and above["uR"].tobytes() == fr[0]["uR"].tobytes()
+    assert (C.stereo_best(at) < bs).all() and C.accepted(at) != C.accepted(above)
+    tr = M.pair_tracks(fr[0], fr[1])
+    bt = int(C.track_best(fr[0], fr[1], tr).max())
+    below, at = M.pair_tracks(fr[0], fr[1], th_track=bt - 1), M.pair_tracks(fr[0], fr[1], th_track=bt)
+    print(f"boundary: stage S b* = {bs}, stage T b* = {bt}: {len(below[0])} / {len(at[0])} tracks")
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(at, tr)) and len(below[0]) < len(at[0])
+
+
+def test_identical_pair_on_one_level_has_median_zero(oracle):
+    left, right = C.median_pair()
+    fr = M.frame_stereo(oracle, left, right, 300.0, orb=dict(nlevels=1))
+    assert len(fr["kL"]) >= 1000 and C.accepted(fr) == 0 and (fr["sad"] == -1).all()
+    assert (fr["j"] >= 0).sum() >= 1000                                      # ... although nearly every keypoint finds its partner
+    uncut = [M.sad(fr["patches"][i].reshape(11, 11), fr["levR"][0], int(fr["kL"]["x"][i]), int(fr["kL"]["y"][i])) for i in range(20)]
+    assert uncut == [0] * 20
+
+
+def test_clamp_pair_reaches_the_zero_disparity_clamp(oracle):
+    fr = M.frame_stereo(oracle, *C.clamp_pair(), 300.0)
+    acc = fr["uR"] >= 0
+    clamped = acc & (fr["uR"] == (fr["kL"]["x"] - F(0.01)).astype(F))
+    print(f"clamp pair: {int(acc.sum())} accepted, {int(clamped.sum())} clamped to uL - 0.01")
+    assert acc.sum() >= 300 and clamped.sum() >= 1
+    assert (fr["kL"]["x"][clamped] == np.round(fr["kL"]["x"][clamped])).all()
+
+
+def test_flat_sequence_records(oracle, small_seq):
+    seq, frames = small_seq
+    ref, fr = C.flat_ref(oracle, seq, frames)
+    got = [(r["ok"], r["fail_stage"], r["n_prev_kps"], r["n_cur_kps"], r["n_tracked"]) for r, _ in ref]
+    assert got == [(1, 0, 1490, 1503, 330), (0, 2, 1503, 0, 0), (0, 2, 0, 1507, 0), (1, 0, 1507, 1495, 346), (0, 2, 1495, 1495, 0)]
+    assert [C.accepted(f) for f in fr] == [905, 911, 0, 939, 0, 953]
+    assert len(fr[4]["kL"]) == 1495 and len(fr[4]["kR"]) == 0 and len(fr[2]["kL"]) == 0
+    # the pose chain skips the failed pairs
+    assert np.array_equal(ref[1][1], ref[0][1]) and np.array_equal(ref[2][1], ref[0][1]) and np.array_equal(ref[4][1], ref[3][1])
+    assert not np.array_equal(ref[3][1], ref[0][1])
