@@ -585,6 +585,7 @@ int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int height, int
  *       leaves *res and active untouched and still sets *n_out, the size to come back with. */
 #define SVO_REFINE_OFF    0
 #define SVO_REFINE_REPROJ 1
+#define SVO_REFINE_BA     2     /* two-frame stereo bundle adjustment: the block below; selected by svo_set_pose_refine_ba */
 #define SVO_REFINE_APPLIED  0
 #define SVO_REFINE_KEPT_PNP 1
 #define SVO_REFINE_SKIPPED  2
@@ -601,6 +602,59 @@ int svo_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left,
                     const double P1[12], const double P2[12], const double rvec0[3], const double tvec0[3],
                     svo_refine_result *res, uint8_t *active, int mem);
 int svo_get_refine_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out);
+
+/* ---- two-frame stereo bundle adjustment: the refinement stage's second mode (additive; detected by symbol, the ABI version
+ * stays 9 and svo_config / svo_step_result / svo_refine_result are unchanged) -------------------------------------------------
+ * SVO_REFINE_REPROJ treats the triangulated t1 points as exact.  They are not: they are the float32 triangulation of noisy t1
+ * tracks.  SVO_REFINE_BA is the maximum-likelihood estimator for a stereo pair of pairs instead: it minimises the
+ * reprojection error in all four images over the pose AND the points.  Every pair stays independent; OFF and REPROJ are byte
+ * for byte what they were.  rounds / iters / sigma_px / min_inliers keep their meaning and their ranges.
+ *
+ * Arithmetic, all in double (the numpy twin is tests/_ba_ref.py); R1-R7 are the rules above:
+ *   unknowns  the pose (R, t) of R2, started at the PnP record, and one X_i per point, started at (double) of the triangulated
+ *      float32 point.
+ *   views     as R1.  At t1 both views project X_i, at t2 they project Y_i = R X_i + t.  LK mode: four observations, d = 8
+ *      residuals per point (t1_left, t1_right, t2_left, t2_right).  ORB mode (both matchers): t1_left, t1_right, t2_left,
+ *      d = 6; its t2_right is not read.  svo_refine_ba: d = 8 when img2_right is given, else d = 6.  A point is projectable
+ *      when h2 > 1e-6 in every view used, at both times; otherwise its weight is 0, it is never active and it is never moved.
+ *   cost      c_i = |r_i|^2 / sigma^2; tau = 11.070 (d = 8) or 7.815 (d = 6): the chi-square 95 % points for d - 3 degrees of
+ *      freedom, three being absorbed by the point.
+ *   rounds    exactly R5 (Huber in rounds 0 and 1, plain afterwards, every projectable point re-classified after each round,
+ *      the estimate carried over).  A point that a re-classification leaves inactive returns to its triangulation: its
+ *      position means nothing by then (a gross outlier wanders off under the Huber weight), and a later re-admission is
+ *      judged on the triangulated point.
+ *   one LM iteration.  Per active point, with J_x (d x 3: the t1 rows du/dX, the t2 rows (du/dY) R) and J_p (the t2 rows only,
+ *      (du/dY) [I | -[Y]x]), weighted by w_i / sigma^2: V = J_x^T J_x, W = J_p^T J_x, U = J_p^T J_p, g_x = J_x^T r, g_p = J_p^T r;
+ *      V* = V + lambda diag V is factored by a 3 x 3 Cholesky; if a pivot is <= 0 the point contributes U, g_p only and is not
+ *      moved in this step.  Reduced system: H = sum (U - W V*^-1 W^T), g = sum (g_p - W V*^-1 g_x);
+ *      (H + lambda diag sum U) xi = -g by the 6 x 6 Cholesky of R6; dX_i = -V*^-1 (g_x + W^T xi).  The trial pose and all
+ *      trial points are accepted or rejected together by R6's test (the cost a (sum, remainder) pair; no active point may
+ *      become non-projectable); lambda's schedule and the exits are R6's, the short-step exit being |xi| < 1e-10 and
+ *      max |dX_i| < 1e-9 (Euclidean norm).
+ *   outcome   as R7, with info = the reduced H at lambda = 0 over the active points at the final estimate: the pose's marginal
+ *      information, the uncertainty of the structure included.  Same APPLIED / KEPT_PNP / SKIPPED rules; the PnP record's rvec /
+ *      tvec / R are overwritten when applied; n_inliers, ransac_iters, lm_iters and the RANSAC mask stay RANSAC's.  When the
+ *      PnP pose is kept the points that stand are the triangulated ones.  svo_refine_result.views is the number of t2 views.
+ *   svo_set_pose_refine_ba : selects the mode, with svo_set_pose_refine's other arguments, ranges and errors;
+ *       svo_get_pose_refine then reports mode SVO_REFINE_BA, and svo_set_pose_refine(OFF or REPROJ) leaves it.  The mode has a
+ *       setter of its own because svo_set_pose_refine's contract is to refuse every mode but OFF and REPROJ, and it still
+ *       does.  Every fused entry point then runs pose_ba_kernel where it would run
+ *       pose_refine_kernel.  The first call that selects the mode (or the first svo_refine_ba) allocates, beside the stage's
+ *       block, 48 bytes x (max_batch + 1) x max_keypoints + 16 bytes x max_keypoints (two buffers of double points per pair,
+ *       stage-call scratch; 256 pairs x 8192 points: 101 MB) and waits for the device; a context that never does allocates
+ *       nothing.  svo_get_refine_result works unchanged.
+ *   svo_refine_ba (stage API): the same kernel on a caller's points (n <= max_keypoints) with the CURRENT settings, whatever
+ *       the mode.  obj, img*, active and X_out (n x 3 doubles, the points that stand; may be NULL) follow `mem`; img2_right may
+ *       be NULL (d = 6); res is a HOST struct.  The start pose is (Rodrigues(rvec0), tvec0).
+ *   svo_get_refine_points : the points that stand of pair `pair` of the most recent fused launch, addressed as
+ *       svo_get_refine_result addresses pairs; HOST pointer, *n_out = n_points.  SVO_ERR_ARG unless that launch ran in
+ *       SVO_REFINE_BA mode, when pair is out of range or cap < n_points (X may be NULL: cap is ignored; *n_out is still set). */
+int svo_set_pose_refine_ba(svo_ctx *ctx, int rounds, int iters, double sigma_px, int min_inliers);
+int svo_refine_ba(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img1_left, const svo_pt2f *img1_right,
+                  const svo_pt2f *img2_left, const svo_pt2f *img2_right /* may be NULL */, int n, const double P1[12],
+                  const double P2[12], const double rvec0[3], const double tvec0[3], svo_refine_result *res, uint8_t *active,
+                  double *X_out /* n x 3 doubles, may be NULL */, int mem);
+int svo_get_refine_points(svo_ctx *ctx, int pair, double *X, int cap, int *n_out);
 
 /* ---- guided ORB matcher: epipolar stereo and sub-pixel refinement (additive; detected by symbol, the ABI version stays 9 and
  * svo_config / svo_step_result are unchanged) -------------------------------------------------------------------------------

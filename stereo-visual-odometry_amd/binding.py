@@ -53,7 +53,7 @@ class RefineResult(C.Structure):
 
 
 ORB_MATCHER_BRUTE, ORB_MATCHER_GUIDED = 0, 1                                               # svo_set_orb_matcher
-REFINE_OFF, REFINE_REPROJ = 0, 1                                       # svo_set_pose_refine
+REFINE_OFF, REFINE_REPROJ, REFINE_BA = 0, 1, 2                          # svo_set_pose_refine
 REFINE_APPLIED, REFINE_KEPT_PNP, REFINE_SKIPPED = 0, 1, 2              # svo_refine_result.status
 
 
@@ -163,6 +163,10 @@ def load_library():
     lib.svo_refine_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.POINTER(RefineResult), C.c_void_p, C.c_int]
     lib.svo_get_refine_result.argtypes = [C.c_void_p, C.c_int, C.POINTER(RefineResult), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_set_pose_refine_ba.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int]
+    lib.svo_refine_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.POINTER(RefineResult), C.c_void_p, C.c_void_p, C.c_int]
+    lib.svo_get_refine_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     # guided ORB matcher (additive entry points, like the stream sets)
     lib.svo_set_orb_matcher.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
     lib.svo_get_orb_matcher.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -453,11 +457,15 @@ class Context:
 
     # ---- robust two-view pose refinement after solvePnPRansac (svo_set_pose_refine) -----------
     def set_pose_refine(self, mode, rounds=4, iters=10, sigma_px=1.0, min_inliers=6):
-        """"reproj": every fused entry point refines each pair's PnP pose on both cameras' t2 observations; "off": as before."""
-        names = {"off": REFINE_OFF, "none": REFINE_OFF, "reproj": REFINE_REPROJ}
+        """"reproj": every fused entry point refines each pair's PnP pose on both cameras' t2 observations; "ba": it adjusts the
+        pose and the triangulated points together on the observations of both times; "off": as before."""
+        names = {"off": REFINE_OFF, "none": REFINE_OFF, "reproj": REFINE_REPROJ, "ba": REFINE_BA}
         m = names[mode] if isinstance(mode, str) and mode in names else mode
         if isinstance(m, str):
-            raise SvoError(f"pose refinement mode must be 'reproj' or 'off', not {mode!r}")
+            raise SvoError(f"pose refinement mode must be 'reproj', 'ba' or 'off', not {mode!r}")
+        if m == REFINE_BA:                 # (svo_set_pose_refine refuses every mode but OFF and REPROJ: the mode has its own setter)
+            self._check(self.lib.svo_set_pose_refine_ba(self.h, int(rounds), int(iters), float(sigma_px), int(min_inliers)))
+            return
         self._check(self.lib.svo_set_pose_refine(self.h, int(m), int(rounds), int(iters), float(sigma_px), int(min_inliers)))
 
     def pose_refine(self):
@@ -465,7 +473,7 @@ class Context:
         m, r, i, n = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         sg = C.c_double()
         self._check(self.lib.svo_get_pose_refine(self.h, C.byref(m), C.byref(r), C.byref(i), C.byref(sg), C.byref(n)))
-        return ("reproj" if m.value == REFINE_REPROJ else "off"), r.value, i.value, sg.value, n.value
+        return {REFINE_REPROJ: "reproj", REFINE_BA: "ba"}.get(m.value, "off"), r.value, i.value, sg.value, n.value
 
     @staticmethod
     def _refine_dict(res, active):
@@ -518,6 +526,56 @@ class Context:
         n = C.c_int(0)
         self._check(self.lib.svo_get_refine_result(self.h, int(pair), C.byref(res), C.c_void_p(act.ctypes.data), cap, C.byref(n)))
         return self._refine_dict(res, act[:n.value].copy())
+
+    def refine_ba(self, obj, img1_left, img1_right, img2_left, img2_right, P1, P2, rvec0, tvec0):
+        """svo_refine_ba: the stage's bundle-adjustment mode on a caller's points (numpy arrays, or cuda tensors) with the
+        current settings; img2_right None: three views.  The dict of refine_pose plus 'X', the (n, 3) float64 points that stand."""
+        P1 = np.ascontiguousarray(P1, np.float64).reshape(12)
+        P2 = np.ascontiguousarray(P2, np.float64).reshape(12)
+        r0 = np.ascontiguousarray(rvec0, np.float64).reshape(3)
+        t0 = np.ascontiguousarray(tvec0, np.float64).reshape(3)
+        obs = [("img1_left", img1_left), ("img1_right", img1_right), ("img2_left", img2_left), ("img2_right", img2_right)]
+        if any(o is None for _, o in obs[:3]):
+            raise SvoError("refine_ba: only img2_right may be None")
+        if isinstance(obj, np.ndarray):
+            obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
+            obs = [(k, None if o is None else np.ascontiguousarray(o, np.float32).reshape(-1, 2)) for k, o in obs]
+            act = np.zeros(max(obj.shape[0], 1), np.uint8)
+            X = np.zeros((max(obj.shape[0], 1), 3), np.float64)
+        else:
+            import torch
+            for name, t, cols in [("obj", obj, 3)] + [(k, o, 2) for k, o in obs]:
+                if t is None:
+                    continue
+                if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols and t.is_contiguous()
+                        and t.device == obj.device and t.shape[0] == obj.shape[0]):
+                    raise SvoError(f"refine_ba: {name} must be a contiguous float32 tensor of shape (n, {cols}) on the device of obj")
+            act = torch.zeros(max(obj.shape[0], 1), dtype=torch.uint8, device=obj.device)
+            X = torch.zeros((max(obj.shape[0], 1), 3), dtype=torch.float64, device=obj.device)
+            self._order_in(X)
+        n = obj.shape[0]
+        if any(o is not None and o.shape[0] != n for _, o in obs):
+            raise SvoError("refine_ba: obj and the observation lists must have the same number of points")
+        res = RefineResult()
+        po, mem = _ptr(obj)
+        self._check(self.lib.svo_refine_ba(self.h, po, *[_ptr(o)[0] for _, o in obs], n, C.c_void_p(P1.ctypes.data),
+                                           C.c_void_p(P2.ctypes.data), C.c_void_p(r0.ctypes.data), C.c_void_p(t0.ctypes.data),
+                                           C.byref(res), _ptr(act)[0], _ptr(X)[0], mem))
+        if mem == MEM_DEVICE:
+            self._order_out(X)
+            act, X = act.cpu().numpy(), X.cpu().numpy()
+        out = self._refine_dict(res, np.asarray(act[:n]).copy())
+        out["X"] = np.asarray(X[:n]).copy()
+        return out
+
+    def refine_points(self, pair=0, cap=None):
+        """svo_get_refine_points: the (n, 3) float64 points that stand of pair `pair` of the most recent fused launch, which
+        must have run in "ba" mode."""
+        cap = int(self.cfg.max_keypoints) if cap is None else int(cap)
+        X = np.zeros((max(cap, 1), 3), np.float64)
+        n = C.c_int(0)
+        self._check(self.lib.svo_get_refine_points(self.h, int(pair), C.c_void_p(X.ctypes.data), cap, C.byref(n)))
+        return X[:n.value].copy()
 
     # ---- ORB path ---------------------------------------------------------------------------
     def orb_extract(self, img, cap=None):

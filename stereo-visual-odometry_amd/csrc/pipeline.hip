@@ -310,8 +310,10 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
     if (!side) mark(ctx, kTPnp);
     // svo_set_pose_refine: robust two-view refinement of every pair's PnP record in place, before the gates read it
     ctx->refine_last_pairs = ctx->refine_mode != SVO_REFINE_OFF ? n_pairs : 0;
+    ctx->refine_last_mode = ctx->refine_mode;
     if (ctx->refine_last_pairs) {
-        launch_refine_batch(ctx, n_pairs, bs);
+        if (ctx->refine_mode == SVO_REFINE_BA) launch_ba_batch(ctx, n_pairs, bs);
+        else launch_refine_batch(ctx, n_pairs, bs);
         if (!side) mark(ctx, kTRefine);
     }
     const int *ovf = ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->kp_n_snap + 2 * n_pairs : nullptr;

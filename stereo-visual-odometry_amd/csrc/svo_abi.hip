@@ -1593,18 +1593,31 @@ extern "C" int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int 
 }
 
 // ---- robust two-view pose refinement after solvePnPRansac (refine.hip: pose_refine_kernel) ----------------------------
-extern "C" int svo_set_pose_refine(svo_ctx *ctx, int mode, int rounds, int iters, double sigma_px, int min_inliers)
+static int set_pose_refine(svo_ctx *ctx, int mode, int rounds, int iters, double sigma_px, int min_inliers)
 {
-    if (!ctx) return SVO_ERR_ARG;
-    SVO_ARG(mode == SVO_REFINE_OFF || mode == SVO_REFINE_REPROJ, "mode must be SVO_REFINE_OFF or SVO_REFINE_REPROJ");
     SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
     SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
     SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
     SVO_ARG(min_inliers >= 1, "min_inliers < 1");
-    if (mode != SVO_REFINE_OFF) { const int rc = refine_alloc(ctx); if (rc) return rc; }
+    if (mode != SVO_REFINE_OFF) { const int rc = mode == SVO_REFINE_BA ? ba_alloc(ctx) : refine_alloc(ctx); if (rc) return rc; }
     ctx->refine_mode = mode; ctx->refine_rounds = rounds; ctx->refine_iters = iters;
     ctx->refine_sigma = sigma_px; ctx->refine_min_inliers = min_inliers;
     return SVO_OK;
+}
+
+extern "C" int svo_set_pose_refine(svo_ctx *ctx, int mode, int rounds, int iters, double sigma_px, int min_inliers)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(mode == SVO_REFINE_OFF || mode == SVO_REFINE_REPROJ, "mode must be SVO_REFINE_OFF or SVO_REFINE_REPROJ");
+    return set_pose_refine(ctx, mode, rounds, iters, sigma_px, min_inliers);
+}
+
+// the stage's third mode has a setter of its own: svo_set_pose_refine goes on refusing every mode but OFF and REPROJ, as its
+// callers were told it does
+extern "C" int svo_set_pose_refine_ba(svo_ctx *ctx, int rounds, int iters, double sigma_px, int min_inliers)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return set_pose_refine(ctx, SVO_REFINE_BA, rounds, iters, sigma_px, min_inliers);
 }
 
 extern "C" int svo_get_pose_refine(const svo_ctx *ctx, int *mode, int *rounds, int *iters, double *sigma_px, int *min_inliers)
@@ -1635,4 +1648,26 @@ extern "C" int svo_get_refine_result(svo_ctx *ctx, int pair, svo_refine_result *
     SVO_HIP(hipSetDevice(ctx->device));
     if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
     return refine_read_result(ctx, pair, res, active, cap, n_out);
+}
+
+// ---- the stage's bundle-adjustment mode (ba.hip: pose_ba_kernel) -------------------------------------------------------
+extern "C" int svo_refine_ba(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img1_left, const svo_pt2f *img1_right,
+                             const svo_pt2f *img2_left, const svo_pt2f *img2_right, int n, const double P1[12], const double P2[12],
+                             const double rvec0[3], const double tvec0[3], svo_refine_result *res, uint8_t *active, double *X_out,
+                             int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return stage_refine_ba(ctx, obj, img1_left, img1_right, img2_left, img2_right, n, P1, P2, rvec0, tvec0, res, active, X_out, mem);
+}
+
+extern "C" int svo_get_refine_points(svo_ctx *ctx, int pair, double *X, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->refine_last_pairs > 0 && ctx->refine_last_mode == SVO_REFINE_BA && ctx->ba_buf,
+            "the last launch did not run in SVO_REFINE_BA mode (svo_set_pose_refine_ba)");
+    SVO_ARG(pair >= 0 && pair < ctx->refine_last_pairs, "pair is not part of the last launch");
+    SVO_ARG(X == nullptr || cap >= 0, "negative capacity");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    return ba_read_points(ctx, pair, X, cap, n_out);
 }

@@ -200,6 +200,8 @@ struct svo_ctx {
     double refine_sigma = 1.0;
     uint8_t *refine_buf = nullptr;                       // ONE block: records, per-point flags, stage-call scratch (refine.hip)
     int refine_last_pairs = 0;                           // pairs the stage refined in the most recent fused launch (0: it was off)
+    int refine_last_mode = SVO_REFINE_OFF;               // ... and the mode that launch ran in
+    uint8_t *ba_buf = nullptr;                           // SVO_REFINE_BA: the pairs' points, two buffers, + stage-call scratch (ba.hip)
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -261,6 +263,13 @@ void launch_refine_batch(svo_ctx *ctx, int n_pairs, hipStream_t st);
 int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_left, const svo_pt2f *img_right, int n, const double P1[12],
                       const double P2[12], const double rvec0[3], const double tvec0[3], svo_refine_result *res, uint8_t *active, int mem);
 int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out);
+// ba.hip: pose_ba_kernel, the stage's SVO_REFINE_BA mode (pose and points together); same records, same flags
+int ba_alloc(svo_ctx *ctx);                              // refine_alloc + the mode's point buffers, on first use
+void launch_ba_batch(svo_ctx *ctx, int n_pairs, hipStream_t st);
+int stage_refine_ba(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img1_left, const svo_pt2f *img1_right, const svo_pt2f *img2_left,
+                    const svo_pt2f *img2_right, int n, const double P1[12], const double P2[12], const double rvec0[3],
+                    const double tvec0[3], svo_refine_result *res, uint8_t *active, double *X_out, int mem);
+int ba_read_points(svo_ctx *ctx, int pair, double *X, int cap, int *n_out);
 // orb.hip
 int orb_alloc(svo_ctx *ctx);
 int orb_max_keypoints(const svo_ctx *ctx);             // what one image holds at most: the level quotas + 8 each, capped at orb_kp_cap

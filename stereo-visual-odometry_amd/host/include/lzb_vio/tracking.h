@@ -62,7 +62,7 @@ public:
     // quality level that is not a finite number > 0, a negative or non-finite distance, and gftt together with ORB mode, the
     // FAST buckets or fast_keep_strongest are refused (false + a message that names the key).  Applied right after svo_create.
     static bool ReadLkDetector(int *detector, int *max_corners, double *quality_level, double *min_distance, std::string *err);
-    // additive YAML keys pose_refine: none | reproj (absent: none), pose_refine_rounds (4), pose_refine_iters (10),
+    // additive YAML keys pose_refine: none | reproj | ba (absent: none), pose_refine_rounds (4), pose_refine_iters (10),
     // pose_refine_sigma (1.0 px) and pose_refine_min_inliers (6): the robust two-view pose refinement after solvePnPRansac
     // (svo_set_pose_refine, include/svo_abi.h).  ReadPoseRefine reads and checks them for the loaded YAML: an unknown mode,
     // rounds outside 1..16, iterations outside 1..100, a sigma that is not a finite number > 0, min_inliers < 1 -> false, *err

@@ -81,13 +81,13 @@ bool Tracking::ReadPoseRefine(int *mode, int *rounds, int *iters, double *sigma_
     const double sg = Config::Has("pose_refine_sigma") ? Config::Get<double>("pose_refine_sigma") : 1.0;
     const int mi = Config::Has("pose_refine_min_inliers") ? Config::Get<int>("pose_refine_min_inliers") : 6;
     char msg[240] = "";
-    if (m != "none" && m != "reproj") snprintf(msg, sizeof(msg), "pose_refine: '%s' is neither 'none' nor 'reproj'", m.c_str());
+    if (m != "none" && m != "reproj" && m != "ba") snprintf(msg, sizeof(msg), "pose_refine: '%s' is neither 'none', 'reproj' nor 'ba'", m.c_str());
     else if (r < 1 || r > 16) snprintf(msg, sizeof(msg), "pose_refine_rounds: %d is outside 1..16", r);
     else if (it < 1 || it > 100) snprintf(msg, sizeof(msg), "pose_refine_iters: %d is outside 1..100", it);
     else if (!(std::isfinite(sg) && sg > 0.0)) snprintf(msg, sizeof(msg), "pose_refine_sigma: %g is not a finite number > 0", sg);
     else if (mi < 1) snprintf(msg, sizeof(msg), "pose_refine_min_inliers: %d is < 1", mi);
     if (msg[0]) { if (err) *err = msg; return false; }
-    *mode = m == "reproj" ? SVO_REFINE_REPROJ : SVO_REFINE_OFF;
+    *mode = m == "reproj" ? SVO_REFINE_REPROJ : m == "ba" ? SVO_REFINE_BA : SVO_REFINE_OFF;
     *rounds = r; *iters = it; *sigma_px = sg; *min_inliers = mi;
     return true;
 }
@@ -173,9 +173,9 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
     if (!ReadPoseRefine(&pose_refine_, &pose_refine_rounds_, &pose_refine_iters_, &pose_refine_sigma_, &pose_refine_min_inliers_,
                         &refine_error)) {
         if (config_error_.empty()) config_error_ = refine_error;
-    } else if (pose_refine_ == SVO_REFINE_REPROJ)
-        LZB_LOG("INFO", "pose_refine: reproj (pose_refine_rounds %d, pose_refine_iters %d, pose_refine_sigma %g, pose_refine_min_inliers %d)",
-                pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_);
+    } else if (pose_refine_ != SVO_REFINE_OFF)
+        LZB_LOG("INFO", "pose_refine: %s (pose_refine_rounds %d, pose_refine_iters %d, pose_refine_sigma %g, pose_refine_min_inliers %d)",
+                pose_refine_ == SVO_REFINE_BA ? "ba" : "reproj", pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_);
     std::string matcher_error;
     if (!ReadOrbMatcher(&orb_matcher_, &orb_match_th_stereo_, &orb_match_th_track_, &orb_match_ratio_, &orb_match_radius_,
                         &orb_max_disparity_, &matcher_error)) {
@@ -314,10 +314,13 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
         return false;
     }
     // (also while the mode is none: svo_refine_pose, behind G2O_EstimatePose_PnP, runs with the context's settings; nothing is allocated then)
-    if ((rc = svo_set_pose_refine(ctx_, pose_refine_, pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_,
-                                  pose_refine_min_inliers_)) != SVO_OK) {
-        LZB_LOG("ERROR", "svo_set_pose_refine (pose_refine %s, rounds %d, iters %d, sigma %g, min_inliers %d) failed (%d): %s",
-                pose_refine_ == SVO_REFINE_REPROJ ? "reproj" : "none", pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_, rc, svo_last_error(ctx_));
+    rc = pose_refine_ == SVO_REFINE_BA
+             ? svo_set_pose_refine_ba(ctx_, pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_)
+             : svo_set_pose_refine(ctx_, pose_refine_, pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_);
+    if (rc != SVO_OK) {
+        LZB_LOG("ERROR", "%s (pose_refine %s, rounds %d, iters %d, sigma %g, min_inliers %d) failed (%d): %s",
+                pose_refine_ == SVO_REFINE_BA ? "svo_set_pose_refine_ba" : "svo_set_pose_refine",
+                pose_refine_ == SVO_REFINE_REPROJ ? "reproj" : pose_refine_ == SVO_REFINE_BA ? "ba" : "none", pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""The pose refinement stage (svo_set_pose_refine) off and on (bench.py stays the one-line contract).
+"""The pose refinement stage (svo_set_pose_refine) off and in its two modes (bench.py stays the one-line contract).
 
 At 1241x376 on the rendered corridor tools/trajectory_check.py uses, frames resident in HBM, 256 pairs per svo_track_batch
 step, overlap mode as in bench.py's headline, one process run on one box:
 
-  lk_off / lk_on                    LK mode, lk_accum exact, every cv::FAST corner
-  orb_off / orb_on                  ORB mode (view L only: it has no t2_right)
-  lk_buckets_off / lk_buckets_on    LK mode with the 4 strongest FAST corners per 50 x 50 pixel cell
-  lk_off_again                      the first row once more: the run's own spread
+  lk_off / lk_on / lk_ba                          LK mode, lk_accum exact, every cv::FAST corner
+  orb_off / orb_on / orb_ba                       ORB mode (it has no t2_right: one view at t2)
+  lk_buckets_off / lk_buckets_on / lk_buckets_ba  LK mode with the 4 strongest FAST corners per 50 x 50 pixel cell
+  lk_off_again                                    the first row once more: the run's own spread
+
+_off: the stage off; _on: pose_refine reproj (the pose on both cameras' t2 observations, the triangulated points held fixed);
+_ba: pose_refine ba (the two-frame stereo bundle adjustment: pose and points on the observations of both times).
 
 Per row: ms per step and pairs/s over at least one second of steps that ends in a synchronise; the `pnp` and `refine` stages
 of svo_get_timing from a second, short run WITHOUT overlap (in overlap mode the pose stage runs on the side stream, where no
@@ -16,7 +19,9 @@ LM iterations and the share of pairs whose refined pose was applied; and, from a
 tools/trajectory_check.py does, the relative-pose errors and the end-point drift against the renderer's ground truth.
 No figure here is a pass bar.
 
-Usage: python tools/bench_refine.py [--out profiles/refine_bench.json] [--frames 301]
+Usage: python tools/bench_refine.py [--out profiles/refine_ba_bench.json] [--frames 301]
+The rows and the default --out are not those of the earlier profiles/refine_bench.json (off / reproj rows only, written by this
+tool before it had ba rows): that file is kept as the record of its run and is no longer what a default invocation regenerates.
 The document goes to stdout and to --out; --merge FILE copies every key of FILE this tool does not write itself (the bench.py
 runs against the parent commit are recorded there by hand)."""
 import argparse
@@ -37,7 +42,7 @@ from bench_detectors import B, CELL, H, MIN_SECONDS, W, timed, trajectory  # noq
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_bench.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_ba_bench.json"))
     ap.add_argument("--frames", type=int, default=301)
     ap.add_argument("--merge", default="")
     args = ap.parse_args()
@@ -62,8 +67,8 @@ def main():
             c = pkg.Context(W, H, device=0, max_batch=max_batch, P1=P1, P2=P2, **kw)
             if per_cell:
                 c.set_fast_buckets(CELL, CELL, per_cell)
-            if refine:
-                c.set_pose_refine("reproj")
+            if refine != "off":
+                c.set_pose_refine(refine)
             return c
         ctx = make_ctx(B)
         ctx.set_stream(stream.cuda_stream)
@@ -78,7 +83,7 @@ def main():
         per, steps, dt = timed(step, sync)
         rec = np.frombuffer(bufs[1].cpu().numpy().tobytes(), dtype=pkg.STEP_DTYPE)
         stats = None
-        if refine:
+        if refine != "off":
             rr = [ctx.refine_result(p) for p in range(B)]
             stats = {"mean_n_active": float(np.mean([r["n_active"] for r in rr])), "mean_iters": float(np.mean([r["iters"] for r in rr])),
                      "applied_share": float(np.mean([r["status"] == pkg.REFINE_APPLIED for r in rr])),
@@ -93,7 +98,7 @@ def main():
         stages = dict(ctx.get_timing())
         ctx.enable_timing(False)
         ctx.close()
-        row = {"config": name, "mode": "orb" if orb else "lk", "pose_refine": "reproj" if refine else "off",
+        row = {"config": name, "mode": "orb" if orb else "lk", "pose_refine": refine,
                "cell": [CELL, CELL] if per_cell else None, "per_cell": per_cell,
                "step_ms": per * 1e3, "pairs_per_s": B / per, "steps_timed": steps, "seconds": dt,
                "pnp_stage_ms": float(stages.get("pnp", 0.0)), "refine_stage_ms": float(stages["refine"]) if "refine" in stages else None,
@@ -104,10 +109,10 @@ def main():
         print(json.dumps(row), file=sys.stderr, flush=True)
         return row
 
-    rows = [measure("lk_off", False), measure("lk_on", True),
-            measure("orb_off", False, orb=True), measure("orb_on", True, orb=True),
-            measure(f"lk_buckets_{CELL}x{CELL}_4_off", False, per_cell=4), measure(f"lk_buckets_{CELL}x{CELL}_4_on", True, per_cell=4),
-            measure("lk_off_again", False)]
+    rows = []
+    for base, kw in (("lk", {}), ("orb", dict(orb=True)), (f"lk_buckets_{CELL}x{CELL}_4", dict(per_cell=4))):
+        rows += [measure(f"{base}_{tag}", mode, **kw) for tag, mode in (("off", "off"), ("on", "reproj"), ("ba", "ba"))]
+    rows.append(measure("lk_off_again", "off"))
     doc = {"width": W, "height": H, "pairs_per_step": B, "lk_accum": "exact", "frames": "HBM", "overlap": True,
            "min_seconds": MIN_SECONDS, "device": torch.cuda.get_device_name(0),
            "pose_refine_settings": {"rounds": 4, "iters": 10, "sigma_px": 1.0, "min_inliers": 6}, "rows": rows}
