@@ -21,10 +21,13 @@ __device__ inline double refine_wave_allsum(double v)
 // The cost of a round is carried as an unevaluated pair (s, e): TwoSum keeps what every addition rounds away.  "The cost
 // decreases" (R6) is decided on the pair, so the decision does not depend on the order the lanes add in (a plain sum of ~1000
 // terms carries ~1e-13 of order-dependent noise).  The terms' own rounding -- u - x cancels at ~1e2 px -- remains.
+__device__ inline bool refine_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }    // false for NaN and +-inf
+
 __device__ inline void refine_dd_add(double &s, double &e, double bs, double be)
 {
     const double t = s + bs, bb = t - s;
-    const double err = (s - (t - bb)) + (bs - bb);
+    // (an infinite sum has no tail: inf - inf would turn the infinite cost of an inf pixel into NaN)
+    const double err = refine_finite(t) ? (s - (t - bb)) + (bs - bb) : 0.0;
     s = t;
     e = (e + be) + err;
 }
@@ -138,8 +141,6 @@ __device__ inline bool refine_chol6(const double (&A)[36], const double (&b)[6],
     }
     return ok;
 }
-
-__device__ inline bool refine_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }    // false for NaN and +-inf
 
 // ---- the stage's device block: [records x (B + 1)][flags x (B + 1) x cap][stage-call X, xl, xr x cap]; item B is the stage call's
 struct RefineCut { size_t flags, X, xl, xr, end; };

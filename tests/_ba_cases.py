@@ -189,3 +189,205 @@ def default_run(rig, n, kind, d):
         c = make_case(rig, n, kind, SEED0 + 2000)
         _CACHE[key] = (c, run_twin(c, d, rounds=4, iters=10))
     return _CACHE[key]
+
+
+# ==== the fixtures of tests/test_gpu_refine_edges.py (tests/test_ba_ref.py proves on the CPU that each reaches its path) =======
+# Every one is run at settings(n) -- 4 x 2 -- unless its own settings are named, and must meet fixture_ok.
+EDGE_N = (65, 257)                               # one point past a wave, one past the workgroup stride
+EDGE_KINDS = ("outliers", "some_behind")
+SIGMAS = (0.5, 0.75, 2.0)
+
+
+def absdiff(a, b):
+    """max |a - b| where an entry that is the same non-finite number on both sides counts as equal, any other non-finite
+    difference as inf (the fixtures with a spoiled point carry that point's NaN / inf through)."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if a.size == 0:
+        return 0.0
+    with np.errstate(invalid="ignore"):
+        d = np.abs(a - b)
+    same = ~np.isfinite(a) & ((a == b) | (np.isnan(a) & np.isnan(b)))
+    d = np.where(same, 0.0, d)
+    return float(np.where(np.isnan(d), np.inf, d).max())
+
+
+def edge_spread(c, d, run, **kw):
+    """self_spread, with the non-finite entries of a spoiled point compared as what they are."""
+    r = run_twin(c, d, t0=c["t0"] + 1e-15 * np.random.default_rng(1).standard_normal(3), **kw)
+    if not (np.array_equal(r["active"], run["active"]) and r["status"] == run["status"]):
+        return np.inf
+    return max(absdiff(r["t_ref"], run["t_ref"]), absdiff(r["rvec_ref"], run["rvec_ref"]), absdiff(r["X_ref"], run["X_ref"]))
+
+
+def edge_ok(run, spread, tight):
+    """fixture_ok, and where a trial was rejected for a point that stopped being projectable (the twin's log names it), that
+    point's depth 1e-6 m or more from the cut: that decision does not hang on a last bit either."""
+    return fixture_ok(run, spread, tight) and all(s[1] >= 1e-6 for e in run["log"] for s in e["steps"] if s[0] == "unprojectable")
+
+
+def rig_cases():
+    """Section A: the rigs with fy != fx (R1) and K2 != K1 (R2)."""
+    return [(rig, n, kind, d) for rig in ("R1", "R2") for d in (6, 8) for kind in EDGE_KINDS for n in EDGE_N]
+
+
+def sigma_cases():
+    """Section B: sigma as data, one four-view and one three-view fixture per value."""
+    return [(rig, n, kind, d, s) for s in SIGMAS for rig, n, kind, d in (("R0", 65, "some_behind", 8), ("R3", 257, "some_behind", 6))]
+
+
+# per edge case, the first offset from SEED0 for which fixture_ok holds (and, for sigma = 0.5, the final flags differ from the
+# sigma = 1 run of the same data); find_edge_offsets() below
+EDGE_SEED_OFFSET = {
+    ('R1', 65, 'outliers', 6): 1,
+    ('R1', 65, 'outliers', 8): 1,
+    ('R1', 257, 'some_behind', 6): 1,
+    ('R2', 65, 'outliers', 6): 2,
+    ('R2', 65, 'outliers', 8): 3,
+    ('R2', 65, 'some_behind', 6): 2,
+    ('R2', 65, 'some_behind', 8): 6,
+    ('R2', 257, 'outliers', 8): 1,
+    ('R0', 65, 'some_behind', 8, 2.0): 1,
+}
+
+
+def edge_run(rig, n, kind, d, sigma=1.0, seed=None):
+    """(case, twin run, twin's own spread) of a rig or sigma case, computed once per session and shared."""
+    key = ("edge", rig, n, kind, d, sigma, seed)
+    if key not in _CACHE:
+        off = EDGE_SEED_OFFSET.get((rig, n, kind, d) if sigma == 1.0 else (rig, n, kind, d, sigma), 0)
+        c = make_case(rig, n, kind, SEED0 + off if seed is None else seed)
+        run = run_twin(c, d, sigma=sigma)
+        _CACHE[key] = (c, run, self_spread(c, d, run, sigma=sigma))
+    return _CACHE[key]
+
+
+def wrong_intrinsics(c):
+    """The case with the mistake its rig exists to catch: R1 -- fy read where fx stands; R2 -- the left camera's intrinsics
+    used for the right one (the left 3 x 3 of P2 becomes K1 R_rl; the fourth column stands)."""
+    w = dict(c)
+    P1, P2 = c["P1"].copy(), c["P2"].copy()
+    if c["rig"] == "R1":
+        P1[1, 1] = P1[0, 0]
+    else:
+        r = _rigs.RIGS[c["rig"]]
+        P2[:, :3] = P1[:, :3] @ np.asarray(r.get("R_rl", np.eye(3)), np.float64)
+    w.update(P1=P1, P2=P2)
+    return w
+
+
+def find_edge_offsets(tight=1e-9, limit=60):
+    """Maintenance helper: the EDGE_SEED_OFFSET table."""
+    table = {}
+    for case in rig_cases() + sigma_cases():
+        sigma = case[4] if len(case) == 5 else 1.0
+        for off in range(limit):
+            c, run, spread = edge_run(*case[:4], sigma=sigma, seed=SEED0 + off)
+            ok = edge_ok(run, spread, tight)
+            if ok and sigma == 0.5:
+                ok = not np.array_equal(run["active"], run_twin(c, case[3])["active"])
+            if ok:
+                if off:
+                    table[case] = off
+                break
+        else:
+            raise RuntimeError(f"no seed for {case}")
+    return table
+
+
+# ---- the lambda exit: the exact scene started AT the true pose.  Every residual is exactly 0, the trial cost 0 is not below
+# the cost 0, fifteen steps are rejected (lambda 1e-4 -> 1e11) and the round leaves through lam > 1e10; nothing is rounded,
+# so the tie is exact on both sides.
+def lambda_case():
+    c = exact_case()
+    c.update(rvec0=np.zeros(3), t0=c["t_true"].copy())
+    return c
+
+
+LAMBDA_KW = (dict(rounds=1, iters=20), dict(rounds=2, iters=16))          # 15 and 30 iterations
+
+
+# ---- a trial rejected because an active point stops being projectable.  15 % of the points lie 0.3 .. 0.6 m in front of the
+# t2 camera; from 0.5 m off along -z a step moves the pose (and the points) far enough for one of them to end behind a camera
+# while the cost over the others falls: the bad count alone rejects the step.
+NEAR_KW = dict(rounds=1, iters=6)
+NEAR_SEED = {6: 1, 8: 0}
+
+
+def near_case(d, seed=None, n=300, share=0.15, off=0.5, noise=0.3, rig="R0", outlier_share=0.3):
+    seed = NEAR_SEED[d] if seed is None else seed
+    P1, P2 = _rigs.matrices(rig)
+    rng = np.random.default_rng([SEED0, seed, 77])
+    R, t = RC.true_pose()
+    K1 = np.zeros((3, 4))
+    K1[:, :3] = [[P1[0, 0], 0, P1[0, 2]], [0, P1[1, 1], P1[1, 2]], [0, 0, 1]]
+    u, v, z = rng.uniform(40, _rigs.W - 40, n), rng.uniform(20, _rigs.H - 20, n), rng.uniform(4.0, 40.0, n)
+    near = rng.permutation(n)[:int(share * n)]
+    z[near] = rng.uniform(0.3, 0.6, len(near))
+    Y = np.stack([(u - K1[0, 2]) / K1[0, 0] * z, (v - K1[1, 2]) / K1[1, 1] * z, z], 1)
+    X = ((Y - t) @ R).astype(np.float32).astype(np.float64)
+    Y = X @ R.T + t
+    obs = [(RC.project(P, Z) + noise * rng.standard_normal((n, 2))).astype(np.float32) for Z in (X, Y) for P in (K1, P2)]
+    outlier = np.zeros(n, bool)
+    outlier[rng.permutation(n)[:int(outlier_share * n)]] = True
+    ang, rad = rng.uniform(0, 2 * np.pi, outlier.sum()), rng.uniform(15.0, 80.0, outlier.sum())      # gross, as make_case's
+    o2 = np.stack([rad * np.cos(ang), rad * np.sin(ang)], 1).astype(np.float32)
+    obs[2][outlier] += o2
+    obs[3][outlier] -= o2[:, ::-1]
+    X0 = np.ascontiguousarray(conftest.entry.load_oracle().triangulate(P1, P2, obs[0], obs[1]), np.float32)
+    R0, _ = RC.start_pose()
+    return dict(rig=rig, P1=P1, P2=P2, X=X.astype(np.float32), X0=X0, x1l=obs[0], x1r=obs[1], xl=obs[2], xr=obs[3], rvec0=RR.so3_log(R0),
+                t0=t + off * np.array([0.0, 0.0, -1.0]), R_true=R, t_true=t, near=near, outlier=outlier)
+
+
+def unprojectable_steps(run):
+    """The twin's rejections for a point that stops being projectable: (round, step index, entry)."""
+    return [(r, k, s) for r, e in enumerate(run["log"]) for k, s in enumerate(e["steps"]) if s[0] == "unprojectable"]
+
+
+def near_ok(run, spread, tight, stride=256, wave=64):
+    """What section C asks of such a fixture: a rejection of this kind in which every bad point lies outside wave 0 of its
+    stride (wave 0's bad count is zero: a sum over wave 0 alone would accept), the trial cost over the other points BELOW the
+    standing cost (only the bad count decides), every bad depth 1e-6 m or more from the cut, and fixture_ok on the rest."""
+    good = [s for _, _, s in unprojectable_steps(run)
+            if len(s[2]) and (s[2] % stride >= wave).all() and s[3] < s[4] and (s[4][0] - s[3][0]) >= 1e-6 * s[4][0]]
+    return bool(good) and edge_ok(run, spread, tight)
+
+
+# ---- non-finite input: one point of a fixture_ok fixture spoiled
+NONFINITE = ("nan_X", "inf_Z", "nan_x2", "nan_x1", "inf_x2")
+NONFINITE_BASE = [("R0", 65, "outliers"), ("R3", 65, "outliers")]
+# the spoiled point: the k-th of the fixture's clean points (neither outlier nor behind); 0 unless the margins ask otherwise
+NONFINITE_PICK = {}
+
+
+def nonfinite_case(rig, d, variant, pick=None):
+    c, _ = ref_run(rig, 65, "outliers", d)
+    c = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    k = NONFINITE_PICK.get((rig, d, variant), 0) if pick is None else pick
+    i = int(np.flatnonzero(~c["outlier"] & ~c["behind"])[k])
+    if variant == "nan_X":
+        c["X0"][i, 1] = np.nan
+    elif variant == "inf_Z":
+        c["X0"][i, 2] = np.inf
+    elif variant == "nan_x2":
+        c["xl"][i, 0] = np.nan
+    elif variant == "nan_x1":
+        c["x1r"][i, 1] = np.nan
+    elif variant == "inf_x2":
+        c["xl"][i, 1] = np.inf
+    else:
+        raise KeyError(variant)
+    c["spoiled"] = i
+    return c
+
+
+def nonfinite_run(rig, d, variant, pick=None):
+    key = ("nonfinite", rig, d, variant, pick)
+    if key not in _CACHE:
+        import warnings
+        c = nonfinite_case(rig, d, variant, pick)
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            run = run_twin(c, d)
+            _CACHE[key] = (c, run, edge_spread(c, d, run))
+    return _CACHE[key]

@@ -178,6 +178,12 @@ def refine_ba(X0, t1l, t1r, t2l, t2r, P1, P2, R0, t0, rounds=4, iters=10, sigma=
                         rel = abs((cost[0] - costn[0]) + (cost[1] - costn[1])) / cost[0]
                         acc_margin = min(acc_margin, rel)
                         steps.append(("accepted" if accepted else "rejected", rel))
+                else:
+                    # rejected whatever the cost says: an active point is not projectable at the trial estimate.  The entry
+                    # names those points, the trial cost over the others and how far any active point's depth is from the cut
+                    rest = active & evn[2]
+                    steps.append(("unprojectable", RR.depth_margin(Xn, views[:len(obs) - 2], Rn, tn, active, t1_views=views),
+                                  np.flatnonzero(active & ~evn[2]), _cost(_weights(evn[1], rest, tau, robust)[1], rest), cost))
             if accepted:
                 R, t, X, ev, cost = Rn, tn, Xn, evn, costn
                 lam = max(lam / 10.0, 1e-12)
@@ -192,7 +198,8 @@ def refine_ba(X0, t1l, t1r, t2l, t2r, P1, P2, R0, t0, rounds=4, iters=10, sigma=
                     break
         _, c, proj, _, _ = ev
         active = proj & (c <= tau)
-        near = float(np.min(np.abs(c[proj] - tau))) / tau if proj.any() else np.inf
+        cp = c[proj][~np.isnan(c[proj])]          # (a NaN c_i is cut by the comparison itself, not by its distance from tau)
+        near = float(np.min(np.abs(cp - tau))) / tau if len(cp) else np.inf
         if not active.all():
             # a rejected point's position means nothing (under Huber a gross outlier wanders to 1e11 m): it returns to its
             # triangulation, which is also what a later re-admission is judged on

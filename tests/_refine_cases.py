@@ -195,3 +195,230 @@ def default_run(rig, n, kind, d, seed=None):
 
 def stage_cases():
     return [(rig, n, kind, d) for rig in ("R0", "R3") for d in (2, 4) for kind in KINDS for n in STAGE_N]
+
+
+# ==== the fixtures of tests/test_gpu_refine_edges.py (tests/test_refine_ref.py proves on the CPU that each reaches its path) ===
+EDGE_N = (65, 257)                               # one point past a wave, one past the workgroup stride
+EDGE_KINDS = ("outliers", "some_behind")
+SIGMAS = (0.5, 0.75, 2.0)
+# The pixel noise of the sigma fixtures.  This mode holds the points at their true places, so at the 0.3 px of the other
+# fixtures c_i = |noise|^2 / sigma^2 stays far below tau for every clean point even at sigma = 0.5 (mean 1.4 against 9.488) and
+# the flags would not know what sigma is; at 0.6 px the cut at sigma = 0.5 takes a share of them (mean 5.8).
+SIGMA_NOISE = 0.6
+
+
+def absdiff(a, b):
+    """max |a - b|; an entry that is the same non-finite number on both sides counts as equal, any other non-finite difference
+    as inf."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if a.size == 0:
+        return 0.0
+    with np.errstate(invalid="ignore"):
+        d = np.abs(a - b)
+    d = np.where(~np.isfinite(a) & ((a == b) | (np.isnan(a) & np.isnan(b))), 0.0, d)
+    return float(np.where(np.isnan(d), np.inf, d).max())
+
+
+def run_ref(c, d, t0=None, **kw):
+    kw = dict(dict(rounds=ROUNDS, iters=ITERS), **kw)
+    return RR.refine(c["X"], c["xl"], c["xr"] if d == 4 else None, c["P1"], c["P2"], RR.rodrigues(c["rvec0"]),
+                     c["t0"] if t0 is None else t0, **kw)
+
+
+def edge_spread(c, d, run, starts=(1e-15, 1e-13, 1e-11, 1e-9), per=2, seed=1, **kw):
+    """self_spread on the refinement's own estimate (t_ref, rvec_ref): where the PnP pose is kept, what stands is the start
+    itself, which says nothing.  The fixtures whose single round is cut off by the iteration cap are not converged (a start
+    1e-9 away ends further away than that): they are started 1e-15 and 1e-14 apart, as _ba_cases.far_case is."""
+    kw = dict(dict(rounds=ROUNDS, iters=ITERS), **kw)
+    rng, spread = np.random.default_rng(seed), 0.0
+    for eps in starts:
+        for _ in range(per):
+            r = run_ref(c, d, t0=c["t0"] + eps * rng.standard_normal(3), **kw)
+            if not (np.array_equal(r["active"], run["active"]) and r["status"] == run["status"]):
+                return np.inf
+            spread = max(spread, absdiff(r["t_ref"], run["t_ref"]), absdiff(r["rvec_ref"], run["rvec_ref"]))
+    return spread
+
+
+def edge_ok(run, spread, tight=1e-9, exits=("xi",), accept=False):
+    """What a GPU test may compare on: the reference reproduces itself to a tenth of the bar from eight starts 1e-15 .. 1e-9
+    apart; no c_i within 1e-6 tau of the cut at a re-classification; every round ended through one of `exits` ("xi": the
+    mode's fixture_ok -- a round that ends that way has converged, its last accepted step is a tie by construction and the
+    spread is what vouches for it); where a trial was rejected for a point that stopped being projectable, that point's depth
+    1e-6 m or more from the cut; with `accept` (the fixtures whose rounds are cut off by the iteration cap), no accept
+    decision within 1e-6 of a tie."""
+    return (spread <= 0.1 * tight and all(e["exit"] in exits and e["margin"] >= 1e-6 for e in run["log"])
+            and all(s[1] >= 1e-6 for e in run["log"] for s in e["steps"] if s[0] == "unprojectable")
+            and (not accept or all(e["accept_margin"] >= 1e-6 for e in run["log"])))
+
+
+def rig_cases():
+    """Section A: the rigs with fy != fx (R1) and K2 != K1 (R2)."""
+    return [(rig, n, kind, d) for rig in ("R1", "R2") for d in (2, 4) for kind in EDGE_KINDS for n in EDGE_N]
+
+
+def sigma_cases():
+    """Section B: sigma as data, one two-view and one one-view fixture per value."""
+    return [(rig, n, kind, d, s) for s in SIGMAS for rig, n, kind, d in (("R0", 65, "some_behind", 4), ("R3", 257, "some_behind", 2))]
+
+
+# per edge case, the first offset from SEED0 for which edge_ok holds (and, for sigma = 0.5, the final flags differ from the
+# sigma = 1 run of the same data); find_edge_offsets() below
+EDGE_SEED_OFFSET = {
+    ('R1', 65, 'outliers', 2): 7,
+    ('R1', 65, 'outliers', 4): 6,
+    ('R1', 65, 'some_behind', 2): 19,
+    ('R1', 65, 'some_behind', 4): 8,
+    ('R1', 257, 'outliers', 2): 11,
+    ('R1', 257, 'outliers', 4): 1,
+    ('R1', 257, 'some_behind', 2): 3,
+    ('R2', 65, 'outliers', 2): 9,
+    ('R2', 65, 'some_behind', 4): 3,
+    ('R2', 257, 'some_behind', 2): 7,
+    ('R2', 257, 'some_behind', 4): 3,
+    ('R0', 65, 'some_behind', 4, 0.5): 2,
+    ('R0', 65, 'some_behind', 4, 0.75): 2,
+    ('R0', 65, 'some_behind', 4, 2.0): 5,
+    ('R3', 257, 'some_behind', 2, 0.5): 3,
+    ('R3', 257, 'some_behind', 2, 0.75): 10,
+    ('R3', 257, 'some_behind', 2, 2.0): 9,
+}
+
+
+def edge_run(rig, n, kind, d, sigma=1.0, seed=None):
+    """(case, reference run, the reference's own spread) of a rig or sigma case, computed once per session and shared."""
+    key = ("edge", rig, n, kind, d, sigma, seed)
+    if key not in _CACHE:
+        off = EDGE_SEED_OFFSET.get((rig, n, kind, d) if sigma == 1.0 else (rig, n, kind, d, sigma), 0)
+        c = make_case(rig, n, kind, SEED0 + off if seed is None else seed, noise=0.3 if sigma == 1.0 else SIGMA_NOISE)
+        run = run_ref(c, d, sigma=sigma)
+        ok = all(e["exit"] == "xi" and e["margin"] >= 1e-6 for e in run["log"])          # (the spread costs eight more runs)
+        _CACHE[key] = (c, run, edge_spread(c, d, run, sigma=sigma) if ok or seed is None else np.inf)
+    return _CACHE[key]
+
+
+def wrong_intrinsics(c):
+    """The case with the mistake its rig exists to catch: R1 -- fy read where fx stands; R2 -- the left camera's intrinsics
+    used for the right one (the left 3 x 3 of P2 becomes K1 R_rl; the fourth column stands)."""
+    w = dict(c)
+    P1, P2 = c["P1"].copy(), c["P2"].copy()
+    if c["rig"] == "R1":
+        P1[1, 1] = P1[0, 0]
+    else:
+        P2[:, :3] = P1[:, :3] @ np.asarray(_rigs.RIGS[c["rig"]].get("R_rl", np.eye(3)), np.float64)
+    w.update(P1=P1, P2=P2)
+    return w
+
+
+def find_edge_offsets(limit=120):
+    """Maintenance helper: the EDGE_SEED_OFFSET table."""
+    table = {}
+    for case in rig_cases() + sigma_cases():
+        sigma = case[4] if len(case) == 5 else 1.0
+        for off in range(limit):
+            c, run, spread = edge_run(*case[:4], sigma=sigma, seed=SEED0 + off)
+            ok = edge_ok(run, spread)
+            if ok and sigma == 0.5:
+                ok = not np.array_equal(run["active"], run_ref(c, case[3])["active"])
+            if ok:
+                if off:
+                    table[case] = off
+                break
+        else:
+            raise RuntimeError(f"no seed for {case}")
+    return table
+
+
+# ---- the lambda exit: the scene with exact pixels (_ba_cases.exact_case) started AT the true pose.  Every residual is exactly
+# 0, g = 0, the trial cost 0 is not below the cost 0: fifteen steps are rejected (lambda 1e-4 -> 1e11), the round leaves through
+# lam > 1e10.
+def lambda_case():
+    import _ba_cases
+    c = _ba_cases.lambda_case()
+    c["X"] = c["X0"]
+    return c
+
+
+LAMBDA_KW = (dict(rounds=1, iters=20), dict(rounds=2, iters=16))          # 15 and 30 iterations
+
+# ---- a trial rejected because an active point stops being projectable.  Here only the pose moves, and a pose step that
+# sends a point of a consistent scene behind the camera raises the cost over the others (40 seeds of _ba_cases.near_case at
+# seven starts: never otherwise), so the cost would reject it anyway.  The fixture therefore holds points the TRUE pose has
+# behind the camera.
+NEAR_KW = dict(rounds=1, iters=6)
+NEAR_SEED = {2: 0, 4: 3}
+NEAR_STARTS = dict(starts=(1e-15, 1e-14), per=2)
+
+
+def near_case(d, seed=None, n=300, k=3, off=0.5, noise=0.3):
+    """make_case("R0", n, "outliers") with k clean points, none in wave 0 of its stride, moved to 0.1 .. 0.3 m BEHIND the t2
+    camera at the true pose (their pixels: any finite ones, as for the points of `some_behind`), and the start `off` m off along
+    +z, where they lie 0.2 .. 0.4 m in front of it: projectable, so active.  A step towards the true pose lowers the cost
+    over the other points and carries these through the camera plane."""
+    seed = NEAR_SEED[d] if seed is None else seed
+    c = make_case("R0", n, "outliers", SEED0 + 3000 + seed, noise=noise)
+    rng = np.random.default_rng([SEED0, seed, 78])
+    R, t = c["R_true"], c["t_true"]
+    cand = np.flatnonzero(~c["outlier"] & (np.arange(n) % 256 >= 64))
+    idx = rng.permutation(cand)[:k]
+    Y = c["X"][idx].astype(np.float64) @ R.T + t
+    z = -rng.uniform(0.1, 0.3, k)
+    Y = np.stack([Y[:, 0] / Y[:, 2] * 0.2, Y[:, 1] / Y[:, 2] * 0.2, z], 1)
+    c["X"][idx] = ((Y - t) @ R).astype(np.float32)
+    Y = c["X"][idx].astype(np.float64) @ R.T + t
+    K1 = np.zeros((3, 4))
+    K1[:, :3] = c["P1"][:, :3]
+    c["xl"][idx] = (project(K1, Y * [1, 1, -1]) + noise * rng.standard_normal((k, 2))).astype(np.float32)
+    c["xr"][idx] = (project(c["P2"], Y * [1, 1, -1]) + noise * rng.standard_normal((k, 2))).astype(np.float32)
+    c.update(t0=t + off * np.array([0.0, 0.0, 1.0]), through=idx)
+    return c
+
+
+def unprojectable_steps(run):
+    return [(r, k, s) for r, e in enumerate(run["log"]) for k, s in enumerate(e["steps"]) if s[0] == "unprojectable"]
+
+
+def near_ok(run, spread, stride=256, wave=64):
+    """A rejection of this kind in which every bad point lies outside wave 0 of its stride, the trial cost over the other points
+    below the standing cost by 1e-6 of it or more (only the bad count decides), and edge_ok with the accept margins on the rest."""
+    good = [s for _, _, s in unprojectable_steps(run)
+            if len(s[2]) and (s[2] % stride >= wave).all() and s[3] < s[4] and (s[4][0] - s[3][0]) >= 1e-6 * s[4][0]]
+    return bool(good) and edge_ok(run, spread, exits=("iters", "xi"), accept=True)
+
+
+# ---- non-finite input: one point of a fixture_ok fixture spoiled
+NONFINITE = ("nan_X", "inf_Z", "nan_x2", "inf_x2")
+# the spoiled point: the k-th of the fixture's clean points; 0 unless edge_ok asks otherwise
+NONFINITE_PICK = {("R0", 2, "nan_X"): 3, ("R0", 2, "inf_Z"): 3, ("R0", 2, "nan_x2"): 3, ("R0", 2, "inf_x2"): 3,
+                  ("R3", 4, "nan_X"): 3, ("R3", 4, "inf_Z"): 3}
+
+
+def nonfinite_case(rig, d, variant, pick=None):
+    c, _ = ref_run(rig, 65, "outliers", d)
+    c = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    k = NONFINITE_PICK.get((rig, d, variant), 0) if pick is None else pick
+    i = int(np.flatnonzero(~c["outlier"] & ~c["behind"])[k])
+    if variant == "nan_X":
+        c["X"][i, 1] = np.nan
+    elif variant == "inf_Z":
+        c["X"][i, 2] = np.inf
+    elif variant == "nan_x2":
+        c["xl"][i, 0] = np.nan
+    elif variant == "inf_x2":
+        c["xl"][i, 1] = np.inf
+    else:
+        raise KeyError(variant)
+    c["spoiled"] = i
+    return c
+
+
+def nonfinite_run(rig, d, variant, pick=None):
+    key = ("nonfinite", rig, d, variant, pick)
+    if key not in _CACHE:
+        import warnings
+        c = nonfinite_case(rig, d, variant, pick)
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            run = run_ref(c, d)
+            _CACHE[key] = (c, run, edge_spread(c, d, run))
+    return _CACHE[key]

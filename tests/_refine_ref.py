@@ -121,6 +121,16 @@ def evaluate(X, obs, views, R, t, sigma=1.0, jac=True):
     return r, c, proj, J
 
 
+def depth_margin(X, views, R, t, active, t1_views=()):
+    """The smallest distance of an active point's depth h_3 from the projectability cut, over `views` of Y = R X + t and
+    `t1_views` of X itself: how far "not projectable" is from hanging on a last bit."""
+    Y = rows_times(X, R) + t
+    hs = [rows_times(Z, M)[:, 2] + p4[2] for Z, vs in ((Y, views), (X, t1_views)) for M, p4 in vs]
+    # (a NaN depth fails the comparison whatever its bits: it is not near the cut)
+    far = [np.abs(h[active] - MIN_DEPTH) for h in hs]
+    return min([float(np.min(f[~np.isnan(f)])) for f in far if not np.isnan(f).all()], default=np.inf)
+
+
 def chol_solve6(A, b):
     """6x6 Cholesky solve, row by row; fails unless every pivot is > 0."""
     L = np.zeros((6, 6))
@@ -167,13 +177,16 @@ def _sums(r, c, J, active, tau, robust, sigma):
     hi = math.fsum(terms)
     cost = (hi, math.fsum(terms + [-hi]) if math.isfinite(hi) else 0.0)
     is2 = 1.0 / (sigma * sigma)
-    H = (w[:, None, None] * (J[:, :, :, None] * J[:, :, None, :]).sum(1)).sum(0) * is2
-    g = (w[:, None] * (J * r[:, :, None]).sum(1)).sum(0) * is2
+    # over the ACTIVE set (R5): an inactive point adds an exact zero, also where its residual is not finite (0 * NaN is not 0)
+    H = np.where(active[:, None, None], w[:, None, None] * (J[:, :, :, None] * J[:, :, None, :]).sum(1), 0.0).sum(0) * is2
+    g = np.where(active[:, None], w[:, None] * (J * r[:, :, None]).sum(1), 0.0).sum(0) * is2
     return cost, H, g
 
 
 def refine(X, xl, xr, P1, P2, R0, t0, rounds=4, iters=10, sigma=1.0, min_inliers=6, perm=None):
-    """R1-R7.  xr None: one view (d = 2).  Returns a dict; 'log' has one entry per round for fixture_ok."""
+    """R1-R7.  xr None: one view (d = 2).  Returns a dict; 'log' has one entry per round for fixture_ok: its exit, the smallest
+    relative distance of a c_i from tau at its re-classification, the smallest relative cost difference over its accept
+    decisions and 'steps', those decisions one by one (tests/_ba_ref.py keeps the same log)."""
     X = np.asarray(X, np.float64).reshape(-1, 3)
     n = X.shape[0]
     d = 2 if xr is None else 4
@@ -198,7 +211,7 @@ def refine(X, xl, xr, P1, P2, R0, t0, rounds=4, iters=10, sigma=1.0, min_inliers
         cost, H, g = _sums(r, c, J, active, tau, robust, sigma)
         if rd == 0:
             cost_first = cost
-        how = "iters"
+        how, acc_margin, steps = "iters", np.inf, []
         for _ in range(iters):
             total += 1
             A = H + lam * np.diag(np.diag(H))
@@ -211,6 +224,16 @@ def refine(X, xl, xr, P1, P2, R0, t0, rounds=4, iters=10, sigma=1.0, min_inliers
                 if np.all(pn[active]):
                     costn, Hn, gn = _sums(rn, cn, Jn, active, tau, robust, sigma)
                     accepted = costn < cost
+                    if cost[0] > 0.0:                  # how far the decision is from a tie, relative to the cost itself
+                        rel = abs((cost[0] - costn[0]) + (cost[1] - costn[1])) / cost[0]
+                        acc_margin = min(acc_margin, rel)
+                        steps.append(("accepted" if accepted else "rejected", rel))
+                else:
+                    # rejected whatever the cost says: an active point is not projectable at the trial pose.  The entry names
+                    # those points, the trial cost over the others and how far any active point's depth is from the cut
+                    rest = active & pn
+                    steps.append(("unprojectable", depth_margin(X, views, Rn, tn, active), np.flatnonzero(active & ~pn),
+                                  _sums(rn, cn, Jn, rest, tau, robust, sigma)[0], cost))
             if accepted:
                 R, t, r, c, proj, J, cost, H, g = Rn, tn, rn, cn, pn, Jn, costn, Hn, gn
                 lam = max(lam / 10.0, 1e-12)
@@ -223,8 +246,9 @@ def refine(X, xl, xr, P1, P2, R0, t0, rounds=4, iters=10, sigma=1.0, min_inliers
                     how = "lambda"
                     break
         active = proj & (c <= tau)
-        near = float(np.min(np.abs(c[proj] - tau))) / tau if proj.any() else np.inf
-        log.append({"exit": how, "margin": near})
+        cp = c[proj][~np.isnan(c[proj])]          # (a NaN c_i is cut by the comparison itself, not by its distance from tau)
+        near = float(np.min(np.abs(cp - tau))) / tau if len(cp) else np.inf
+        log.append({"exit": how, "margin": near, "accept_margin": acc_margin, "steps": steps})
     info = (active.astype(np.float64)[:, None, None] * (J[:, :, :, None] * J[:, :, None, :]).sum(1)).sum(0) / (sigma * sigma)
     n_active = int(active.sum())
     pd, _ = chol_solve6(info, np.zeros(6))

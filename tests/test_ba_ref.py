@@ -202,7 +202,10 @@ def test_far_start_fixture_rejects_a_step_decisively(d):
     apart the twin reproduces itself to a tenth of the bar (the run is not converged: a start 1e-9 away ends 3e-9 away)."""
     c = BC.far_case(d)
     run = BC.run_twin(c, d, **BC.FAR_KW)
-    steps = run["log"][0]["steps"]
+    # (the decisions the cost takes: the log also names the trial -- the third of d = 6, the second of d = 8 -- that is rejected
+    # before the cost is asked, because a point is not projectable at it)
+    steps = [s for s in run["log"][0]["steps"] if s[0] != "unprojectable"]
+    assert len(steps) == 3 and len(run["log"][0]["steps"]) == 4
     k = [s[0] for s in steps].index("rejected")
     assert k == (0 if d == 6 else 1) and steps[k + 1][0] == "accepted"
     assert all(m >= 0.1 for _, m in steps) and run["log"][0]["margin"] >= 1e-6
@@ -242,3 +245,112 @@ def test_default_setting_fixtures_spread_is_what_the_bars_assume(rig, n, kind, d
             assert max(np.abs(r["t"] - run["t"]).max(), np.abs(r["rvec"] - run["rvec"]).max()) <= 0.1 * BC.DEFAULT_POSE_BAR
             assert np.abs(r["X"] - run["X"]).max() <= 0.1 * BC.DEFAULT_POINT_BAR
             assert np.abs(r["info"] - run["info"]).max() <= 0.1 * BC.DEFAULT_INFO_BAR * np.abs(run["info"]).max()
+
+
+# ---- the fixtures of tests/test_gpu_refine_edges.py: each meets the precondition and reaches the path it is named after ------
+def _report(what, key, run, spread):
+    print(f"{what}: seed offset {BC.EDGE_SEED_OFFSET.get(key, 0)}, classification margin {min(e['margin'] for e in run['log']):.1e}, "
+          f"accept margin {min(e['accept_margin'] for e in run['log']):.1e}, self-spread {spread:.1e}, "
+          f"exits {[e['exit'] for e in run['log']]}, active {run['n_active']}")
+
+
+@pytest.mark.parametrize("rig,n,kind,d", BC.rig_cases())
+def test_rig_fixtures_meet_the_precondition_and_catch_the_mistake_they_exist_for(rig, n, kind, d):
+    """R1 (fy = 0.85 fx) and R2 (K2 != K1) at 4 x 2.  The twin with P1[1, 1] := P1[0, 0] (R1) or with the left 3 x 3 of P2
+    replaced by K1 R_rl (R2) must end more than 1e3 x the bar away in pose, or with another flag: otherwise the fixture could
+    not catch the kernel or the argument fill that makes that mistake."""
+    c, run, spread = BC.edge_run(rig, n, kind, d)
+    _report(f"{rig} n={n} {kind} d={d}", (rig, n, kind, d), run, spread)
+    assert BC.edge_ok(run, spread, TIGHT), (spread, run["log"])
+    clean = ~c["outlier"] & ~c["behind"]
+    # (tau is the 95 % point: a clean point in twenty is cut by design; no outlier and no point behind the camera survives)
+    assert run["status"] == BA.APPLIED and run["active"][clean].mean() >= 0.9 and not run["active"][~clean].any()
+    assert c["P1"][1, 1] != c["P1"][0, 0] or not np.array_equal(c["P2"][:, :3], c["P1"][:, :3])
+    wrong = BC.run_twin(BC.wrong_intrinsics(c), d)
+    dpose = max(np.abs(wrong["t_ref"] - run["t_ref"]).max(), np.abs(wrong["rvec_ref"] - run["rvec_ref"]).max())
+    flips = int((wrong["active"] != run["active"]).sum())
+    print(f"    with the mistake: pose {dpose:.1e} away, {flips} of {n} flags differ")
+    assert dpose > 1e3 * TIGHT or flips > 0
+
+
+@pytest.mark.parametrize("rig,n,kind,d,sigma", BC.sigma_cases())
+def test_sigma_fixtures_meet_the_precondition_and_depend_on_sigma(rig, n, kind, d, sigma):
+    """sigma 0.5 / 0.75 / 2: the twin's info differs from its sigma = 1 run of the same data by more than the info bar (the
+    1 / sigma^2 scale is a tested quantity), the costs likewise, and at sigma = 0.5 the final flags differ too."""
+    c, run, spread = BC.edge_run(rig, n, kind, d, sigma=sigma)
+    _report(f"sigma={sigma} {rig} n={n} {kind} d={d}", (rig, n, kind, d, sigma), run, spread)
+    assert BC.edge_ok(run, spread, TIGHT), (spread, run["log"])
+    assert run["status"] == BA.APPLIED
+    one = BC.run_twin(c, d)
+    top = np.abs(run["info"]).max()
+    dinfo, flips = np.abs(run["info"] - one["info"]).max() / top, int((run["active"] != one["active"]).sum())
+    print(f"    against sigma = 1: info {dinfo:.1e} of its largest entry away, {flips} flags differ, "
+          f"cost_first {run['cost_first']:.6g} vs {one['cost_first']:.6g}")
+    assert dinfo > 1e3 * TIGHT
+    assert abs(run["cost_first"] - one["cost_first"]) > 1e3 * TIGHT * one["cost_first"]
+    if sigma == 0.5:
+        assert flips > 0
+
+
+@pytest.mark.parametrize("kw", BC.LAMBDA_KW, ids=lambda k: f"{k['rounds']}x{k['iters']}")
+@pytest.mark.parametrize("d", [6, 8])
+def test_lambda_fixture_leaves_through_the_lambda_exit_at_an_exact_tie(d, kw):
+    """The exact scene started at the true pose: every residual and the cost are exactly 0, fifteen trials per round are not
+    BELOW it, the rounds leave through lambda > 1e10 before their cap, and the start comes back bit for bit -- which is what
+    entitles the GPU test to ask the kernel for the same."""
+    c = BC.lambda_case()
+    run = BC.run_twin(c, d, **kw)
+    assert run["iters"] == 15 * kw["rounds"] < kw["rounds"] * kw["iters"]
+    assert all(e["exit"] == "lambda" and e["steps"] == [] for e in run["log"])           # (cost 0: no relative margin to log)
+    assert run["status"] == BA.APPLIED and run["n_active"] == 70 and run["cost_first"] == 0.0 and run["cost_last"] == 0.0
+    assert np.array_equal(run["t"], c["t0"]) and np.array_equal(run["rvec"], np.zeros(3)) and np.array_equal(run["R"], np.eye(3))
+    assert np.array_equal(run["X"], c["X0"].astype(np.float64))
+    r, cc, proj, _, _ = BA.evaluate(c["X0"].astype(np.float64), [np.asarray(c[k], np.float64) for k in ("x1l", "x1r", "xl", "xr")][:d // 2],
+                                    BA.views_of(c["P1"], c["P2"]), np.eye(3), c["t0"])
+    assert proj.all() and not r.any()
+
+
+@pytest.mark.parametrize("d", [6, 8])
+def test_near_fixture_rejects_a_trial_for_an_unprojectable_point_alone(d):
+    """_ba_cases.near_case: at least one trial is rejected because an active point is not projectable at it; in one such
+    rejection every bad point lies outside wave 0 of its stride ((i mod 256) >= 64) and the trial cost over the other points is
+    BELOW the standing cost -- the bad count alone decides, and a count summed over wave 0 alone would accept; every depth is
+    1e-6 m or more from the cut; all other decisions meet fixture_ok."""
+    c = BC.near_case(d)
+    run = BC.run_twin(c, d, **BC.NEAR_KW)
+    spread = BC.self_spread(c, d, run, **BC.NEAR_KW)
+    un = BC.unprojectable_steps(run)
+    for rd, k, s in un:
+        print(f"d={d} round {rd} step {k}: bad {s[2].tolist()}, cost over the rest {s[3][0]:.6g} against {s[4][0]:.6g} standing, "
+              f"nearest depth {s[1]:.1e} m from the cut")
+    _report(f"near d={d} seed {BC.NEAR_SEED[d]}", None, run, spread)
+    print(f"    steps {[(s[0], float(s[1])) for s in run['log'][0]['steps']]}")
+    assert un and BC.near_ok(run, spread, TIGHT)
+    assert any((s[2] % 256 >= 64).all() and s[3] < s[4] for _, _, s in un)
+    assert run["status"] == BA.APPLIED and run["iters"] == 6 and [s[0] for s in run["log"][0]["steps"]].count("accepted") >= 2
+    # the bad points are active, projectable at the accepted estimate, and among the near ones or the outliers' victims
+    assert all(len(s[2]) > 0 for _, _, s in un)
+
+
+@pytest.mark.parametrize("variant", BC.NONFINITE)
+@pytest.mark.parametrize("rig,d", [("R0", 6), ("R0", 8), ("R3", 6), ("R3", 8)])
+def test_nonfinite_fixtures_take_the_paths_the_twin_defines(rig, d, variant):
+    c, run, spread = BC.nonfinite_run(rig, d, variant)
+    i = c["spoiled"]
+    _report(f"{variant} {rig} d={d} point {i}", None, run, spread)
+    assert BC.edge_ok(run, spread, TIGHT), (spread, run["log"])
+    assert run["n_active"] == 45 and run["active"][i] == 0 and run["iters"] == 8
+    assert np.isfinite(run["info"]).all() and np.isfinite(run["t_ref"]).all() and np.isfinite(run["rvec_ref"]).all()
+    if variant in ("nan_X", "inf_Z"):
+        # never projectable, never active: the run is that of the other 64 points
+        assert run["status"] == BA.APPLIED and np.isfinite(run["cost_first"])
+        assert run["X"][i].tobytes() == c["X0"][i].astype(np.float64).tobytes()
+    else:
+        # active in round 0, whose cost is not finite and whose trials all fail; dropped at the first re-classification; the
+        # later rounds run clean on 45 points -- and cost_first keeps the PnP pose
+        assert run["status"] == BA.KEPT_PNP and not np.isfinite(run["cost_first"]) and np.isfinite(run["cost_last"])
+        assert (np.isnan(run["cost_first"])) == variant.startswith("nan")
+        assert not any(s[0] == "accepted" for s in run["log"][0]["steps"])
+        assert all(any(s[0] == "accepted" for s in e["steps"]) for e in run["log"][1:])
+        assert np.array_equal(run["t"], c["t0"]) and run["X"].tobytes() == c["X0"].astype(np.float64).tobytes()
+        assert np.abs(run["t_ref"] - c["t_true"]).max() < 0.03

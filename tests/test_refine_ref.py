@@ -170,3 +170,94 @@ def test_default_setting_fixtures_reproduce_themselves(rig, n, kind, d):
     assert all(e["margin"] >= 1e-6 for e in run["log"]), run["log"]
     assert spread <= 1e-10, spread
     assert (run["active"][~c["outlier"]] == 1).all() and not run["active"][c["outlier"]].any()
+
+
+# ---- the fixtures of tests/test_gpu_refine_edges.py: each meets the precondition and reaches the path it is named after ------
+TIGHT = 1e-9                                     # the bar of the GPU comparison (tests/test_gpu_parity_pose.py)
+
+
+def _report(what, key, run, spread):
+    print(f"{what}: seed offset {RC.EDGE_SEED_OFFSET.get(key, 0)}, classification margin {min(e['margin'] for e in run['log']):.1e}, "
+          f"self-spread {spread:.1e}, exits {[e['exit'] for e in run['log']]}, active {run['n_active']}")
+
+
+@pytest.mark.parametrize("rig,n,kind,d", RC.rig_cases())
+def test_rig_fixtures_meet_the_precondition_and_catch_the_mistake_they_exist_for(rig, n, kind, d):
+    """R1 (fy = 0.85 fx) and R2 (K2 != K1).  The reference with P1[1, 1] := P1[0, 0] (R1) or with the left 3 x 3 of P2 replaced
+    by K1 R_rl (R2; the one-view cases never read P2 and are held to R1's mistake only where it applies) must end more than
+    1e3 x the bar away in pose, or with another flag."""
+    c, run, spread = RC.edge_run(rig, n, kind, d)
+    _report(f"{rig} n={n} {kind} d={d}", (rig, n, kind, d), run, spread)
+    assert fixture_ok(run) and RC.edge_ok(run, spread), (spread, run["log"])
+    clean = ~c["outlier"] & ~c["behind"]
+    assert run["status"] == RR.APPLIED and (run["active"][clean] == 1).all() and not run["active"][~clean].any()
+    if rig == "R2" and d == 2:
+        return                                   # view L alone: K2 is not an input
+    wrong = RC.run_ref(RC.wrong_intrinsics(c), d)
+    dpose = max(np.abs(wrong["t_ref"] - run["t_ref"]).max(), np.abs(wrong["rvec_ref"] - run["rvec_ref"]).max())
+    flips = int((wrong["active"] != run["active"]).sum())
+    print(f"    with the mistake: pose {dpose:.1e} away, {flips} of {n} flags differ")
+    assert dpose > 1e3 * TIGHT or flips > 0
+
+
+@pytest.mark.parametrize("rig,n,kind,d,sigma", RC.sigma_cases())
+def test_sigma_fixtures_meet_the_precondition_and_depend_on_sigma(rig, n, kind, d, sigma):
+    c, run, spread = RC.edge_run(rig, n, kind, d, sigma=sigma)
+    _report(f"sigma={sigma} {rig} n={n} {kind} d={d}", (rig, n, kind, d, sigma), run, spread)
+    assert fixture_ok(run) and RC.edge_ok(run, spread), (spread, run["log"])
+    assert run["status"] == RR.APPLIED
+    one = RC.run_ref(c, d)
+    top = np.abs(run["info"]).max()
+    dinfo, flips = np.abs(run["info"] - one["info"]).max() / top, int((run["active"] != one["active"]).sum())
+    print(f"    against sigma = 1: info {dinfo:.1e} of its largest entry away, {flips} flags differ")
+    assert dinfo > 1e3 * TIGHT and abs(run["cost_first"] - one["cost_first"]) > 1e3 * TIGHT * one["cost_first"]
+    if sigma == 0.5:
+        assert flips > 0
+
+
+@pytest.mark.parametrize("kw", RC.LAMBDA_KW, ids=lambda k: f"{k['rounds']}x{k['iters']}")
+@pytest.mark.parametrize("d", [2, 4])
+def test_lambda_fixture_leaves_through_the_lambda_exit_at_an_exact_tie(d, kw):
+    c = RC.lambda_case()
+    run = RC.run_ref(c, d, **kw)
+    assert run["iters"] == 15 * kw["rounds"] < kw["rounds"] * kw["iters"]
+    assert all(e["exit"] == "lambda" and e["steps"] == [] for e in run["log"])
+    assert run["status"] == RR.APPLIED and run["n_active"] == 70 and run["cost_first"] == 0.0 and run["cost_last"] == 0.0
+    assert np.array_equal(run["t"], c["t0"]) and np.array_equal(run["rvec"], np.zeros(3)) and np.array_equal(run["R"], np.eye(3))
+
+
+@pytest.mark.parametrize("d", [2, 4])
+def test_near_fixture_rejects_a_trial_for_an_unprojectable_point_alone(d):
+    """_refine_cases.near_case: a rejection in which every bad point lies outside wave 0 of its stride and the trial cost over
+    the other points is BELOW the standing cost; the bad points are the ones the true pose has behind the camera."""
+    c = RC.near_case(d)
+    run = RC.run_ref(c, d, **RC.NEAR_KW)
+    spread = RC.edge_spread(c, d, run, **RC.NEAR_STARTS, **RC.NEAR_KW)
+    un = RC.unprojectable_steps(run)
+    for rd, k, s in un:
+        print(f"d={d} round {rd} step {k}: bad {s[2].tolist()}, cost over the rest {s[3][0]:.6g} against {s[4][0]:.6g} standing, "
+              f"nearest depth {s[1]:.1e} m from the cut")
+    _report(f"near d={d} seed {RC.NEAR_SEED[d]}", None, run, spread)
+    print(f"    accept margin {run['log'][0]['accept_margin']:.1e}, steps {[(s[0], float(s[1])) for s in run['log'][0]['steps']]}")
+    assert un and RC.near_ok(run, spread)
+    assert all(set(s[2]) <= set(c["through"]) and (s[2] % 256 >= 64).all() for _, _, s in un)
+    assert run["status"] == RR.APPLIED and run["iters"] == 6 and [s[0] for s in run["log"][0]["steps"]].count("accepted") >= 2
+
+
+@pytest.mark.parametrize("variant", RC.NONFINITE)
+@pytest.mark.parametrize("rig,d", [("R0", 2), ("R0", 4), ("R3", 2), ("R3", 4)])
+def test_nonfinite_fixtures_take_the_paths_the_reference_defines(rig, d, variant):
+    c, run, spread = RC.nonfinite_run(rig, d, variant)
+    i = c["spoiled"]
+    _report(f"{variant} {rig} d={d} point {i}", None, run, spread)
+    assert RC.edge_ok(run, spread, exits=("xi", "lambda")), (spread, run["log"])
+    assert run["n_active"] == 45 and run["active"][i] == 0
+    assert np.isfinite(run["info"]).all() and np.isfinite(run["t_ref"]).all() and np.isfinite(run["rvec_ref"]).all()
+    if variant in ("nan_X", "inf_Z"):
+        assert run["status"] == RR.APPLIED and np.isfinite(run["cost_first"])
+    else:
+        # round 0: the cost is not finite, fifteen solves or trials fail, lambda exit; the point goes at the re-classification
+        assert run["status"] == RR.KEPT_PNP and not np.isfinite(run["cost_first"]) and np.isfinite(run["cost_last"])
+        assert run["log"][0]["exit"] == "lambda" and not any(s[0] == "accepted" for s in run["log"][0]["steps"])
+        assert run["log"][1]["exit"] == "xi" and np.array_equal(run["t"], c["t0"])
+        assert np.abs(run["t_ref"] - c["t_true"]).max() < 0.03
