@@ -726,6 +726,71 @@ int svo_orb_track_frames(svo_ctx *ctx, int slot_prev, int slot_cur, svo_pt2f *t1
                          int32_t *idx_prev, int32_t *idx_cur, int cap, int *n_out);
 int svo_get_frame_stereo(svo_ctx *ctx, float *uR, int32_t *sad, int cap, int *n_out);
 
+/* ---- Track carry: LK tracks kept across frames under persistent ids, on the online paths (additive; detected by symbol, the
+ * ABI version stays 9 and svo_config is unchanged) ---------------------------------------------------------------------------
+ * By default every frame's corners are detected afresh and tracked through exactly one pair (src/tracking.cpp:258-344).  With
+ * track carry on, the list a frame hands to the next pair is the points the circular LK has just tracked INTO it, each under
+ * the id it already had, followed by those of the frame's detections that do not crowd them.  A back end gets the same
+ * physical point over many frames under one id; the odometry chain tracks from sub-pixel positions.
+ *
+ * Semantics (the numpy twin is tests/_carry_ref.py; the kernel equals it bit for bit).  A frame's list is up to max_keypoints
+ * entries (xy float32 x 2, response, id int64, age int32).  Inputs of a pair: the previous frame's list Lp (n_p entries); the
+ * new frame's detections D (n_d entries, in the order the detector chain leaves them); per i < n_p the keep byte of the
+ * circular LK and q[i] = its t2_left.
+ *   C1 candidates: ascending i with keep[i] != 0, q[i] finite, 0 <= q.x <= w-1 and 0 <= q.y <= h-1 (float compares), and
+ *      max_age == 0 or age[i] + 1 <= max_age.
+ *   C2 near(a, b): dx = a.x - b.x, dy = a.y - b.y in float32 (one rounding each); d2 = (double)dx*dx + (double)dy*dy (the
+ *      products are exact, the sum is the only rounding); near iff d2 < min_distance * min_distance in double.
+ *   C3 carried: candidate i is carried iff no candidate j < i is near it -- every earlier candidate counts, carried itself or
+ *      not.  The rule depends on indices only (it evaluates in parallel) and list order is seniority order: the older track
+ *      wins.  It drops a little more than a greedy pass would.
+ *   C4 detections: detection k is kept iff no CARRIED point is near it.  Detections are not tested against each other.
+ *   C5 the new list: the carried points in ascending i as (q[i], response[i], id[i], age[i] + 1), then the kept detections in
+ *      ascending k as (xy, response, id = next_id + rank, age 0), cut at max_keypoints: only trailing detections fall off, and
+ *      they get no id.  next_id advances by the number of detections listed.  This list is what the next pair tracks from and
+ *      what svo_get_frame_keypoints returns (x, y: the tracked sub-pixel position; the other fields as the detector made them).
+ *   C6 a list without ids -- a chain's first frame, the first frame after a reset, a frame stored before the switch -- is
+ *      numbered next_id.. in list order, age 0, by the step that first sees it.  ids start at 0 per stream and per online
+ *      chain; svo_reset / svo_streams_reset restart them.
+ *   C7 an image whose detector count exceeds max_keypoints contributes no detections.  Its pair ends in SVO_FAIL_CAPACITY as
+ *      without carry; the following pair tracks the carried points and is a regular pair.
+ *   C8 the carry happens whatever the step's outcome (the reference replaces last_frame_ on every exit).  n_prev_kps = the
+ *      length of Lp; n_cur_kps and the < 30 gate stay the detector's count.
+ *   svo_set_track_carry : LK mode; svo_add_frame, svo_streams_step and their svo_ingest_* twins.  on = 0 (the default): off, the
+ *       other arguments are ignored, and every step runs exactly the launches it ran before this option existed.
+ *       Recommended when on: min_distance 3.0, max_age 0 (unlimited).  May be called at any time between calls on the
+ *       context.  While on, svo_track_batch, svo_track_uploaded(_async) and svo_ingest_track_batch return SVO_ERR_STATE: a
+ *       batch treats its pairs as independent.  SVO_ERR_ARG (nothing changes): an ORB-mode context; min_distance not finite,
+ *       < 1 or > 256; max_age < 0.  Memory: allocated by the first enabling call -- 12 bytes x max_keypoints per working frame
+ *       (max_batch + 1) and per stream of an existing stream set, 30 bytes x max_keypoints per pair of max_batch; a stream set
+ *       created afterwards includes its share.  A context that never enables it allocates and pays nothing.  The id counters
+ *       live on the device (one for the online ring, one per stream): no host synchronisation is added to a step.
+ *   svo_get_track_carry : what is set (0, 0.0, 0 while off).  Any pointer may be NULL.
+ *   svo_carry_merge (stage API): the same kernel on a caller's arrays, independent of the context's size and mode.  Tracks:
+ *       trk_xy = q, trk_resp / trk_id / trk_age / trk_keep, n_trk entries; detections det_xy / det_resp, n_det entries; next_id.
+ *       Outputs, cap >= n_trk entries each: the list (out_xy, out_resp, out_id, out_age), out_src = the track index or n_trk +
+ *       the detection index of every entry, *n_out the length, *n_carried the carried points.  `mem` says where every array AND
+ *       the two counts live; SVO_MEM_DEVICE: in stream order on the context's stream, no host synchronisation (scratch grows
+ *       on demand; a call that grows it waits for the device), inputs and outputs must not overlap; SVO_MEM_HOST: returns when
+ *       the outputs are complete.  SVO_ERR_ARG: a size < 1 or > 16384, the parameter rules above, cap < n_trk, n > 2^20.
+ *   Read-backs (HOST).  ids / ages NULL (both): *n_out only; otherwise SVO_ERR_ARG when cap is too small.  SVO_ERR_ARG when
+ *   track carry was off for the step in question.
+ *       svo_get_frame_track_ids      : ids and ages of the list svo_get_frame_keypoints returns.
+ *       svo_get_last_track_ids       : id and age at t1 of every track of svo_get_last_tracks, in its order.
+ *       svo_streams_get_track_ids    : the same for item `item` of the last svo_streams_step (svo_streams_get_tracks).
+ *       svo_streams_get_frame_tracks : a stream's stored list: records as svo_get_frame_keypoints makes them, ids, ages. */
+int svo_set_track_carry(svo_ctx *ctx, int on, double min_distance, int max_age);
+int svo_get_track_carry(const svo_ctx *ctx, int *on, double *min_distance, int *max_age);
+int svo_carry_merge(svo_ctx *ctx, int width, int height, double min_distance, int max_age,
+                    const svo_pt2f *trk_xy, const float *trk_resp, const int64_t *trk_id, const int32_t *trk_age,
+                    const uint8_t *trk_keep, int n_trk, const svo_pt2f *det_xy, const float *det_resp, int n_det, int64_t next_id,
+                    svo_pt2f *out_xy, float *out_resp, int64_t *out_id, int32_t *out_age, int32_t *out_src, int cap,
+                    int *n_out, int *n_carried, int mem);
+int svo_get_frame_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages, int cap, int *n_out);
+int svo_get_last_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages, int cap, int *n_out);
+int svo_streams_get_track_ids(svo_ctx *ctx, int item, int64_t *ids, int32_t *ages, int cap, int *n_out);
+int svo_streams_get_frame_tracks(svo_ctx *ctx, int stream_id, svo_keypoint *kps, int64_t *ids, int32_t *ages, int cap, int *n_out);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

@@ -176,6 +176,14 @@ def load_library():
     lib.svo_orb_track_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.POINTER(C.c_int)]
     lib.svo_get_frame_stereo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_set_track_carry.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int]
+    lib.svo_get_track_carry.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    lib.svo_carry_merge.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 5 + [C.c_int] +
+                                    [C.c_void_p] * 2 + [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int])
+    lib.svo_get_frame_track_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_get_last_track_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_streams_get_track_ids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_streams_get_frame_tracks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     _LIB = lib
     return lib
 
@@ -715,6 +723,88 @@ class Context:
         if ordered:
             self._order_out(out)
         return out, m
+
+    # ---- track carry (svo_set_track_carry / svo_carry_merge and the id read-backs) -------------------
+    def set_track_carry(self, on=True, min_distance=3.0, max_age=0):
+        """LK mode, add_frame / streams_step and their ingest twins: keep the points the circular LK tracked into a frame,
+        under persistent ids, as the head of the list the next pair tracks from; the frame's detections closer than
+        min_distance to one of them are dropped.  max_age = 0: unlimited.  While on, the batch entry points refuse."""
+        self._check(self.lib.svo_set_track_carry(self.h, 1 if on else 0, float(min_distance), int(max_age)))
+
+    def track_carry(self):
+        """(on, min_distance, max_age) as set; (False, 0.0, 0) while off."""
+        on, md, ma = C.c_int(0), C.c_double(0), C.c_int(0)
+        self._check(self.lib.svo_get_track_carry(self.h, C.byref(on), C.byref(md), C.byref(ma)))
+        return bool(on.value), md.value, ma.value
+
+    def carry_merge(self, width, height, min_distance, max_age, trk_xy, trk_resp, trk_id, trk_age, trk_keep, det_xy, det_resp,
+                    next_id=0, cap=None):
+        """svo_carry_merge.  numpy inputs: returns a dict of numpy arrays xy, resp, id, age, src (n_out entries) and the int
+        n_carried.  torch cuda inputs: returns the same keys as `cap`-entry tensors plus n_out / n_carried as int32 tensors,
+        all filled in stream order without a host synchronisation."""
+        host = isinstance(trk_xy, np.ndarray)
+        if host:
+            conv = lambda a, dt, shape: np.ascontiguousarray(a, dt).reshape(shape)
+            new = lambda shape, dt: np.zeros(shape, dt)
+            f32, i64, i32, u8 = np.float32, np.int64, np.int32, np.uint8
+            ptr = lambda a: C.c_void_p(a.ctypes.data)
+        else:
+            import torch
+            dev = trk_xy.device
+            conv = lambda a, dt, shape: a.to(dt).contiguous().reshape(shape)
+            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            f32, i64, i32, u8 = torch.float32, torch.int64, torch.int32, torch.uint8
+            ptr = lambda a: C.c_void_p(a.data_ptr())
+        txy, tr, ti, ta, tk = (conv(trk_xy, f32, (-1, 2)), conv(trk_resp, f32, (-1,)), conv(trk_id, i64, (-1,)),
+                               conv(trk_age, i32, (-1,)), conv(trk_keep, u8, (-1,)))
+        dxy, dr = conv(det_xy, f32, (-1, 2)), conv(det_resp, f32, (-1,))
+        n_trk, n_det = int(txy.shape[0]), int(dxy.shape[0])
+        assert tr.shape[0] == ti.shape[0] == ta.shape[0] == tk.shape[0] == n_trk and dr.shape[0] == n_det
+        cap = n_trk + n_det if cap is None else int(cap)
+        m = max(cap, 1)
+        out = {"xy": new((m, 2), f32), "resp": new((m,), f32), "id": new((m,), i64), "age": new((m,), i32), "src": new((m,), i32)}
+        if host:
+            n_out, n_car = C.c_int(0), C.c_int(0)
+            pn, pc = C.cast(C.byref(n_out), C.c_void_p), C.cast(C.byref(n_car), C.c_void_p)
+        else:
+            n_out, n_car = new((1,), i32), new((1,), i32)
+            pn, pc = ptr(n_out), ptr(n_car)
+            ordered = self._order_in(n_car)
+        self._check(self.lib.svo_carry_merge(self.h, int(width), int(height), float(min_distance), int(max_age), ptr(txy), ptr(tr),
+                                             ptr(ti), ptr(ta), ptr(tk), n_trk, ptr(dxy), ptr(dr), n_det, int(next_id),
+                                             ptr(out["xy"]), ptr(out["resp"]), ptr(out["id"]), ptr(out["age"]), ptr(out["src"]), cap,
+                                             pn, pc, MEM_HOST if host else MEM_DEVICE))
+        if host:
+            res = {k: v[:n_out.value].copy() for k, v in out.items()}
+            res["n_carried"] = n_car.value
+            return res
+        if ordered:
+            self._order_out(n_car)
+        out["n_out"], out["n_carried"] = n_out, n_car
+        return out
+
+    def _ids(self, fn, *head, cap=65536):
+        ids, ages, n = np.zeros(cap, np.int64), np.zeros(cap, np.int32), C.c_int(0)
+        self._check(fn(self.h, *head, C.c_void_p(ids.ctypes.data), C.c_void_p(ages.ctypes.data), cap, C.byref(n)))
+        return ids[:n.value].copy(), ages[:n.value].copy()
+
+    def frame_track_ids(self, cap=65536):
+        """(ids, ages) of the list frame_keypoints() returns (track carry on)."""
+        return self._ids(self.lib.svo_get_frame_track_ids, cap=cap)
+
+    def last_track_ids(self, cap=65536):
+        """(ids, ages at t1) of the tracks last_tracks() returns, in their order (track carry on)."""
+        return self._ids(self.lib.svo_get_last_track_ids, cap=cap)
+
+    def streams_track_ids(self, item, cap=65536):
+        """(ids, ages at t1) of the tracks streams_tracks(item) returns, in their order (track carry on)."""
+        return self._ids(self.lib.svo_streams_get_track_ids, int(item), cap=cap)
+
+    def streams_frame_tracks(self, stream_id, cap=65536):
+        """(keypoint records, ids, ages) of the list stream `stream_id` keeps for its next pair (track carry on)."""
+        kps = np.zeros(cap, dtype=KP_DTYPE)
+        ids, ages = self._ids(self.lib.svo_streams_get_frame_tracks, int(stream_id), C.c_void_p(kps.ctypes.data), cap=cap)
+        return kps[:len(ids)].copy(), ids, ages
 
     # ---- Shi-Tomasi corners (svo_set_lk_detector / svo_min_eigen_map / svo_gftt_detect) ------------
     def set_lk_detector(self, detector, max_corners=500, quality_level=0.01, min_distance=20.0):

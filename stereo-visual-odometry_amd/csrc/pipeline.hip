@@ -11,6 +11,7 @@
 // two-frame ring.
 #include <cstring>
 #include "abi_io.h"
+#include "carry.h"
 
 namespace svo {
 
@@ -90,6 +91,7 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
 struct StreamStep { const int32_t *ids; const uint8_t *init; };
 static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first = false,
                     const StreamStep *ss = nullptr);
+static const char *kTGather = "stream_gather", *kTScatter = "stream_scatter";
 
 // What a frame carries from one step to the next -- the list exists here only.  work[k]: the working array behind segment k (frame
 // slot f at work[k] + f * bytes[k]); is_count[k]: a count segment.  carry_last_frame moves them between frame slots, a stream
@@ -113,8 +115,97 @@ static int stream_segments(svo_ctx *ctx, uint8_t *work[kMaxSeg], size_t bytes[kM
         work[1] = (uint8_t *)ctx->kp_xy;        bytes[1] = cap * sizeof(float2);            is_count[1] = 0;
         work[2] = (uint8_t *)ctx->kp_resp;      bytes[2] = cap * sizeof(float);             is_count[2] = 0;
         work[3] = (uint8_t *)ctx->kp_n;         bytes[3] = sizeof(int);                     is_count[3] = 1;
+        if (ctx->carry_on) {
+            // svo_set_track_carry: the list's ids and ages travel with it
+            work[4] = (uint8_t *)ctx->kp_id;    bytes[4] = cap * sizeof(long long);         is_count[4] = 0;
+            work[5] = (uint8_t *)ctx->kp_age;   bytes[5] = cap * sizeof(int);               is_count[5] = 0;
+            return 6;
+        }
     }
     return 4;
+}
+
+// ---- track carry (svo_set_track_carry; the kernel and its rules: carry.hip) -------------------------------------------------
+static const char *kTCarry = "carry";
+
+int carry_alloc(svo_ctx *ctx)
+{
+    const size_t cap = (size_t)ctx->cfg.max_keypoints, nf = (size_t)ctx->n_img, np = (size_t)ctx->cfg.max_batch;
+    if (!ctx->carry_buf) {
+        BlockCut cut;
+        const size_t o_next = cut.add(sizeof(long long)), o_id = cut.add(sizeof(long long) * cap * nf), o_age = cut.add(sizeof(int) * cap * nf),
+                     o_tid = cut.add(sizeof(long long) * cap * np), o_tage = cut.add(sizeof(int) * cap * np),
+                     o_sorted = cut.add(sizeof(int) * cap * np), o_flag = cut.add(cap * np), o_dflag = cut.add(cap * np),
+                     o_dxy = cut.add(sizeof(float2) * cap * np), o_dresp = cut.add(sizeof(float) * cap * np);
+        uint8_t *s = nullptr;
+        if (dev_alloc(ctx, &s, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+        SVO_HIP(hipMemsetAsync(s, 0, cut.total(), ctx->stream));
+        ctx->carry_next = (long long *)(s + o_next);
+        ctx->kp_id = (long long *)(s + o_id); ctx->kp_age = (int *)(s + o_age);
+        ctx->trk_id = (long long *)(s + o_tid); ctx->trk_age = (int *)(s + o_tage);
+        ctx->carry_sorted = (int *)(s + o_sorted); ctx->carry_flag = s + o_flag; ctx->carry_dflag = s + o_dflag;
+        ctx->carry_dxy = (float2 *)(s + o_dxy); ctx->carry_dresp = (float *)(s + o_dresp);
+        ctx->carry_buf = s;
+    }
+    StreamSet &ss = ctx->streams;
+    if (ss.n > 0) {
+        // the store's share, in whichever order the set and the switch came (a call that failed half way finds what it made)
+        const size_t bytes[3] = {cap * sizeof(long long) * (size_t)ss.n + 16, cap * sizeof(int) * (size_t)ss.n + 16, sizeof(long long) * (size_t)ss.n};
+        uint8_t **at[3] = {&ss.seg[4], &ss.seg[5], (uint8_t **)&ss.next_id};
+        for (int k = 0; k < 3; k++) {
+            if (*at[k]) continue;
+            if (dev_alloc(ctx, at[k], bytes[k]) != SVO_OK) return SVO_ERR_HIP;
+            SVO_HIP(hipMemsetAsync(*at[k], 0, bytes[k], ctx->stream));
+        }
+        ss.seg_bytes[4] = cap * sizeof(long long); ss.seg_bytes[5] = cap * sizeof(int);
+    }
+    return SVO_OK;
+}
+
+// The carry step of n_pairs pairs (frame slot fp0 + p*fstep -> fc0 + p*fstep), behind the compaction and the count snapshot:
+// the new frames' detections become their merged lists, in place.  no_prev: a chain's first frame, which only gets its ids.
+static void launch_carry_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, const StreamStep *ss, bool no_prev)
+{
+    const size_t cap = (size_t)ctx->cfg.max_keypoints;
+    CarryMergeArgs a{};
+    a.w = ctx->cfg.width; a.h = ctx->cfg.height;
+    carry_grid(a.w, a.h, ctx->carry_min_distance, &a.cell, &a.cols, &a.rows);
+    a.min_d2 = ctx->carry_min_distance * ctx->carry_min_distance;
+    a.max_age = ctx->carry_max_age;
+    a.cap = a.out_cap = (int)cap;
+    a.stride = (int64_t)fstep * (int64_t)cap; a.n_stride = fstep;
+    a.q = ctx->pts_out[2]; a.keep = ctx->keep;
+    a.p_resp = ctx->kp_resp + (size_t)fp0 * cap; a.p_id = ctx->kp_id + (size_t)fp0 * cap; a.p_age = ctx->kp_age + (size_t)fp0 * cap;
+    a.p_n = no_prev ? nullptr : ctx->kp_n + fp0; a.n_trk = 0;
+    a.d_xy = ctx->kp_xy + (size_t)fc0 * cap; a.d_resp = ctx->kp_resp + (size_t)fc0 * cap; a.d_n = ctx->kp_n + fc0;
+    a.o_xy = ctx->kp_xy + (size_t)fc0 * cap; a.o_resp = ctx->kp_resp + (size_t)fc0 * cap;
+    a.o_id = ctx->kp_id + (size_t)fc0 * cap; a.o_age = ctx->kp_age + (size_t)fc0 * cap;
+    a.o_n = ctx->kp_n + fc0;
+    a.trk_id = ctx->trk_id; a.trk_age = ctx->trk_age;
+    a.sorted = ctx->carry_sorted; a.flag = ctx->carry_flag; a.dflag = ctx->carry_dflag; a.s_dxy = ctx->carry_dxy; a.s_dresp = ctx->carry_dresp;
+    if (!ss) {
+        // the online ring: one pair, one counter
+        a.next_id = ctx->carry_next;
+        a.fresh[0] = !no_prev && !ctx->carry_ids[fp0 & 1];
+        a.restart[0] = ctx->carry_restart;
+        ctx->carry_restart = false;
+        launch_carry_merge(a, 1, ctx->stream);
+        return;
+    }
+    StreamSet &set = ctx->streams;
+    a.next_id = set.next_id;
+    for (int i0 = 0; i0 < n_pairs; i0 += kCarryChunk) {
+        const int n = n_pairs - i0 < kCarryChunk ? n_pairs - i0 : kCarryChunk;
+        a.item0 = i0;
+        for (int t = 0; t < n; t++) {
+            const size_t id = (size_t)ss->ids[i0 + t];
+            a.cnt[t] = (int32_t)id;
+            a.fresh[t] = !ss->init[i0 + t] && !set.has_ids[id];     // (an init item has no previous list: the gather left its count 0)
+            a.restart[t] = set.restart[id];
+            set.restart[id] = 0; set.has_ids[id] = 1;
+        }
+        launch_carry_merge(a, n, ctx->stream);
+    }
 }
 
 // A micro-batch of a stream starts with the frame the previous one ended with: instead of building that frame's
@@ -289,6 +380,17 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
     }
     launch_triangulate_batch(ctx, n_pairs, cap, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, &snap);
     mark(ctx, kTTri);
+    ctx->carry_last_pairs = ctx->carry_on ? n_pairs : 0;
+    if (ctx->carry_on) {
+        // svo_set_track_carry: the new frames' lists = what was just tracked into them + their detections; the counts the
+        // pose stage reports are already frozen.  A stream set stores the new frames only now.
+        launch_carry_pairs(ctx, n_pairs, fp0, fc0, fstep, ss, false);
+        mark(ctx, kTCarry);
+        if (ss) {
+            for_stream_chunks(ss->ids, nullptr, n_pairs, [&](const StreamTable &tab, int i0, int n) { launch_stream_copy(ctx, tab, n, fc0 + i0, /*to_store*/ true); });
+            mark(ctx, kTScatter);
+        }
+    }
     return run_back(ctx, n_pairs, pose0_host, results_dev, false, ss);
 }
 
@@ -408,9 +510,15 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     int rc = ingest_frames(ctx, left, right, pitch, 0, cur, 1);
     if (rc) return rc;
     memset(res, 0, sizeof(*res));
+    ctx->carry_ids[cur] = ctx->carry_on;
     if (ctx->online_frames == 0) {
         // StereoInit_f2f (:78-92): detect only
         SVO_TRY(count_read(ctx, ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur, &res->n_cur_kps));
+        if (ctx->carry_on) {                     // svo_set_track_carry: the chain's first list gets its ids (the count above stays the detector's)
+            launch_carry_pairs(ctx, 1, prev, cur, 0, nullptr, /*no_prev*/ true);
+            mark(ctx, kTCarry);
+            SVO_HIP(hipGetLastError());
+        }
         res->ok = 1;
         for (int i = 0; i < 9; i++) res->R[i] = (i % 4 == 0) ? 1.0 : 0.0;
         for (int i = 0; i < 16; i++) { res->T_rel_inv[i] = (i % 5 == 0) ? 1.0 : 0.0; res->pose[i] = ctx->pose[i]; }
@@ -429,7 +537,6 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
 }
 
 // ---- stream sets: many independent live streams through one launch set -----------------------------------------------
-static const char *kTGather = "stream_gather", *kTScatter = "stream_scatter";
 
 int pipeline_streams_create(svo_ctx *ctx, int n_streams)
 {
@@ -448,8 +555,11 @@ int pipeline_streams_create(svo_ctx *ctx, int n_streams)
     if (dev_alloc(ctx, &ss.pose, sizeof(double) * 16 * (size_t)n_streams) != SVO_OK) return SVO_ERR_HIP;
     ss.n_frames.assign((size_t)n_streams, 0);
     ss.seen.assign((size_t)n_streams, 0);
+    ss.has_ids.assign((size_t)n_streams, 0);
+    ss.restart.assign((size_t)n_streams, 1);
     ss.call = 0;
     ss.n = n_streams;                                  // the set exists from here on
+    if (ctx->carry_buf) SVO_TRY(carry_alloc(ctx));     // svo_set_track_carry came first: the store's ids, ages and counters
     launch_streams_set_pose(ctx, 0, n_streams, nullptr);
     SVO_HIP(hipGetLastError());
     return SVO_OK;
@@ -462,7 +572,7 @@ int pipeline_streams_reset(svo_ctx *ctx, int id)
     SVO_ARG(id >= -1 && id < ss.n, "stream id out of range");
     SVO_HIP(hipSetDevice(ctx->device));
     const int id0 = id < 0 ? 0 : id, n = id < 0 ? ss.n : 1;
-    for (int s = id0; s < id0 + n; s++) ss.n_frames[(size_t)s] = 0;
+    for (int s = id0; s < id0 + n; s++) { ss.n_frames[(size_t)s] = 0; ss.restart[(size_t)s] = 1; }
     launch_streams_set_pose(ctx, id0, n, nullptr);     // in stream order: steps queued before it keep their poses
     SVO_HIP(hipGetLastError());
     return SVO_OK;
@@ -527,8 +637,11 @@ int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t
     mark(ctx, kTGather);
     int rc = ingest_frames(ctx, L, R, pitch, m == 1 ? 0 : frame_stride, m, m);
     if (rc) return rc;
-    for_stream_chunks(ids, nullptr, m, [&](const StreamTable &tab, int i0, int n) { launch_stream_copy(ctx, tab, n, m + i0, /*to_store*/ true); });
-    mark(ctx, kTScatter);
+    if (!ctx->carry_on) {                               // (with track carry the lists are still to be merged: run_pairs stores the frames)
+        for_stream_chunks(ids, nullptr, m, [&](const StreamTable &tab, int i0, int n) { launch_stream_copy(ctx, tab, n, m + i0, /*to_store*/ true); });
+        mark(ctx, kTScatter);
+        for (int i = 0; i < m; i++) ss.has_ids[(size_t)ids[i]] = 0;
+    }
     // last_frame_ = current_frame_ on every outcome (src/tracking.cpp:59-68): the store already holds the new frames
     for (int i = 0; i < m; i++) ss.n_frames[(size_t)ids[i]]++;
     const StreamStep step{ids, init.data()};

@@ -9,6 +9,7 @@
 #include <new>
 #include <vector>
 #include "abi_io.h"
+#include "carry.h"
 
 using namespace svo;
 
@@ -733,6 +734,7 @@ extern "C" int svo_reset(svo_ctx *ctx)
 {
     if (!ctx) return SVO_ERR_ARG;
     ctx->online_frames = 0; ctx->online_cur = 0;
+    ctx->carry_restart = true;                   // svo_set_track_carry: the next chain's ids start at 0
     for (int i = 0; i < 16; i++) ctx->pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
     return SVO_OK;
 }
@@ -880,6 +882,10 @@ static int track_batch(svo_ctx *ctx, int w, int h, bool resize, const uint8_t *l
     SVO_ARG(n_frames >= 2 && n_frames - 1 <= ctx->cfg.max_batch, "n_frames - 1 must be in [1, max_batch]");
     SVO_ARG(pitch >= w && frame_stride >= (int64_t)pitch * h, "bad pitch / frame_stride");
     SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
+    if (ctx->carry_on) {
+        ctx->err = "track carry is on (svo_set_track_carry): a batch treats its pairs as independent; use svo_add_frame / svo_streams_step";
+        return SVO_ERR_STATE;
+    }
     SVO_HIP(hipSetDevice(ctx->device));
     if (resize) {
         const int rc = ingest_resize(ctx, &lefts, &rights, &pitch, &frame_stride, n_frames);
@@ -1670,4 +1676,178 @@ extern "C" int svo_get_refine_points(svo_ctx *ctx, int pair, double *X, int cap,
     SVO_HIP(hipSetDevice(ctx->device));
     if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
     return ba_read_points(ctx, pair, X, cap, n_out);
+}
+
+// ---- track carry: LK tracks kept across frames under persistent ids (carry.hip: carry_merge_kernel) ------------------------
+static bool carry_params_ok(double min_distance, int max_age)
+{
+    return std::isfinite(min_distance) && min_distance >= 1.0 && min_distance <= 256.0 && max_age >= 0;
+}
+
+extern "C" int svo_set_track_carry(svo_ctx *ctx, int on, double min_distance, int max_age)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (!on) { ctx->carry_on = false; return SVO_OK; }               // off: the other arguments are ignored
+    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "track carry is an LK-mode option (ORB mode matches descriptors frame to frame)");
+    SVO_ARG(carry_params_ok(min_distance, max_age), "min_distance must be finite and in [1, 256], max_age >= 0");
+    SVO_HIP(hipSetDevice(ctx->device));
+    SVO_TRY(carry_alloc(ctx));                                       // first enabling call: the working frames' and an existing stream set's share
+    ctx->carry_on = true; ctx->carry_min_distance = min_distance; ctx->carry_max_age = max_age;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_track_carry(const svo_ctx *ctx, int *on, double *min_distance, int *max_age)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (on) *on = ctx->carry_on ? 1 : 0;
+    if (min_distance) *min_distance = ctx->carry_on ? ctx->carry_min_distance : 0.0;
+    if (max_age) *max_age = ctx->carry_on ? ctx->carry_max_age : 0;
+    return SVO_OK;
+}
+
+extern "C" int svo_carry_merge(svo_ctx *ctx, int width, int height, double min_distance, int max_age, const svo_pt2f *trk_xy,
+                               const float *trk_resp, const int64_t *trk_id, const int32_t *trk_age, const uint8_t *trk_keep, int n_trk,
+                               const svo_pt2f *det_xy, const float *det_resp, int n_det, int64_t next_id, svo_pt2f *out_xy,
+                               float *out_resp, int64_t *out_id, int32_t *out_age, int32_t *out_src, int cap, int *n_out, int *n_carried,
+                               int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(width >= 1 && height >= 1 && width <= 16384 && height <= 16384, "width / height out of range");
+    SVO_ARG(carry_params_ok(min_distance, max_age), "min_distance must be finite and in [1, 256], max_age >= 0");
+    SVO_ARG(n_trk >= 0 && n_det >= 0 && n_trk <= (1 << 20) && n_det <= (1 << 20), "bad n_trk / n_det");
+    SVO_ARG(n_trk == 0 || (trk_xy && trk_resp && trk_id && trk_age && trk_keep), "null track list");
+    SVO_ARG(n_det == 0 || (det_xy && det_resp), "null detection list");
+    SVO_ARG(cap >= n_trk && cap <= (1 << 21), "cap < n_trk: only detections may fall off the list");
+    SVO_ARG(n_out && n_carried && (cap == 0 || (out_xy && out_resp && out_id && out_age && out_src)), "null output");
+    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "mem must be SVO_MEM_HOST or SVO_MEM_DEVICE");
+    SVO_HIP(hipSetDevice(ctx->device));
+    const bool host = mem == SVO_MEM_HOST;
+    const size_t nt = (size_t)n_trk, nd = (size_t)n_det, nc = (size_t)cap, ns = std::max(std::max(nt, nd), (size_t)1);
+    BlockCut cut;
+    const size_t o_cnt = cut.add(256), o_sorted = cut.add(sizeof(int) * ns), o_flag = cut.add(ns), o_dflag = cut.add(ns),
+                 o_sxy = cut.add(sizeof(float2) * ns), o_sresp = cut.add(sizeof(float) * ns);
+    const size_t i_xy = cut.add(host ? sizeof(float2) * nt : 0), i_resp = cut.add(host ? sizeof(float) * nt : 0),
+                 i_id = cut.add(host ? sizeof(long long) * nt : 0), i_age = cut.add(host ? sizeof(int) * nt : 0), i_keep = cut.add(host ? nt : 0),
+                 i_dxy = cut.add(host ? sizeof(float2) * nd : 0), i_dresp = cut.add(host ? sizeof(float) * nd : 0);
+    const size_t r_xy = cut.add(host ? sizeof(float2) * nc : 0), r_resp = cut.add(host ? sizeof(float) * nc : 0),
+                 r_id = cut.add(host ? sizeof(long long) * nc : 0), r_age = cut.add(host ? sizeof(int) * nc : 0), r_src = cut.add(host ? sizeof(int) * nc : 0);
+    if (dev_reserve(ctx, &ctx->carry_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+    uint8_t *s = ctx->carry_stage.base;
+    CarryMergeArgs a{};
+    a.w = width; a.h = height;
+    carry_grid(width, height, min_distance, &a.cell, &a.cols, &a.rows);
+    a.min_d2 = min_distance * min_distance; a.max_age = max_age;
+    a.cap = (int)ns; a.out_cap = cap;
+    a.n_trk = n_trk; a.n_det = n_det; a.next0 = (long long)next_id;
+    SVO_TRY(to_device(ctx, (const float2 *)trk_xy, (float2 *)(s + i_xy), nt, mem, &a.q));
+    SVO_TRY(to_device(ctx, trk_resp, (float *)(s + i_resp), nt, mem, &a.p_resp));
+    SVO_TRY(to_device(ctx, (const long long *)trk_id, (long long *)(s + i_id), nt, mem, &a.p_id));
+    SVO_TRY(to_device(ctx, (const int *)trk_age, (int *)(s + i_age), nt, mem, &a.p_age));
+    SVO_TRY(to_device(ctx, trk_keep, s + i_keep, nt, mem, &a.keep));
+    SVO_TRY(to_device(ctx, (const float2 *)det_xy, (float2 *)(s + i_dxy), nd, mem, &a.d_xy));
+    SVO_TRY(to_device(ctx, det_resp, (float *)(s + i_dresp), nd, mem, &a.d_resp));
+    a.o_xy = host ? (float2 *)(s + r_xy) : (float2 *)out_xy; a.o_resp = host ? (float *)(s + r_resp) : out_resp;
+    a.o_id = host ? (long long *)(s + r_id) : (long long *)out_id; a.o_age = host ? (int *)(s + r_age) : (int *)out_age;
+    a.o_src = host ? (int *)(s + r_src) : (int *)out_src;
+    a.o_n = host ? (int *)(s + o_cnt) : n_out; a.o_carried = host ? (int *)(s + o_cnt) + 1 : n_carried;
+    a.sorted = (int *)(s + o_sorted); a.flag = s + o_flag; a.dflag = s + o_dflag; a.s_dxy = (float2 *)(s + o_sxy); a.s_dresp = (float *)(s + o_sresp);
+    launch_carry_merge(a, 1, ctx->stream);
+    SVO_HIP(hipGetLastError());
+    if (!host) return SVO_OK;
+    const int *h;
+    SVO_TRY(count_fetch(ctx, 0, a.o_n, 2));
+    SVO_TRY(counts_wait(ctx, &h));
+    *n_out = h[0]; *n_carried = h[1];
+    const size_t n = (size_t)h[0];
+    SVO_TRY(from_device(ctx, (float2 *)out_xy, (const float2 *)a.o_xy, n, mem));
+    SVO_TRY(from_device(ctx, out_resp, (const float *)a.o_resp, n, mem));
+    SVO_TRY(from_device(ctx, (long long *)out_id, (const long long *)a.o_id, n, mem));
+    SVO_TRY(from_device(ctx, (int *)out_age, (const int *)a.o_age, n, mem));
+    SVO_TRY(from_device(ctx, (int *)out_src, (const int *)a.o_src, n, mem));
+    return io_done(ctx, mem);
+}
+
+// n ids and ages at `offset` of two device lists -> the caller's.  Capacity rule of the read-backs below: ids / ages null asks
+// for the count only; otherwise the count must fit `cap`.
+static int read_ids(svo_ctx *ctx, const long long *d_id, const int *d_age, size_t offset, int n, int64_t *ids, int32_t *ages, int cap, int *n_out)
+{
+    *n_out = n;
+    if (!ids && !ages) return SVO_OK;
+    SVO_ARG(n <= cap, "id capacity too small");
+    SVO_TRY(from_device(ctx, (long long *)ids, d_id + offset, (size_t)n, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, (int *)ages, d_age + offset, (size_t)n, SVO_MEM_HOST));
+    return io_done(ctx, SVO_MEM_HOST);
+}
+
+extern "C" int svo_get_frame_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(n_out && cap >= 0, "null output");
+    SVO_ARG(ctx->online_frames > 0, "no frame has been added");
+    const int cur = ctx->online_cur;
+    SVO_ARG(ctx->carry_ids[cur] && ctx->carry_buf, "track carry was off when the last frame was added (svo_set_track_carry)");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    int n = 0;
+    SVO_TRY(count_read(ctx, ctx->kp_n + cur, &n));
+    const size_t kcap = (size_t)ctx->cfg.max_keypoints;
+    n = n < (int)kcap ? n : (int)kcap;
+    return read_ids(ctx, ctx->kp_id, ctx->kp_age, (size_t)cur * kcap, n, ids, ages, cap, n_out);
+}
+
+// ids / ages-at-t1 of the tracks of pair `pair` of the last fused launch, in the order of svo_get_batch_tracks' lists
+static int pair_track_ids(svo_ctx *ctx, int pair, int64_t *ids, int32_t *ages, int cap, int *n_out)
+{
+    SVO_ARG(n_out && cap >= 0, "null output");
+    SVO_ARG(ctx->carry_last_pairs > 0 && ctx->carry_buf, "track carry was off for the last step (svo_set_track_carry)");
+    SVO_ARG(pair >= 0 && pair < ctx->carry_last_pairs, "item is not part of the last step");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    int n;
+    SVO_TRY(count_read(ctx, ctx->m_out + pair, &n));
+    SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "corrupt track count");
+    return read_ids(ctx, ctx->trk_id, ctx->trk_age, (size_t)pair * ctx->cfg.max_keypoints, n, ids, ages, cap, n_out);
+}
+
+extern "C" int svo_get_last_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->online_frames >= 2, "no pair has been tracked by svo_add_frame");
+    return pair_track_ids(ctx, 0, ids, ages, cap, n_out);
+}
+
+extern "C" int svo_streams_get_track_ids(svo_ctx *ctx, int item, int64_t *ids, int32_t *ages, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
+    return pair_track_ids(ctx, item, ids, ages, cap, n_out);
+}
+
+extern "C" int svo_streams_get_frame_tracks(svo_ctx *ctx, int stream_id, svo_keypoint *kps, int64_t *ids, int32_t *ages, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    StreamSet &ss = ctx->streams;
+    SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
+    SVO_ARG(stream_id >= 0 && stream_id < ss.n, "stream id out of range");
+    SVO_ARG(n_out && cap >= 0, "null output");
+    SVO_ARG(ss.n_frames[(size_t)stream_id] > 0 && ss.has_ids[(size_t)stream_id] && ss.seg[4] && ss.seg[5],
+            "the stream has no stored list with ids (no frame yet, or track carry was off for its last step)");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    const size_t kcap = (size_t)ctx->cfg.max_keypoints, sid = (size_t)stream_id;
+    int n = 0;
+    SVO_TRY(count_read(ctx, (const int *)ss.seg[3] + sid, &n));
+    n = n < (int)kcap ? n : (int)kcap;
+    *n_out = n;
+    if (!kps && !ids && !ages) return SVO_OK;
+    SVO_ARG(n <= cap, "capacity too small");
+    if (kps && n > 0) {
+        std::vector<float2> xy((size_t)n);
+        std::vector<float> resp((size_t)n);
+        SVO_TRY(from_device(ctx, xy.data(), (const float2 *)ss.seg[1] + sid * kcap, (size_t)n, SVO_MEM_HOST));
+        SVO_TRY(from_device(ctx, resp.data(), (const float *)ss.seg[2] + sid * kcap, (size_t)n, SVO_MEM_HOST));
+        SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+        format_keypoints(xy.data(), resp.data(), n, kps);
+    }
+    return read_ids(ctx, (const long long *)ss.seg[4], (const int *)ss.seg[5], sid * kcap, n, ids, ages, cap, n_out);
 }

@@ -42,13 +42,17 @@ struct DevArena {
 // A stream set (svo_streams_create): n independent live stereo streams of one context.  What a stream keeps in HBM between
 // steps is the segments stream_segments() lists (pipeline.hip; carry_last_frame moves the same list) -- seg[k] + id * seg_bytes[k],
 // k < n_seg -- and its frame_pose_ (pose + 16 * id); the INITING / TRACKING state is host-side (steps are issued in host order).
-constexpr int kMaxSeg = 5;               // segments a frame carries at most (ORB mode with the guided matcher: the stereo block)
+constexpr int kMaxSeg = 6;               // segments a frame carries at most (LK mode with track carry: the ids and the ages)
 struct StreamSet {
     int n = 0;
     int n_seg = 0;
-    uint8_t *seg[kMaxSeg] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t seg_bytes[kMaxSeg] = {0, 0, 0, 0, 0};
+    uint8_t *seg[kMaxSeg] = {};
+    size_t seg_bytes[kMaxSeg] = {};
     double *pose = nullptr;
+    // track carry (svo_set_track_carry): the id counter of every stream, on the device; which streams' stored lists have ids, and
+    // which start their ids over with the next step (a new or a reset stream)
+    long long *next_id = nullptr;
+    std::vector<uint8_t> has_ids, restart;
     std::vector<int> n_frames;        // frames fed since the stream's reset (0: INITING)
     std::vector<int> seen;            // call number a stream id was last named in (duplicate check)
     int call = 0;
@@ -202,6 +206,20 @@ struct svo_ctx {
     int refine_last_pairs = 0;                           // pairs the stage refined in the most recent fused launch (0: it was off)
     int refine_last_mode = SVO_REFINE_OFF;               // ... and the mode that launch ran in
     uint8_t *ba_buf = nullptr;                           // SVO_REFINE_BA: the pairs' points, two buffers, + stage-call scratch (ba.hip)
+    // ---- track carry (svo_set_track_carry / svo_carry_merge, carry.hip; off and nothing allocated until it is first enabled)
+    bool carry_on = false;
+    double carry_min_distance = 3.0;
+    int carry_max_age = 0;
+    uint8_t *carry_buf = nullptr;                        // ONE block, cut into what follows
+    long long *kp_id = nullptr; int *kp_age = nullptr;   // beside kp_xy / kp_resp: n_img frame slots x max_keypoints
+    long long *trk_id = nullptr; int *trk_age = nullptr; // id / age-at-t1 of a pair's tracks, in the order of cmp[]: max_batch x max_keypoints
+    int *carry_sorted = nullptr; uint8_t *carry_flag = nullptr, *carry_dflag = nullptr;       // kernel scratch, max_batch x max_keypoints
+    float2 *carry_dxy = nullptr; float *carry_dresp = nullptr;
+    long long *carry_next = nullptr;                     // the online chain's id counter, on the device
+    bool carry_ids[2] = {false, false};                  // the list in online ring slot 0 / 1 has ids
+    bool carry_restart = true;                           // the online chain's ids start at 0 with its next carry launch
+    int carry_last_pairs = 0;                            // pairs of the most recent fused launch that ran with carry (0: it was off)
+    DevScratch carry_stage;                              // svo_carry_merge: the caller's lists, the outputs and the scratch
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -304,6 +322,7 @@ void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const i
 int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, svo_step_result *res);
 int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch, int64_t frame_stride,
                          int n_frames, const double *pose0, svo_step_result *results, int results_mem, int carry_first);
+int carry_alloc(svo_ctx *ctx);                           // track carry: its block and, for an existing stream set, the store's share
 int pipeline_streams_create(svo_ctx *ctx, int n_streams);
 int pipeline_streams_reset(svo_ctx *ctx, int id);
 int pipeline_streams_set_pose(svo_ctx *ctx, int id, const double *pose);

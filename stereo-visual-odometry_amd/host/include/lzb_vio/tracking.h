@@ -75,6 +75,16 @@ public:
     // non-finite radius / disparity, and guided without track_mode ORB_stereof2f_pnp are refused (false + a message that
     // names the key).  Applied right after svo_create.
     static bool ReadOrbMatcher(int *mode, int *th_stereo, int *th_track, double *ratio, double *radius, double *max_disparity, std::string *err);
+    // additive YAML keys track_carry: 0 | 1 (absent: 0), track_carry_min_distance (3.0 px) and track_carry_max_age (0 = unlimited):
+    // LK tracks kept across frames under persistent ids (svo_set_track_carry, include/svo_abi.h); Parameter carries them.
+    // ReadTrackCarry reads and checks them for the loaded YAML: a switch that is neither 0 nor 1, a distance that is not a finite
+    // number in [1, 256], a negative age, and track_carry 1 with track_mode ORB_stereof2f_pnp are refused (false + a message that
+    // names the key).  Applied right after svo_create.  It is a feature of the per-frame paths: System refuses it together with
+    // batch_size > 1, stream_depth > 0 and --split-pairs.
+    static bool ReadTrackCarry(int *on, double *min_distance, int *max_age, std::string *err);
+    bool TrackCarry() const { return track_carry_ != 0; }
+    // id and age at t1 of every track GetLastTracks returns, in its order (track carry on; false otherwise)
+    bool GetLastTrackIds(std::vector<int64_t> &ids, std::vector<int32_t> &ages);
     // The stage the reference declares as Tracking::G2O_EstimatePose_PnP (include/lzb_vio/tracking.h:82; its body there is a copy
     // of the OpenCV one and it is never called): here it does what its name says, through svo_refine_pose -- a robust motion-only
     // bundle adjustment of (rotation, translation) on the points' t2 observations in the left and, when pointsRight_t2 is not null,
@@ -139,6 +149,8 @@ private:
     double pose_refine_sigma_ = 1.0;
     int orb_matcher_ = SVO_ORB_MATCHER_BRUTE, orb_match_th_stereo_ = 75, orb_match_th_track_ = 100;                     // orb_matcher / orb_match_*
     double orb_match_ratio_ = 0.9, orb_match_radius_ = 0.0, orb_max_disparity_ = 0.0;
+    int track_carry_ = 0, track_carry_max_age_ = 0;          // additive YAML keys track_carry / track_carry_max_age
+    double track_carry_min_distance_ = 3.0;                  // ... and track_carry_min_distance
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128
     double image_scale_ = 1.0;                               // additive YAML key image_scale (1 = no ingest stage)
     int image_interp_ = SVO_INTERP_NEAREST;                  // additive YAML key image_interp: nearest (default) | linear

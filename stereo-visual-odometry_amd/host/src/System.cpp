@@ -360,6 +360,12 @@ System::System(std::string &config_path) : config_file_path_(config_path)
     batch_size_ = Config::Has("batch_size") ? Config::Get<int>("batch_size") : 1;
     decode_threads_ = Config::Has("decode_threads") ? Config::Get<int>("decode_threads") : 0;    // 0: the usable cores
     stream_depth_ = Config::Has("stream_depth") ? Config::Get<int>("stream_depth") : 0;           // 0: Step_ros is synchronous
+    // track_carry is a feature of the per-frame paths: a batch treats its pairs as independent (svo_set_track_carry)
+    if (tracking_->TrackCarry() && (batch_size_ > 1 || stream_depth_ > 0)) {
+        fprintf(stderr, "%s: track_carry: 1 with %s (tracks are carried by the per-frame loop and --interleave only; a batch treats "
+                        "its pairs as independent)\n", config_file_path_.c_str(), batch_size_ > 1 ? "batch_size > 1" : "stream_depth > 0");
+        exit(2);
+    }
     if (stream_depth_ > 0 && tracks_file_)
         LZB_LOG("WARNING", "tracks_file is set together with stream_depth: the pipelined stream keeps poses only, the tracks file "
                            "will hold its header and nothing else (use the per-frame loop or batch_size for track dumps)");
@@ -409,7 +415,9 @@ bool System::SetTracksFile(const std::string &path)
 {
     if (tracks_file_) fclose(tracks_file_);
     tracks_file_ = fopen(path.c_str(), "w");
-    if (tracks_file_) fprintf(tracks_file_, "# F frame ok fail_stage n_cur_kps n_tracked n_inliers / T x1l y1l x1r y1r x2l y2l inlier\n");
+    if (tracks_file_)
+        fprintf(tracks_file_, "# F frame ok fail_stage n_cur_kps n_tracked n_inliers / T x1l y1l x1r y1r x2l y2l inlier%s\n",
+                tracking_ && tracking_->TrackCarry() ? " id age" : "");
     return tracks_file_ != nullptr;
 }
 
@@ -422,8 +430,15 @@ void System::WriteTracks()
     std::vector<cv::Point2f> a, b, c;
     std::vector<unsigned char> in;
     if (!tracking_->GetLastTracks(a, b, c, in)) return;
-    for (size_t i = 0; i < a.size(); i++)
-        fprintf(tracks_file_, "T %.4f %.4f %.4f %.4f %.4f %.4f %d\n", a[i].x, a[i].y, b[i].x, b[i].y, c[i].x, c[i].y, (int)in[i]);
+    // track_carry: 1 -- every row ends with the track's persistent id and its age at t1
+    std::vector<int64_t> ids;
+    std::vector<int32_t> ages;
+    const bool carry = tracking_->TrackCarry() && tracking_->GetLastTrackIds(ids, ages) && ids.size() == a.size();
+    for (size_t i = 0; i < a.size(); i++) {
+        fprintf(tracks_file_, "T %.4f %.4f %.4f %.4f %.4f %.4f %d", a[i].x, a[i].y, b[i].x, b[i].y, c[i].x, c[i].y, (int)in[i]);
+        if (carry) fprintf(tracks_file_, " %lld %d", (long long)ids[i], (int)ages[i]);
+        fputc('\n', tracks_file_);
+    }
 }
 
 bool System::SetPoseFile(const std::string &path)
@@ -541,6 +556,11 @@ Frame::Ptr System::NextFrame_kitti()
 // decoder threads fill the other page-locked buffer with chunk c+1.
 void System::RunBatched(int B, int decode_threads)
 {
+    if (tracking_->TrackCarry()) {
+        LZB_LOG("ERROR", "RunBatched with track_carry: 1: a batch treats its pairs as independent (use Run() per frame or --interleave)%s", "");
+        run_failed_ = true;
+        return;
+    }
     cv::Mat l0, r0;
     if (!ReadStereo(frame_base_, l0, r0)) { LZB_LOG("WARNING", "cannot find images at index %d", frame_base_); return; }
     const int w = l0.cols, h = l0.rows;
@@ -901,10 +921,6 @@ int RunSequences(const std::vector<std::string> &yamls, const std::vector<std::s
 int RunSplitPairs(const std::string &yaml, const std::string &pose_file, int n_parts, int n_devices,
                   std::vector<SequenceReport> *report)
 {
-    if (n_devices <= 0 && (svo_device_count(&n_devices) != SVO_OK || n_devices <= 0)) {
-        LZB_LOG("ERROR", "no HIP device: %s not run (there is no CPU path)", yaml.c_str());
-        return 1;
-    }
     std::string path = yaml;
     // The probe and the chunk Systems hand their records to a sink: none of them may open (= truncate) the pose_file /
     // tracks_file the YAML names.  The poses of the whole sequence go to `pose_file`, or to the YAML's pose_file when the
@@ -915,9 +931,20 @@ int RunSplitPairs(const std::string &yaml, const std::string &pose_file, int n_p
     const int n_pairs = n_frames - 1;
     const int default_batch = probe->BatchSize() > 1 ? probe->BatchSize() : 256;
     const std::string out_path = !pose_file.empty() ? pose_file : probe->YamlPoseFile();
+    if (probe->TrackCarry()) {
+        System::DeferYamlOutputs(false);
+        fprintf(stderr, "%s: track_carry: 1 with --split-pairs (the chunks are tracked as batches of independent pairs)\n", yaml.c_str());
+        exit(2);                                           // refused on the host like the constructor's key errors
+    }
     if (!probe->YamlTracksFile().empty())
         LZB_LOG("WARNING", "tracks_file is not written by --split-pairs runs (the chunks keep relative motions only)%s", "");
     probe.reset();
+    // (after the YAML's own refusals, which need no device)
+    if (n_devices <= 0 && (svo_device_count(&n_devices) != SVO_OK || n_devices <= 0)) {
+        System::DeferYamlOutputs(false);
+        LZB_LOG("ERROR", "no HIP device: %s not run (there is no CPU path)", yaml.c_str());
+        return 1;
+    }
     if (n_pairs < 1) { System::DeferYamlOutputs(false); LZB_LOG("ERROR", "%s: fewer than two stereo frames", yaml.c_str()); return 1; }
     if (n_parts < 1) n_parts = 1;
     if (n_parts > n_pairs) n_parts = n_pairs;

@@ -163,6 +163,8 @@ int RunInterleaved(const std::vector<std::string> &yamls, const std::vector<std:
         if (!Tracking::ReadPoseRefine(&rmode, &rrounds, &riters, &rsigma, &rmin, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
         // ... and orb_matcher / orb_match_th_stereo / _th_track / _ratio / _radius / orb_max_disparity
         int mmode, mts, mtt; double mra, mrd, mmd;
+        int con, cma; double cmd;
+        if (!Tracking::ReadTrackCarry(&con, &cmd, &cma, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
         if (!Tracking::ReadOrbMatcher(&mmode, &mts, &mtt, &mra, &mrd, &mmd, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
     }
     for (int s = 0; s < n; s++) {

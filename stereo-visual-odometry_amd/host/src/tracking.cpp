@@ -117,6 +117,24 @@ bool Tracking::ReadOrbMatcher(int *mode, int *th_stereo, int *th_track, double *
     return true;
 }
 
+bool Tracking::ReadTrackCarry(int *on, double *min_distance, int *max_age, std::string *err)
+{
+    *on = 0; *min_distance = 3.0; *max_age = 0;
+    // (a value that does not parse as a number reads as 0)
+    const int c = Config::Has("track_carry") ? Config::Get<int>("track_carry") : 0;
+    const double md = Config::Has("track_carry_min_distance") ? Config::Get<double>("track_carry_min_distance") : 3.0;
+    const int ma = Config::Has("track_carry_max_age") ? Config::Get<int>("track_carry_max_age") : 0;
+    char msg[240] = "";
+    if (c != 0 && c != 1) snprintf(msg, sizeof(msg), "track_carry: %d is neither 0 nor 1", c);
+    else if (!(std::isfinite(md) && md >= 1.0 && md <= 256.0)) snprintf(msg, sizeof(msg), "track_carry_min_distance: %g is not a finite number in [1, 256]", md);
+    else if (ma < 0) snprintf(msg, sizeof(msg), "track_carry_max_age: %d is < 0 (0 = unlimited)", ma);
+    else if (c == 1 && Config::Has("track_mode") && Config::Get<std::string>("track_mode") == "ORB_stereof2f_pnp")
+        snprintf(msg, sizeof(msg), "track_carry: 1 with track_mode ORB_stereof2f_pnp (track carry is an LK-mode option)");
+    if (msg[0]) { if (err) *err = msg; return false; }
+    *on = c; *min_distance = md; *max_age = ma;
+    return true;
+}
+
 bool Tracking::G2O_EstimatePose_PnP(const double projMatrl[12], const double projMatrr[12], const std::vector<cv::Point2f> &pointsLeft_t2,
                                     const std::vector<cv::Point2f> *pointsRight_t2, const std::vector<cv::Point3f> &points3D_t0,
                                     double rotation[3], double translation[3], svo_refine_result *result)
@@ -176,6 +194,11 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
     } else if (pose_refine_ != SVO_REFINE_OFF)
         LZB_LOG("INFO", "pose_refine: %s (pose_refine_rounds %d, pose_refine_iters %d, pose_refine_sigma %g, pose_refine_min_inliers %d)",
                 pose_refine_ == SVO_REFINE_BA ? "ba" : "reproj", pose_refine_rounds_, pose_refine_iters_, pose_refine_sigma_, pose_refine_min_inliers_);
+    std::string carry_error;
+    if (!ReadTrackCarry(&track_carry_, &track_carry_min_distance_, &track_carry_max_age_, &carry_error)) {
+        if (config_error_.empty()) config_error_ = carry_error;
+    } else if (track_carry_)
+        LZB_LOG("INFO", "track_carry: 1 (track_carry_min_distance %g, track_carry_max_age %d)", track_carry_min_distance_, track_carry_max_age_);
     std::string matcher_error;
     if (!ReadOrbMatcher(&orb_matcher_, &orb_match_th_stereo_, &orb_match_th_track_, &orb_match_ratio_, &orb_match_radius_,
                         &orb_max_disparity_, &matcher_error)) {
@@ -334,6 +357,13 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
         ctx_ = nullptr;
         return false;
     }
+    if (track_carry_ && (rc = svo_set_track_carry(ctx_, 1, track_carry_min_distance_, track_carry_max_age_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_track_carry (track_carry 1, track_carry_min_distance %g, track_carry_max_age %d) failed (%d): %s",
+                track_carry_min_distance_, track_carry_max_age_, rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
     ctx_w_ = src_w; ctx_h_ = src_h; ctx_batch_ = max_batch;
     work_w_ = width; work_h_ = height;
     if (resized) svo_set_pose(ctx_, frame_pose_.m);          // the new context's first frame only initialises; the chain goes on
@@ -428,6 +458,18 @@ bool Tracking::GetLastTracks(std::vector<cv::Point2f> &t1_left, std::vector<cv::
         t1_right.push_back(cv::Point2f{b[i].x, b[i].y});
         t2_left.push_back(cv::Point2f{c[i].x, c[i].y});
     }
+    return true;
+}
+
+bool Tracking::GetLastTrackIds(std::vector<int64_t> &ids, std::vector<int32_t> &ages)
+{
+    ids.clear(); ages.clear();
+    if (!ctx_ || !track_carry_) return false;
+    const int cap = last_.n_tracked > 0 ? last_.n_tracked : 0;
+    ids.resize((size_t)cap + 1); ages.resize((size_t)cap + 1);
+    int n = 0;
+    if (svo_get_last_track_ids(ctx_, ids.data(), ages.data(), cap, &n) != SVO_OK) { ids.clear(); ages.clear(); return false; }
+    ids.resize((size_t)n); ages.resize((size_t)n);
     return true;
 }
 
