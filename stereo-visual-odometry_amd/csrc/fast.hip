@@ -2,27 +2,34 @@
 // output, for gfx950.  Replaces cv::FAST(img, kps, thr, true) at reference src/tracking.cpp:101
 // (Tracking::Detect_OpenCVFASTFeatures).  All-integer: bit-exact against oracle/fast.c.
 //
-// Two launches per batch of images:
-//   fast_score_kernel : one 64x16 pixel tile per 256-thread workgroup.  The raw tile (+4 halo)
+// Two launches per batch of images, and no dense score map between them: a corner is ~0.5 % of the pixels, so
+// what crosses HBM is the corners themselves (layout and bounds: fast_scratch.h).
+//   fast_score_kernel : one 64x32 pixel tile per 256-thread workgroup.  The raw tile (+4 halo)
 //       is staged in LDS once; the segment test + corner score are evaluated for the tile plus
 //       a 1-pixel ring (the NMS neighbours) in three passes over compacted LDS position lists
-//       (quick reject -> arc test -> score), NMS is done out of LDS, the suppressed score map
-//       (u8, 0 = no keypoint) goes to HBM with 64-byte coalesced row stores, and per-row
-//       keypoint counts are accumulated with one integer atomic per (row, tile).
-//   fast_emit_kernel  : one wave per image row; its output offset is the sum of the row counts
-//       above it (<= 17 coalesced loads), so keypoints come out in cv::FAST's row-major order
-//       without a sort or an append-atomic.
-// Algorithmic HBM bytes per image: W*H read + W*H score write/read + 12*N written.
+//       (quick reject -> arc test -> score).  NMS runs over the corner list as well (interior
+//       positions only, scores out of the LDS map) and sets the survivor's bit in a 32 x 64-bit
+//       occupancy mask; a survivor's place among its row's records is the popcount of the bits
+//       below it, so the order in which the LDS atomics land decides nothing.  The tile writes
+//       its records and one count byte per row to scratch only it owns: no global atomic, and
+//       nothing to zero beforehand.
+//   fast_emit_kernel  : one workgroup per 1024 consecutive (row, tile column) counts in raster
+//       order.  Its output offset is the sum of the counts before it (16-byte loads) plus a
+//       block scan of its own, then every thread gathers the records of its four counts, so
+//       keypoints come out in cv::FAST's row-major order without a sort or an append-atomic.
+// Algorithmic HBM bytes per image: W*H read + 12*N written (+ 2*N of records and W*H/64 of
+// counts written and read back).
 #include "svo_device.h"
 #include "svo_kernels.h"
+#include "fast_scratch.h"
 
 namespace svo {
 
-constexpr int kTileW = 64, kTileH = 16, kHalo = 4;
+constexpr int kTileW = kFastTileW, kTileH = kFastTileH, kHalo = 4;
 constexpr int kRawW = kTileW + 2 * kHalo;   // 72
-constexpr int kRawH = kTileH + 2 * kHalo;   // 24
+constexpr int kRawH = kTileH + 2 * kHalo;   // 40
 constexpr int kScW = kTileW + 2;            // 66
-constexpr int kScH = kTileH + 2;            // 18
+constexpr int kScH = kTileH + 2;            // 34
 
 // Bresenham circle, radius 3 (cv::FAST pattern 16), as byte offsets in the 72-wide LDS tile.
 __device__ __forceinline__ void load_circle(const uint8_t *c, int d[16], int v)
@@ -105,16 +112,18 @@ __global__ __launch_bounds__(256) void fast_score_kernel(FastArgs a)
     __shared__ __attribute__((aligned(16))) uint8_t raw[kRawH * kRawW];
     __shared__ __attribute__((aligned(4))) uint8_t sc[(kScH * kScW + 3) & ~3];
     __shared__ uint16_t cand[kScH * kScW], corners[kScH * kScW];
+    __shared__ unsigned long long occ[kTileH];             // bit x of word y: the tile's pixel (x, y) is a keypoint
     __shared__ int n_cand, n_corner;
     const int b = blockIdx.z;
     const uint8_t *img = a.img + (int64_t)b * a.img_stride;
-    uint8_t *score = a.score + (int64_t)b * a.score_stride;
-    int *rowcount = a.rowcount + (int64_t)b * a.rowcount_stride;
     const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
     const int tid = threadIdx.y * 64 + threadIdx.x;
     if (tid == 0) { n_cand = 0; n_corner = 0; }
+    if (tid < kTileH) occ[tid] = 0;
+    // a position of the score map that lies in the tile itself: the 1-pixel ring only serves as NMS neighbours
+    auto in_tile = [](int sy, int sx) { return sx >= 1 && sx <= kTileW && sy >= 1 && sy <= kTileH; };
 
-    // stage raw tile + halo (72 x 24 bytes); out-of-image bytes are never used by a valid centre.
+    // stage raw tile + halo (72 x 40 bytes); out-of-image bytes are never used by a valid centre.
     // x0 - 4 is a multiple of 4, so with a 4-byte aligned image the tile is 18 dwords per row.
     if ((((uintptr_t)img | (uintptr_t)a.pitch) & 3) == 0) {
         uint32_t *raw32 = (uint32_t *)raw;
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(256) void fast_score_kernel(FastArgs a)
         const int sy = pos / kScW, sx = pos - sy * kScW;
         const bool corner = i < nc && fast_arc(&raw[(sy + kHalo - 1) * kRawW + sx + kHalo - 1], a.thr);
         if (a.nms) list_push(corner, pos, corners, &n_corner);
-        else if (corner) sc[pos] = 1;
+        else if (corner && in_tile(sy, sx)) atomicOr(&occ[sy - 1], 1ull << (sx - 1));
     }
     __syncthreads();
     if (a.nms) {
@@ -216,58 +225,89 @@ __global__ __launch_bounds__(256) void fast_score_kernel(FastArgs a)
             sc[pos] = (uint8_t)fast_corner_score(&raw[(sy + kHalo - 1) * kRawW + sx + kHalo - 1], a.thr);
         }
         __syncthreads();
+        // strict 3x3 NMS, corners only: everything else in the map is 0, and a score of 0 (thr == 0) is no keypoint
+        for (int i = tid; i < nk; i += 256) {
+            const int pos = corners[i];
+            const int sy = pos / kScW, sx = pos - sy * kScW;
+            if (!in_tile(sy, sx)) continue;
+            const uint8_t *p = &sc[pos];
+            const int s = p[0];
+            if (s > p[-1] && s > p[1] && s > p[-kScW - 1] && s > p[-kScW] && s > p[-kScW + 1] &&
+                s > p[kScW - 1] && s > p[kScW] && s > p[kScW + 1])
+                atomicOr(&occ[sy - 1], 1ull << (sx - 1));
+        }
+        __syncthreads();
     }
 
+    // records: a keypoint's place in its row is the number of occupancy bits below its own.  The quick test only admits
+    // positions inside the image, so a set bit needs no bounds check; rows and columns past the image have none.
+    const int ntx = fast_tile_cols(a.w);
+    uint8_t *rec = a.score + (int64_t)b * a.score_stride + (int64_t)y0 * a.spitch + blockIdx.x * kTileW;
 #pragma unroll
     for (int j = 0; j < kTileH / 4; j++) {
-        int ly = threadIdx.y + 4 * j, lx = threadIdx.x;
-        int gx = x0 + lx, gy = y0 + ly;
-        const uint8_t *p = &sc[(ly + 1) * kScW + lx + 1];
-        int s = p[0];
-        if (a.nms && s) {
-            bool keep = s > p[-1] && s > p[1] && s > p[-kScW - 1] && s > p[-kScW] && s > p[-kScW + 1] &&
-                        s > p[kScW - 1] && s > p[kScW] && s > p[kScW + 1];
-            if (!keep) s = 0;
+        const int ly = threadIdx.y + 4 * j, lx = threadIdx.x;
+        const unsigned long long m = occ[ly];
+        if ((m >> lx) & 1ull) {
+            const int rank = __popcll(m & ((1ull << lx) - 1ull));
+            uint8_t *row = rec + (int64_t)ly * a.spitch;
+            if (a.nms) ((uint16_t *)row)[rank] = (uint16_t)(lx | (sc[(ly + 1) * kScW + lx + 1] << 8));
+            else row[rank] = (uint8_t)lx;
         }
-        bool inimg = gx < a.w && gy < a.h;
-        if (!inimg) s = 0;
-        unsigned long long m = __ballot(s != 0);
-        if (inimg) score[(int64_t)gy * a.spitch + gx] = (uint8_t)s;
-        if (threadIdx.x == 0 && m && gy < a.h) atomicAdd(&rowcount[gy], __popcll(m));
     }
+    uint8_t *cnt = (uint8_t *)(a.rowcount + (int64_t)b * a.rowcount_stride);
+    if (tid < kTileH && y0 + tid < a.h) cnt[(int64_t)(y0 + tid) * ntx + blockIdx.x] = (uint8_t)__popcll(occ[tid]);
 }
 
-// One wave per row: ordered emission of (x, y, response).
+// Ordered emission of (x, y, response): one workgroup per kEmitEntries consecutive count bytes, four per thread.
+constexpr int kEmitEntries = 4 * 256;
+
+__device__ __forceinline__ int byte_sum(uint32_t v, int acc) { return (int)__builtin_amdgcn_sad_u8(v, 0u, (uint32_t)acc); }
+
 __global__ __launch_bounds__(256) void fast_emit_kernel(FastArgs a)
 {
-    const int b = blockIdx.y;
-    const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (y >= a.h) return;
-    const uint8_t *score = a.score + (int64_t)b * a.score_stride + (int64_t)y * a.spitch;
-    const int *rowcount = a.rowcount + (int64_t)b * a.rowcount_stride;
-    int mine = rowcount[y];
-    bool last = (y == a.h - 1);
-    if (mine == 0 && !last) return;
-    // exclusive prefix over the rows above
-    int part = 0;
-    for (int r = lane; r < y; r += 64) part += rowcount[r];
-    int off = wave_sum_i32(part);
-    if (last && lane == 0) a.n_out[b] = off + mine;
+    __shared__ int wave_before[4], wave_mine[4];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int ntx = fast_tile_cols(a.w), total = ntx * a.h;
+    const uint8_t *cnt = (const uint8_t *)(a.rowcount + (int64_t)b * a.rowcount_stride);
+    const int e0 = blockIdx.x * kEmitEntries;
+    // keypoints before this workgroup's entries: e0 is a multiple of 16 and the counts of an image start 16-byte aligned
+    int before = 0;
+    for (int i = tid * 16; i < e0; i += 256 * 16) {
+        const uint4 v = *(const uint4 *)(cnt + i);
+        before = byte_sum(v.x, byte_sum(v.y, byte_sum(v.z, byte_sum(v.w, before))));
+    }
+    // this thread's four counts; the bytes past the image's last entry (inside the buffer's 16-byte rounding) are masked off
+    const int e = e0 + tid * 4;
+    uint32_t c4 = 0;
+    if (e < total) {
+        c4 = *(const uint32_t *)(cnt + e);
+        if (total - e < 4) c4 &= (1u << (8 * (total - e))) - 1u;
+    }
+    const int mine = byte_sum(c4, 0);
+    const int incl = wave_incl_scan(mine);
+    before = wave_sum_i32(before);
+    if (lane == 63) { wave_before[wv] = before; wave_mine[wv] = incl; }
+    __syncthreads();
+    int off = incl - mine, sum = 0;
+    for (int q = 0; q < 4; q++) {
+        off += wave_before[q] + (q < wv ? wave_mine[q] : 0);
+        sum += wave_before[q] + wave_mine[q];
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) a.n_out[b] = sum;
     if (mine == 0) return;
     float2 *xy = a.kp_xy + (int64_t)b * a.kp_stride;
     float *resp = a.kp_resp + (int64_t)b * a.kp_stride;
-    for (int x = lane; x < ((a.w + 63) & ~63); x += 64) {
-        int s = x < a.w ? score[x] : 0;
-        unsigned long long m = __ballot(s != 0);
-        if (s) {
-            int idx = off + __popcll(m & ((1ull << lane) - 1ull));
-            if (idx < a.cap) {
-                xy[idx] = make_float2((float)x, (float)y);
-                resp[idx] = a.nms ? (float)s : 0.f;
-            }
+    int y = e / ntx, tx = e - y * ntx;
+    for (int q = 0; q < 4; q++) {
+        const int c = (c4 >> (8 * q)) & 255u;
+        const uint8_t *row = a.score + (int64_t)b * a.score_stride + (int64_t)y * a.spitch + tx * kTileW;
+        for (int k = 0; k < c && off + k < a.cap; k++) {
+            const int r = a.nms ? ((const uint16_t *)row)[k] : row[k];
+            xy[off + k] = make_float2((float)(tx * kTileW + (r & 255)), (float)y);
+            resp[off + k] = (float)(r >> 8);              // 0.f without NMS: the record is the x byte alone
         }
-        off += __popcll(m);
+        off += c;
+        if (++tx == ntx) { tx = 0; y++; }
     }
 }
 
@@ -499,10 +539,9 @@ void launch_bucket_pack(const float2 *xy, const float *resp, const int *n_dev, i
 
 void launch_fast(const FastArgs &a, int batch, hipStream_t st)
 {
-    (void)hipMemsetAsync(a.rowcount, 0, sizeof(int) * (size_t)a.rowcount_stride * batch, st);
-    dim3 g1((a.w + kTileW - 1) / kTileW, (a.h + kTileH - 1) / kTileH, batch), b1(64, 4, 1);
+    dim3 g1(fast_tile_cols(a.w), (a.h + kTileH - 1) / kTileH, batch), b1(64, 4, 1);
     hipLaunchKernelGGL(fast_score_kernel, g1, b1, 0, st, a);
-    dim3 g2((a.h + 3) / 4, batch, 1), b2(256, 1, 1);
+    dim3 g2((fast_tile_cols(a.w) * a.h + kEmitEntries - 1) / kEmitEntries, batch, 1), b2(256, 1, 1);
     hipLaunchKernelGGL(fast_emit_kernel, g2, b2, 0, st, a);
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 #include "abi_io.h"
 #include "carry.h"
+#include "fast_scratch.h"
 
 using namespace svo;
 
@@ -240,10 +241,11 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
     ctx->slot_built.assign(cfg->num_slots, 0);
     ctx->stage_pitch = align_up(w, 256);
     DA(ctx->stage_img, (size_t)ctx->stage_pitch * h * 2);
-    ctx->spitch = align_up(w, 64);
+    // FAST scratch: corner records and per-(row, tile column) counts, sized by the bounds in fast_scratch.h
+    ctx->spitch = fast_record_pitch(w);
     ctx->score_stride = (int64_t)ctx->spitch * h;
     DA(ctx->score, (size_t)ctx->score_stride * n_fast);
-    ctx->rowcount_stride = align_up(h, 64);
+    ctx->rowcount_stride = fast_count_words(w, h);
     DA(ctx->rowcount, sizeof(int) * (size_t)ctx->rowcount_stride * n_fast);
     DA(ctx->kp_xy, sizeof(float2) * (size_t)cap * n_fast);
     DA(ctx->kp_resp, sizeof(float) * (size_t)cap * n_fast);

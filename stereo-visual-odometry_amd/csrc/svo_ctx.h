@@ -107,7 +107,7 @@ struct svo_ctx {
     uint8_t *h_stage = nullptr;       // pinned mirror of stage_img: rows gathered on the host, one H2D copy per image
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
     bool h_stage_busy[2] = {false, false};
-    // ---- FAST scratch + outputs, n_img images
+    // ---- FAST scratch (corner records and their counts, fast_scratch.h) + outputs, n_img images
     uint8_t *score = nullptr; int spitch = 0; int64_t score_stride = 0;
     int *rowcount = nullptr; int64_t rowcount_stride = 0;
     float2 *kp_xy = nullptr; float *kp_resp = nullptr; int *kp_n = nullptr;
