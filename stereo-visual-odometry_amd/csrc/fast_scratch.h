@@ -8,6 +8,8 @@
 //                 kFastTileW / 2 of them: 2 * kFastTileW / 2 bytes, the region exactly;
 //       no nms  : 1 byte per corner (x - tx * kFastTileW; the response is 0), at most tw <= kFastTileW corners.
 //     Both bounds hold for any image content and for partial tiles (the pitch covers whole tiles), so nothing is ever cut.
+//     tests/test_gpu_fast_bounds.py::test_saturated_records pins both: tile rows of 32 survivors and of 64 corners, the last
+//     record at rank 31 / 63, beside live records of the next tile column (inputs: tests/_fast_cases.py staircase_rows).
 // FastArgs.rowcount : the COUNTS, one byte per (image row, tile column) in raster order -- byte y * tile_cols + tx, at most
 //     kFastTileW <= 255 -- rounded up to whole 16-byte groups per image, fast_count_words(w, h) ints.
 // Every byte the emit kernel reads is written by the tile that owns it in the same launch: nothing is zeroed beforehand.

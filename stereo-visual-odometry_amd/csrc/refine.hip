@@ -275,7 +275,12 @@ int refine_alloc(svo_ctx *ctx)
     uint8_t *p = nullptr;
     if (dev_alloc(ctx, &p, bytes) != SVO_OK) return SVO_ERR_HIP;
     // (a block that could not be cleared is not used: it stays the context's, to be freed with it)
-    if (hipMemset(p, 0, bytes) != hipSuccess) { ctx->err = "hipMemset of the refinement block failed"; return SVO_ERR_HIP; }
+    // Cleared ON THE CONTEXT'S STREAM and waited for: hipMemset runs on the null stream and may return before the fill has run,
+    // and the context's streams are non-blocking, so a stage call's first input copy into this block could be overtaken by it.
+    if (hipMemsetAsync(p, 0, bytes, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        ctx->err = "hipMemset of the refinement block failed";
+        return SVO_ERR_HIP;
+    }
     ctx->refine_buf = p;
     return SVO_OK;
 }
