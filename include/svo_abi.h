@@ -791,6 +791,135 @@ int svo_get_last_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages, int cap, i
 int svo_streams_get_track_ids(svo_ctx *ctx, int item, int64_t *ids, int32_t *ages, int cap, int *n_out);
 int svo_streams_get_frame_tracks(svo_ctx *ctx, int stream_id, svo_keypoint *kps, int64_t *ids, int32_t *ages, int cap, int *n_out);
 
+/* ---- Sliding window: the landmark table over carried tracks (additive; detected by symbol, the ABI version stays 9 and
+ * svo_config is unchanged) ------------------------------------------------------------------------------------------------
+ * Track carry gives one physical point one id over many frames.  The table below is the store a fixed-lag back end needs on
+ * top of that: the last W <= SVO_WINDOW_MAX_FRAMES frames of a chain and, per id, one world point with the stereo observation
+ * of every frame of the window that saw it.  svo_window_update is the stage call that moves a table on by one tracked pair;
+ * nothing in a context's fused steps uses it yet.
+ *
+ * A table (svo_window_table) is `cap` rows of room plus
+ *   counts    int32[4]: n frames (0..W; slot 0 oldest, slot n-1 newest), m rows, the rows the last update needed, 0
+ *   poses     double[SVO_WINDOW_MAX_FRAMES][12]: per slot the camera-from-world pose, R row-major then t (Y = R X + t);
+ *             slots >= n are 0
+ *   ids       int64[m], strictly ascending            X       double[m][3], world
+ *   seen      uint32[m], bit s = slot s has an observation of the row
+ *   active    uint32[m], bit s = the back end's last verdict on that observation (the update only moves it; new observations
+ *             enter with the bit clear)
+ *   obs_left / obs_right   svo_pt2f[m][SVO_WINDOW_MAX_FRAMES]; columns without a seen bit are 0
+ * Rules (the numpy twin is tests/_window_ref.py; the kernel equals it bit for bit in counts, ids, masks and observations, and
+ * to 1e-12 relative in poses and X).  One call = one step with ok = 1 on pair a -> b; pose_a is the chain pose before the step
+ * (frame a, world from camera, 4 x 4 row-major as svo_get_pose returns it), pose_b the step record's pose.
+ *   T1 a cleared table is n = m = 0.  The caller clears: on a chain's first frame, after a failed step, a reset or a re-seeded pose.
+ *   T2 n = 0: slot 0 becomes frame a with pose inverse(pose_a); rows of the input are ignored.
+ *   T3 n = W: slide -- slot 0 leaves; seen, active and the observation columns move down by one (the top column is 0); rows
+ *      whose seen is now 0 leave, the others keep their order.
+ *   T4 frame b becomes the newest slot with pose inverse(pose_b).  inverse(T): R = Rw^T, t_i = -((R_i0 tw_0 + R_i1 tw_1) +
+ *      R_i2 tw_2), in double.
+ *   T5 for every track of the pair -- in the order svo_get_last_tracks lists them, which by rule C5 is ascending id -- that is
+ *      usable (t1_left, t1_right, t2_left, t2_right and the float32 triangulated point all finite): the newest slot gets
+ *      (t2_left, t2_right); the slot before it gets (t1_left, t1_right) unless its seen bit is already set; an id without a
+ *      row creates one with X_j = (Ra_0j d_0 + Ra_1j d_1) + Ra_2j d_2, d = (double)X_tri - ta, (Ra, ta) = slot a's pose.
+ *   T6 the result is the merge of the two id-sorted lists: a usable track whose row was never made (its triangulation was not
+ *      finite earlier) or has left enters at its id's place.
+ *   T7 the update needs (surviving rows + new rows) <= cap.  A chain whose pairs have at most K tracks never needs more than
+ *      (W - 1) x K.  When cap is too small NOTHING of `out` is written but counts = {0, 0, rows needed, 0} -- a cleared table.
+ *   svo_window_update: independent of the context's size and mode.  `frames` = W, 2..SVO_WINDOW_MAX_FRAMES.  `in` and `out`
+ *       both have `cap` rows of room and must not overlap; `in` is not written.  ids must be strictly ascending (unspecified
+ *       rows, but no access outside the arrays, otherwise).  `mem` says where every array, both poses and the counts live
+ *       (the two svo_window_table structs themselves are host memory).  SVO_MEM_DEVICE: one launch in stream order on the
+ *       context's stream, no host synchronisation (scratch grows on demand; a call that grows it waits for the device); a
+ *       short cap shows in out->counts[2] > cap.  SVO_MEM_HOST: returns when `out` is complete; SVO_ERR_ARG when cap was too
+ *       small (out->counts is set as above).  SVO_ERR_ARG also: frames out of range, cap < 1 or > 2^21, n_trk < 0 or > 2^20,
+ *       a null pointer, and (HOST) input counts outside 0..frames / 0..cap.
+ *
+ * The optimiser over a table: a sliding-window stereo bundle adjustment, the two-frame SVO_REFINE_BA generalised to n <= 8
+ * frames.  All arithmetic in double; R1-R7 are the rules of the refinement stage above; the numpy twin is solve() of
+ * tests/_window_ref.py (the kernel agrees with it in status, masks and counts, and to 1e-9 in poses, X and info).
+ *   W1 slot 0 is fixed (the gauge; stereo fixes the scale).  Unknowns: xi_f for slots 1..n-1 (R2's update on the slot's
+ *      camera-from-world pose) and X_i per usable landmark.
+ *   W2 observation (i, f) -- a seen bit -- has d = 4 residuals: view L [K1 | 0] and view R the full P2 of Y = R_f X_i + t_f, as
+ *      R1 and R3 (K1 = fx, fy, cx, cy of P1).  It is projectable when h2 > 1e-6 in both views.  c = |r|^2 / sigma^2, tau = 9.488
+ *      (the chi-square 95 % point for 4 degrees of freedom: the share of the landmark's three is spread over its observations
+ *      and is not subtracted).
+ *   W3 a landmark is usable in a round when >= 2 of its observations are active; otherwise it has no active observation, weighs
+ *      nothing and is not moved.
+ *   W4 rounds are R5's, per observation: rounds 0 and 1 Huber (w = 1 if c <= tau else sqrt(tau / c)), later rounds plain; the
+ *      first round starts from all projectable seen observations; after each round every projectable seen observation is
+ *      re-classified (active iff c <= tau, re-admission allowed); a landmark that falls below two active observations returns
+ *      to the X it had at entry.
+ *   W5 one LM iteration.  Per usable landmark over its active observations, weighted by w / sigma^2: V = sum J_x^T J_x, g_x,
+ *      V* = V + lambda diag V = L L^T (3 x 3 Cholesky; a pivot <= 0: the landmark contributes U and g_p only and is not moved);
+ *      per slot f >= 1: W_if = J_p^T J_x, U_f += J_p^T J_p, g_pf += J_p^T r, T_if = W_if L^-T, y_i = L^-1 g_x.  Reduced system
+ *      of dimension 6 (n - 1) <= 42: H_ff' = delta_ff' sum U_f - sum_i T_if T_if'^T, g_f = sum (g_pf - T_if y_i);
+ *      (H + lambda diag sum U) xi = -g by Cholesky, every pivot > 0; dX_i = -L^-T (y_i + sum_f T_if^T xi_f).  Slot 0's
+ *      observations enter V and g_x only.
+ *   W6 accept / reject as R6: the cost a (sum, remainder) pair; no active observation may become non-projectable; all poses and
+ *      points are accepted or rejected together; lambda 1e-4 at the start of a round, / 10 (floor 1e-12) on accept, x 10 on
+ *      reject or a failed factorisation, the round ends past 1e10; short-step exit |xi| < 1e-10 (the whole vector) and
+ *      max |dX_i| < 1e-9.  A rejected step counts as an iteration.
+ *   W7 after the last re-classification info = the reduced H at lambda = 0 over the active set at the final estimate.
+ *      SVO_REFINE_APPLIED iff every slot 1..n-1 has >= min_obs active observations, info factors and everything (poses, points,
+ *      info, cost_first, cost_last) is finite: then the table's poses, X and active are overwritten.  SVO_REFINE_KEPT_PNP
+ *      otherwise: the table is left as it was, bit for bit.  SVO_REFINE_SKIPPED when n < 2.
+ *   W8 the same input gives the same bytes on every run: sums run in a fixed order, there are no floating-point atomics.
+ *   svo_window_result: status; n_frames, n_landmarks (rows); n_usable, n_active (landmarks / observations active after the last
+ *      re-classification), n_obs (seen bits); iters (LM iterations run, rejected ones included); frame_active[8] per slot;
+ *      cost_first / cost_last as svo_refine_result; info row-major 42 x 42, the leading 6 (n - 1) square in the order of xi
+ *      (slot 1 first, translation first), the rest 0 -- also when the table is kept.
+ *   svo_window_ba (stage API): window_ba_kernel on a caller's table, independent of the context's size and mode.  The table has
+ *      `cap` rows of room (counts[1] <= cap); ids is not read.  P1, P2 are HOST pointers; rounds, iters, sigma_px keep
+ *      svo_set_pose_refine's ranges, min_obs >= 1 (SVO_ERR_ARG otherwise).  `mem` says where the table's arrays, its counts
+ *      and *res live.  SVO_MEM_DEVICE: one launch in stream order on the context's stream, the table updated in place, no host
+ *      synchronisation (scratch -- 1140 bytes a row -- grows on demand; a call that grows it waits for the device).
+ *      SVO_MEM_HOST: returns when *res and the table's poses, X and active are complete.
+ *   svo_set_window_ba : LK mode, the online chain (svo_add_frame / svo_ingest_add_frame) with track carry on.  frames = 0 (the
+ *      default) switches it off -- the other arguments are ignored and every step runs exactly the launches it ran before this
+ *      option existed; frames 2..8 = W.  While on, every step with a previous frame runs window_update_kernel and
+ *      window_ba_kernel after the gates and the pose chain, on the step's stream, before the record is delivered (timing marks
+ *      win_update, win_ba); no host synchronisation is added.  The table is cleared (T1) by a chain's first frame, by a step
+ *      whose record has ok = 0 (on the device), by svo_reset, svo_set_pose, svo_set_window_ba and svo_set_track_carry.  The
+ *      pair's tracks are those of svo_get_last_tracks, their ids those of svo_get_last_track_ids, the triangulation the pose
+ *      stage's.  SVO_REFINE_APPLIED: the step record's pose, and with it frame_pose_ (svo_get_pose), become inverse(newest
+ *      slot); T_rel_inv, rvec, tvec, R, the counts and every track stay the pair's.  Otherwise the record is untouched.
+ *      SVO_ERR_ARG (nothing changes): an ORB-mode context, frames not 0 or 2..8, rounds / iters / sigma_px outside
+ *      svo_set_pose_refine's ranges, min_obs < 1.  SVO_ERR_STATE: track carry is off.  While it is on, svo_set_track_carry(off),
+ *      svo_streams_step and svo_ingest_streams_step return SVO_ERR_STATE (stream sets have no table yet).  Memory: the first
+ *      enabling call (and a later one with a larger W) allocates ONE block for (W - 1) x max_keypoints rows -- 2 tables of 168
+ *      bytes a row and 1140 bytes a row of scratch -- and waits for the device; a context that never enables it allocates
+ *      nothing.
+ *   svo_get_window_ba : what is set (all 0 while off).  Any pointer may be NULL.
+ *   svo_get_window : the online chain's table after the last svo_add_frame step, into HOST arrays with `cap` rows of room
+ *      (counts first; every other pointer NULL: the counts only; SVO_ERR_ARG when counts[1] > cap).
+ *   svo_get_window_result : that step's svo_window_result (SKIPPED after a failed step or with fewer than two frames).  Both
+ *      return SVO_ERR_ARG when the window was off for the last step or no pair has been tracked.
+ *   Host mirror: YAML window_ba: W with window_ba_rounds / _iters / _sigma / _min_obs. */
+#define SVO_WINDOW_MAX_FRAMES 8
+typedef struct {
+    int32_t  *counts;
+    double   *poses;
+    int64_t  *ids;
+    double   *X;
+    uint32_t *seen, *active;
+    svo_pt2f *obs_left, *obs_right;
+} svo_window_table;
+int svo_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, const svo_window_table *out, int cap,
+                      const svo_pt2f *t1_left, const svo_pt2f *t1_right, const svo_pt2f *t2_left, const svo_pt2f *t2_right,
+                      const int64_t *ids, const svo_pt3f *tri, int n_trk, const double pose_a[16], const double pose_b[16], int mem);
+
+typedef struct {
+    int32_t status, n_frames, n_landmarks, n_usable, n_obs, n_active, iters, _pad;
+    int32_t frame_active[SVO_WINDOW_MAX_FRAMES];
+    double cost_first, cost_last;
+    double info[42 * 42];
+} svo_window_result;
+int svo_set_window_ba(svo_ctx *ctx, int frames, int rounds, int iters, double sigma_px, int min_obs);
+int svo_get_window_ba(const svo_ctx *ctx, int *frames, int *rounds, int *iters, double *sigma_px, int *min_obs);
+int svo_get_window(svo_ctx *ctx, const svo_window_table *out, int cap);
+int svo_get_window_result(svo_ctx *ctx, svo_window_result *res);
+int svo_window_ba(svo_ctx *ctx, const svo_window_table *table, int cap, const double P1[12], const double P2[12], int rounds, int iters,
+                  double sigma_px, int min_obs, svo_window_result *res, int mem);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

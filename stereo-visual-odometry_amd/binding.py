@@ -73,6 +73,27 @@ STEP_DTYPE = np.dtype([("ok", "<i4"), ("fail_stage", "<i4"), ("n_prev_kps", "<i4
 assert STEP_DTYPE.itemsize == C.sizeof(StepResult)
 
 
+WINDOW_MAX_FRAMES = 8
+_WINDOW_COLS = ("counts", "poses", "ids", "X", "seen", "active", "obs_left", "obs_right")
+
+
+class WindowTable(C.Structure):
+    """svo_window_table: the columns of a sliding-window landmark table as raw pointers."""
+    _fields_ = [(k, C.c_void_p) for k in _WINDOW_COLS]
+
+
+class WindowResult(C.Structure):
+    """svo_window_result: the outcome of svo_window_ba."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "n_frames", "n_landmarks", "n_usable", "n_obs", "n_active", "iters", "_pad")] + [
+        ("frame_active", C.c_int32 * WINDOW_MAX_FRAMES), ("cost_first", C.c_double), ("cost_last", C.c_double), ("info", C.c_double * (42 * 42))]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("status", "n_frames", "n_landmarks", "n_usable", "n_obs", "n_active", "iters", "cost_first", "cost_last")}
+        d["frame_active"] = np.array(self.frame_active, np.int32)
+        d["info"] = np.array(self.info, np.float64).reshape(42, 42)
+        return d
+
+
 def library_path():
     return os.path.join(_HERE, "libsvo_hip.so")
 
@@ -184,6 +205,15 @@ def load_library():
     lib.svo_get_last_track_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.svo_streams_get_track_ids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.svo_streams_get_frame_tracks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_set_window_ba.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
+    lib.svo_get_window_ba.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int)]
+    lib.svo_get_window.argtypes = [C.c_void_p, C.POINTER(WindowTable), C.c_int]
+    lib.svo_get_window_result.argtypes = [C.c_void_p, C.c_void_p]
+    lib.svo_window_ba.argtypes = [C.c_void_p, C.POINTER(WindowTable), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int,
+                                  C.c_void_p, C.c_int]
+    lib.svo_window_update.argtypes = ([C.c_void_p, C.c_int, C.POINTER(WindowTable), C.POINTER(WindowTable), C.c_int] + [C.c_void_p] * 6 +
+                                      [C.c_int, C.c_void_p, C.c_void_p, C.c_int])
     _LIB = lib
     return lib
 
@@ -782,6 +812,139 @@ class Context:
             self._order_out(n_car)
         out["n_out"], out["n_carried"] = n_out, n_car
         return out
+
+    # ---- sliding window: the landmark table over carried tracks (svo_window_update) -----------------
+    def window_update(self, table, frames, t1_left, t1_right, t2_left, t2_right, ids, tri, pose_a, pose_b, cap=None):
+        """svo_window_update: one tracked pair a -> b moves a landmark table on.  table: None (a cleared table) or a dict as
+        this method returns it; frames: the window length W; the four track lists, ids (ascending) and tri (the float32
+        triangulation in frame a) of the pair; pose_a / pose_b: the 4 x 4 chain pose before the step and the step's.  numpy
+        inputs: returns dict(n, m, poses (8, 12), ids, X, seen, active, obs_left (m, 8, 2), obs_right), m rows each; raises
+        SvoError when the result needs more than `cap` rows (default: rows in + tracks).  torch cuda inputs: the table carries
+        `counts` (int32[4]: n, m, rows needed, 0) in place of n and m, every column has `cap` rows, and everything is
+        filled in stream order without a host synchronisation."""
+        host = isinstance(t1_left, np.ndarray)
+        F = WINDOW_MAX_FRAMES
+        if host:
+            conv = lambda a, dt, shape: np.ascontiguousarray(a, dt).reshape(shape)
+            new = lambda shape, dt: np.zeros(shape, dt)
+            f32, f64, i64, i32, u32 = np.float32, np.float64, np.int64, np.int32, np.uint32
+            ptr = lambda a: a.ctypes.data
+        else:
+            import torch
+            dev = t1_left.device
+            conv = lambda a, dt, shape: a.to(dt).contiguous().reshape(shape)
+            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            f32, f64, i64, i32, u32 = torch.float32, torch.float64, torch.int64, torch.int32, torch.int32   # masks travel as int32 bits
+            ptr = lambda a: a.data_ptr()
+        obs = [conv(a, f32, (-1, 2)) for a in (t1_left, t1_right, t2_left, t2_right)]
+        tid, tx = conv(ids, i64, (-1,)), conv(tri, f32, (-1, 3))
+        n_trk = int(tid.shape[0])
+        assert all(int(o.shape[0]) == n_trk for o in obs) and int(tx.shape[0]) == n_trk
+        pa, pb = conv(pose_a, f64, (16,)), conv(pose_b, f64, (16,))
+        shapes = {"poses": ((F, 12), f64), "ids": ((-1,), i64), "X": ((-1, 3), f64), "seen": ((-1,), u32), "active": ((-1,), u32),
+                  "obs_left": ((-1, F, 2), f32), "obs_right": ((-1, F, 2), f32)}
+        if table is None:
+            m_in = 0
+            tin = {k: new(tuple(1 if d < 0 else d for d in sh), dt) for k, (sh, dt) in shapes.items()}
+            tin["counts"] = new((4,), i32)
+        else:
+            tin = {k: conv(table[k], dt, sh) for k, (sh, dt) in shapes.items()}
+            if host:
+                m_in = int(table["m"])
+                tin["counts"] = np.array([int(table["n"]), m_in, 0, 0], np.int32)
+            else:
+                m_in = int(tin["ids"].shape[0])
+                tin["counts"] = conv(table["counts"], i32, (4,))
+        cap = m_in + n_trk if cap is None else int(cap)
+        rows = max(cap, 1)
+        if int(tin["ids"].shape[0]) < rows:                       # both tables have `cap` rows of room
+            grown = {k: new((rows,) + tuple(tin[k].shape[1:]), dt) for k, (sh, dt) in shapes.items() if k != "poses"}
+            for k, g in grown.items():
+                g[:tin[k].shape[0]] = tin[k]
+            tin.update(grown)
+        out = {k: new((F, 12) if k == "poses" else (rows,) + tuple(tin[k].shape[1:]), dt) for k, (sh, dt) in shapes.items()}
+        out["counts"] = new((4,), i32)
+        ti, to = (WindowTable(*[ptr(t[k]) for k in _WINDOW_COLS]) for t in (tin, out))
+        if not host:
+            ordered = self._order_in(out["counts"])
+        rc = self.lib.svo_window_update(self.h, int(frames), C.byref(ti), C.byref(to), cap, *[ptr(o) for o in obs], ptr(tid), ptr(tx),
+                                        n_trk, ptr(pa), ptr(pb), MEM_HOST if host else MEM_DEVICE)
+        self._check(rc)
+        if not host:
+            if ordered:
+                self._order_out(out["counts"])
+            return out
+        m = int(out["counts"][1])
+        res = {k: (v if k == "poses" else v[:m].copy()) for k, v in out.items() if k != "counts"}
+        res["n"], res["m"] = int(out["counts"][0]), m
+        return res
+
+    def set_window_ba(self, frames=5, rounds=4, iters=5, sigma_px=1.0, min_obs=10):
+        """LK mode, add_frame / ingest_add_frame with track carry on: keep a landmark table over the last `frames` frames of the
+        chain and adjust its poses and points together after every step (svo_set_window_ba); frames = 0 switches it off."""
+        self._check(self.lib.svo_set_window_ba(self.h, int(frames), int(rounds), int(iters), float(sigma_px), int(min_obs)))
+
+    def window_ba(self):
+        """(frames, rounds, iters, sigma_px, min_obs) as set; all 0 while off."""
+        f, r, i, s, m = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0), C.c_int(0)
+        self._check(self.lib.svo_get_window_ba(self.h, C.byref(f), C.byref(r), C.byref(i), C.byref(s), C.byref(m)))
+        return f.value, r.value, i.value, s.value, m.value
+
+    def window(self):
+        """The online chain's landmark table after the last add_frame step: a dict as window_update returns it (numpy)."""
+        F = WINDOW_MAX_FRAMES
+        counts = np.zeros(4, np.int32)
+        self._check(self.lib.svo_get_window(self.h, C.byref(WindowTable(counts.ctypes.data, *([None] * 7))), 0))
+        m, rows = int(counts[1]), max(int(counts[1]), 1)
+        t = {"counts": counts, "poses": np.zeros((F, 12)), "ids": np.zeros(rows, np.int64), "X": np.zeros((rows, 3)),
+             "seen": np.zeros(rows, np.uint32), "active": np.zeros(rows, np.uint32), "obs_left": np.zeros((rows, F, 2), np.float32),
+             "obs_right": np.zeros((rows, F, 2), np.float32)}
+        self._check(self.lib.svo_get_window(self.h, C.byref(WindowTable(*[t[k].ctypes.data for k in _WINDOW_COLS])), rows))
+        res = {k: (v if k == "poses" else v[:m].copy()) for k, v in t.items() if k != "counts"}
+        res["n"], res["m"] = int(counts[0]), m
+        return res
+
+    def window_result(self):
+        """The last add_frame step's optimiser outcome (svo_get_window_result) as a dict."""
+        res = WindowResult()
+        self._check(self.lib.svo_get_window_result(self.h, C.addressof(res)))
+        return res.as_dict()
+
+    def window_solve(self, table, P1, P2, rounds=4, iters=5, sigma_px=1.0, min_obs=10):
+        """svo_window_ba: the sliding-window bundle adjustment on a landmark table (a dict as window_update returns it).  numpy:
+        returns (result dict -- status, counts, frame_active (8), cost_first / cost_last, info (42, 42) -- and the table as it
+        stands afterwards: poses, X and active replaced when status is REFINE_APPLIED, the input otherwise; the input dict is not
+        modified).  torch cuda: the table's poses / X / active tensors are overwritten IN PLACE in stream order and the result
+        comes back as a uint8 tensor holding a WindowResult (WindowResult.from_buffer_copy after a synchronisation)."""
+        host = isinstance(table["X"], np.ndarray)
+        F = WINDOW_MAX_FRAMES
+        P1c, P2c = np.ascontiguousarray(P1, np.float64).reshape(12), np.ascontiguousarray(P2, np.float64).reshape(12)
+        if host:
+            m = int(table["m"])
+            t = {"counts": np.array([int(table["n"]), m, 0, 0], np.int32), "poses": np.array(table["poses"], np.float64).reshape(F, 12),
+                 "ids": np.ascontiguousarray(table["ids"][:m], np.int64), "X": np.array(table["X"][:m], np.float64).reshape(-1, 3),
+                 "seen": np.ascontiguousarray(table["seen"][:m], np.uint32), "active": np.array(table["active"][:m], np.uint32),
+                 "obs_left": np.ascontiguousarray(table["obs_left"][:m], np.float32).reshape(-1, F, 2),
+                 "obs_right": np.ascontiguousarray(table["obs_right"][:m], np.float32).reshape(-1, F, 2)}
+            if m == 0:
+                t.update({k: np.zeros((1,) + t[k].shape[1:], t[k].dtype) for k in _WINDOW_COLS[2:]})
+            tt = WindowTable(*[t[k].ctypes.data for k in _WINDOW_COLS])
+            res = WindowResult()
+            self._check(self.lib.svo_window_ba(self.h, C.byref(tt), max(m, 1), P1c.ctypes.data, P2c.ctypes.data, int(rounds), int(iters),
+                                               float(sigma_px), int(min_obs), C.addressof(res), MEM_HOST))
+            out = dict(table, poses=t["poses"], X=t["X"][:m], active=t["active"][:m])
+            return res.as_dict(), out
+        import torch
+        for k in _WINDOW_COLS:
+            assert table[k].is_cuda and table[k].is_contiguous(), k
+        res = torch.zeros(C.sizeof(WindowResult), dtype=torch.uint8, device=table["X"].device)
+        ordered = self._order_in(res)
+        tt = WindowTable(*[table[k].data_ptr() for k in _WINDOW_COLS])
+        self._check(self.lib.svo_window_ba(self.h, C.byref(tt), int(table["ids"].shape[0]), P1c.ctypes.data, P2c.ctypes.data, int(rounds),
+                                           int(iters), float(sigma_px), int(min_obs), res.data_ptr(), MEM_DEVICE))
+        if ordered:
+            self._order_out(res)
+        return res, table
 
     def _ids(self, fn, *head, cap=65536):
         ids, ages, n = np.zeros(cap, np.int64), np.zeros(cap, np.int32), C.c_int(0)

@@ -144,7 +144,7 @@ __device__ inline bool refine_chol6(const double (&A)[36], const double (&b)[6],
 
 // ---- the stage's device block: [records x (B + 1)][flags x (B + 1) x cap][stage-call X, xl, xr x cap]; item B is the stage call's
 struct RefineCut { size_t flags, X, xl, xr, end; };
-static RefineCut refine_cut(const svo_config &c)
+inline RefineCut refine_cut(const svo_config &c)
 {
     const size_t items = (size_t)c.max_batch + 1, cap = (size_t)c.max_keypoints;
     BlockCut cut;

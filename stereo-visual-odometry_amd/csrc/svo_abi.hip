@@ -737,6 +737,7 @@ extern "C" int svo_reset(svo_ctx *ctx)
     if (!ctx) return SVO_ERR_ARG;
     ctx->online_frames = 0; ctx->online_cur = 0;
     ctx->carry_restart = true;                   // svo_set_track_carry: the next chain's ids start at 0
+    ctx->win_clear = true;                       // svo_set_window_ba, T1
     for (int i = 0; i < 16; i++) ctx->pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
     return SVO_OK;
 }
@@ -752,6 +753,7 @@ extern "C" int svo_set_pose(svo_ctx *ctx, const double pose[16])
 {
     if (!ctx || !pose) return SVO_ERR_ARG;
     memcpy(ctx->pose, pose, sizeof(double) * 16);
+    ctx->win_clear = true;                       // svo_set_window_ba, T1: the window's poses belong to the chain that was
     return SVO_OK;
 }
 
@@ -1124,6 +1126,7 @@ extern "C" int svo_streams_count(const svo_ctx *ctx, int *n_streams)
 static int streams_step(svo_ctx *ctx, int w, int h, bool resize, const int32_t *stream_ids, int m, const uint8_t *lefts,
                         const uint8_t *rights, int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
 {
+    if (ctx->win_frames > 0) { ctx->err = "the sliding window (svo_set_window_ba) works on the online chain only: stream sets have no table yet"; return SVO_ERR_STATE; }
     SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
     SVO_ARG(stream_ids && lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
     SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
@@ -1689,12 +1692,14 @@ static bool carry_params_ok(double min_distance, int max_age)
 extern "C" int svo_set_track_carry(svo_ctx *ctx, int on, double min_distance, int max_age)
 {
     if (!ctx) return SVO_ERR_ARG;
+    if (!on && ctx->win_frames > 0) { ctx->err = "the sliding window is on and needs track carry (svo_set_window_ba(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
     if (!on) { ctx->carry_on = false; return SVO_OK; }               // off: the other arguments are ignored
     SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "track carry is an LK-mode option (ORB mode matches descriptors frame to frame)");
     SVO_ARG(carry_params_ok(min_distance, max_age), "min_distance must be finite and in [1, 256], max_age >= 0");
     SVO_HIP(hipSetDevice(ctx->device));
     SVO_TRY(carry_alloc(ctx));                                       // first enabling call: the working frames' and an existing stream set's share
     ctx->carry_on = true; ctx->carry_min_distance = min_distance; ctx->carry_max_age = max_age;
+    ctx->win_clear = true;                                           // svo_set_window_ba, T1
     return SVO_OK;
 }
 
@@ -1767,6 +1772,71 @@ extern "C" int svo_carry_merge(svo_ctx *ctx, int width, int height, double min_d
     SVO_TRY(from_device(ctx, (int *)out_age, (const int *)a.o_age, n, mem));
     SVO_TRY(from_device(ctx, (int *)out_src, (const int *)a.o_src, n, mem));
     return io_done(ctx, mem);
+}
+
+// ---- sliding window: the landmark table's update on a caller's tables (window.hip: window_update_kernel) --------------------
+extern "C" int svo_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, const svo_window_table *out, int cap,
+                                 const svo_pt2f *t1_left, const svo_pt2f *t1_right, const svo_pt2f *t2_left, const svo_pt2f *t2_right,
+                                 const int64_t *ids, const svo_pt3f *tri, int n_trk, const double pose_a[16], const double pose_b[16], int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return stage_window_update(ctx, frames, in, out, cap, t1_left, t1_right, t2_left, t2_right, ids, tri, n_trk, pose_a, pose_b, mem);
+}
+
+extern "C" int svo_set_window_ba(svo_ctx *ctx, int frames, int rounds, int iters, double sigma_px, int min_obs)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (frames == 0) { ctx->win_frames = 0; ctx->win_clear = true; return SVO_OK; }      // off: the other arguments are ignored
+    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "the sliding window is an LK-mode option");
+    SVO_ARG(frames >= 2 && frames <= SVO_WINDOW_MAX_FRAMES, "frames must be 0 or 2..SVO_WINDOW_MAX_FRAMES");
+    SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
+    SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
+    SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
+    SVO_ARG(min_obs >= 1, "min_obs < 1");
+    if (!ctx->carry_on) { ctx->err = "the sliding window needs track carry (svo_set_track_carry) on"; return SVO_ERR_STATE; }
+    SVO_TRY(window_alloc(ctx, frames));
+    ctx->win_frames = frames; ctx->win_rounds = rounds; ctx->win_iters = iters; ctx->win_sigma = sigma_px; ctx->win_min_obs = min_obs;
+    ctx->win_clear = true;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_window_ba(const svo_ctx *ctx, int *frames, int *rounds, int *iters, double *sigma_px, int *min_obs)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    const bool on = ctx->win_frames > 0;
+    if (frames) *frames = ctx->win_frames;
+    if (rounds) *rounds = on ? ctx->win_rounds : 0;
+    if (iters) *iters = on ? ctx->win_iters : 0;
+    if (sigma_px) *sigma_px = on ? ctx->win_sigma : 0.0;
+    if (min_obs) *min_obs = on ? ctx->win_min_obs : 0;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_window(svo_ctx *ctx, const svo_window_table *out, int cap)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(out && out->counts && cap >= 0, "null table / counts");
+    SVO_ARG(ctx->win_last && ctx->win_block.base, "the sliding window was off for the last svo_add_frame step (svo_set_window_ba)");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    return window_read(ctx, out, cap);
+}
+
+extern "C" int svo_get_window_result(svo_ctx *ctx, svo_window_result *res)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(res, "null result");
+    SVO_ARG(ctx->win_last && ctx->win_block.base, "the sliding window was off for the last svo_add_frame step (svo_set_window_ba)");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    return window_read_result(ctx, res);
+}
+
+extern "C" int svo_window_ba(svo_ctx *ctx, const svo_window_table *table, int cap, const double P1[12], const double P2[12], int rounds,
+                             int iters, double sigma_px, int min_obs, svo_window_result *res, int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return stage_window_ba(ctx, table, cap, P1, P2, rounds, iters, sigma_px, min_obs, res, mem);
 }
 
 // n ids and ages at `offset` of two device lists -> the caller's.  Capacity rule of the read-backs below: ids / ages null asks

@@ -220,6 +220,17 @@ struct svo_ctx {
     bool carry_restart = true;                           // the online chain's ids start at 0 with its next carry launch
     int carry_last_pairs = 0;                            // pairs of the most recent fused launch that ran with carry (0: it was off)
     DevScratch carry_stage;                              // svo_carry_merge: the caller's lists, the outputs and the scratch
+    // ---- sliding window (svo_window_update, window.hip): nothing allocated until the stage call is first used
+    DevScratch window_stage;                             // the caller's tables and tracks (HOST calls) and the kernel's prefix scratch
+    DevScratch window_ba_stage;                          // svo_window_ba's own: a growing stage call never frees what the other one's launch still reads
+    // svo_set_window_ba: the online chain's table (two buffers, swapped per step) and the optimiser's scratch, ONE growable block
+    int win_frames = 0;                                  // W; 0: off
+    int win_rounds = 4, win_iters = 5, win_min_obs = 10; double win_sigma = 1.0;
+    DevScratch win_block;
+    int win_cur = 0;                                     // which of the two tables is the chain's
+    bool win_clear = true;                               // T1: the next step starts from a cleared table
+    bool win_step = false;                               // set by pipeline_add_frame around its run_pairs: run_back runs the two kernels
+    bool win_last = false; int win_last_frames = 0;      // the last online step ran them (with this W): what the read-backs return
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -322,6 +333,16 @@ void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const i
 int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, svo_step_result *res);
 int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch, int64_t frame_stride,
                          int n_frames, const double *pose0, svo_step_result *results, int results_mem, int carry_first);
+// window.hip: window_update_kernel on a caller's tables
+int stage_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, const svo_window_table *out, int cap, const svo_pt2f *t1_left,
+                        const svo_pt2f *t1_right, const svo_pt2f *t2_left, const svo_pt2f *t2_right, const int64_t *ids, const svo_pt3f *tri,
+                        int n_trk, const double *pose_a, const double *pose_b, int mem);
+int window_alloc(svo_ctx *ctx, int frames);
+int window_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st);
+int window_read(svo_ctx *ctx, const svo_window_table *out, int cap);
+int window_read_result(svo_ctx *ctx, svo_window_result *res);
+int stage_window_ba(svo_ctx *ctx, const svo_window_table *tab, int cap, const double *P1, const double *P2, int rounds, int iters,
+                    double sigma_px, int min_obs, svo_window_result *res, int mem);
 int carry_alloc(svo_ctx *ctx);                           // track carry: its block and, for an existing stream set, the store's share
 int pipeline_streams_create(svo_ctx *ctx, int n_streams);
 int pipeline_streams_reset(svo_ctx *ctx, int id);

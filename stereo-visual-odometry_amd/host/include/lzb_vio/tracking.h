@@ -82,6 +82,10 @@ public:
     // names the key).  Applied right after svo_create.  It is a feature of the per-frame paths: System refuses it together with
     // batch_size > 1, stream_depth > 0 and --split-pairs.
     static bool ReadTrackCarry(int *on, double *min_distance, int *max_age, std::string *err);
+    // additive YAML keys window_ba: W (absent / 0: off; 2..8) with window_ba_rounds (4), window_ba_iters (5), window_ba_sigma (1.0)
+    // and window_ba_min_obs (10): the sliding-window bundle adjustment of the per-frame chain (svo_set_window_ba).  Refused like
+    // the keys above: W outside 0, 2..8, values outside svo_set_window_ba's ranges, and window_ba without track_carry: 1.
+    static bool ReadWindowBa(int *frames, int *rounds, int *iters, double *sigma, int *min_obs, std::string *err);
     bool TrackCarry() const { return track_carry_ != 0; }
     // id and age at t1 of every track GetLastTracks returns, in its order (track carry on; false otherwise)
     bool GetLastTrackIds(std::vector<int64_t> &ids, std::vector<int32_t> &ages);
@@ -149,6 +153,7 @@ private:
     double pose_refine_sigma_ = 1.0;
     int orb_matcher_ = SVO_ORB_MATCHER_BRUTE, orb_match_th_stereo_ = 75, orb_match_th_track_ = 100;                     // orb_matcher / orb_match_*
     double orb_match_ratio_ = 0.9, orb_match_radius_ = 0.0, orb_max_disparity_ = 0.0;
+    int window_ba_ = 0, window_ba_rounds_ = 4, window_ba_iters_ = 5, window_ba_min_obs_ = 10; double window_ba_sigma_ = 1.0;   // additive YAML keys window_ba*
     int track_carry_ = 0, track_carry_max_age_ = 0;          // additive YAML keys track_carry / track_carry_max_age
     double track_carry_min_distance_ = 3.0;                  // ... and track_carry_min_distance
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128

@@ -135,6 +135,27 @@ bool Tracking::ReadTrackCarry(int *on, double *min_distance, int *max_age, std::
     return true;
 }
 
+bool Tracking::ReadWindowBa(int *frames, int *rounds, int *iters, double *sigma, int *min_obs, std::string *err)
+{
+    *frames = 0; *rounds = 4; *iters = 5; *sigma = 1.0; *min_obs = 10;
+    const int w = Config::Has("window_ba") ? Config::Get<int>("window_ba") : 0;
+    const int r = Config::Has("window_ba_rounds") ? Config::Get<int>("window_ba_rounds") : 4;
+    const int it = Config::Has("window_ba_iters") ? Config::Get<int>("window_ba_iters") : 5;
+    const double sg = Config::Has("window_ba_sigma") ? Config::Get<double>("window_ba_sigma") : 1.0;
+    const int mo = Config::Has("window_ba_min_obs") ? Config::Get<int>("window_ba_min_obs") : 10;
+    const int carry = Config::Has("track_carry") ? Config::Get<int>("track_carry") : 0;
+    char msg[240] = "";
+    if (w != 0 && (w < 2 || w > SVO_WINDOW_MAX_FRAMES)) snprintf(msg, sizeof(msg), "window_ba: %d is neither 0 nor in 2..%d", w, SVO_WINDOW_MAX_FRAMES);
+    else if (r < 1 || r > 16) snprintf(msg, sizeof(msg), "window_ba_rounds: %d is outside 1..16", r);
+    else if (it < 1 || it > 100) snprintf(msg, sizeof(msg), "window_ba_iters: %d is outside 1..100", it);
+    else if (!(std::isfinite(sg) && sg > 0.0)) snprintf(msg, sizeof(msg), "window_ba_sigma: %g is not a finite number > 0", sg);
+    else if (mo < 1) snprintf(msg, sizeof(msg), "window_ba_min_obs: %d is < 1", mo);
+    else if (w != 0 && carry != 1) snprintf(msg, sizeof(msg), "window_ba: %d without track_carry: 1 (the window is built from carried tracks)", w);
+    if (msg[0]) { if (err) *err = msg; return false; }
+    *frames = w; *rounds = r; *iters = it; *sigma = sg; *min_obs = mo;
+    return true;
+}
+
 bool Tracking::G2O_EstimatePose_PnP(const double projMatrl[12], const double projMatrr[12], const std::vector<cv::Point2f> &pointsLeft_t2,
                                     const std::vector<cv::Point2f> *pointsRight_t2, const std::vector<cv::Point3f> &points3D_t0,
                                     double rotation[3], double translation[3], svo_refine_result *result)
@@ -199,6 +220,12 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
         if (config_error_.empty()) config_error_ = carry_error;
     } else if (track_carry_)
         LZB_LOG("INFO", "track_carry: 1 (track_carry_min_distance %g, track_carry_max_age %d)", track_carry_min_distance_, track_carry_max_age_);
+    std::string window_error;
+    if (!ReadWindowBa(&window_ba_, &window_ba_rounds_, &window_ba_iters_, &window_ba_sigma_, &window_ba_min_obs_, &window_error)) {
+        if (config_error_.empty()) config_error_ = window_error;
+    } else if (window_ba_)
+        LZB_LOG("INFO", "window_ba: %d (window_ba_rounds %d, window_ba_iters %d, window_ba_sigma %g, window_ba_min_obs %d)", window_ba_,
+                window_ba_rounds_, window_ba_iters_, window_ba_sigma_, window_ba_min_obs_);
     std::string matcher_error;
     if (!ReadOrbMatcher(&orb_matcher_, &orb_match_th_stereo_, &orb_match_th_track_, &orb_match_ratio_, &orb_match_radius_,
                         &orb_max_disparity_, &matcher_error)) {
@@ -360,6 +387,12 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
     if (track_carry_ && (rc = svo_set_track_carry(ctx_, 1, track_carry_min_distance_, track_carry_max_age_)) != SVO_OK) {
         LZB_LOG("ERROR", "svo_set_track_carry (track_carry 1, track_carry_min_distance %g, track_carry_max_age %d) failed (%d): %s",
                 track_carry_min_distance_, track_carry_max_age_, rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    if (window_ba_ && (rc = svo_set_window_ba(ctx_, window_ba_, window_ba_rounds_, window_ba_iters_, window_ba_sigma_, window_ba_min_obs_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_window_ba (window_ba %d) failed (%d): %s", window_ba_, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;
