@@ -4,13 +4,13 @@
 // include/svo_abi.h and DESIGN.md section 5g; tests/_ba_ref.py is its numpy twin.
 //
 // pose_ba_kernel: ONE workgroup of four waves per pair, lanes stride the pair's points -- the mapping, the butterfly, the
-// fixed-order cross-wave sum and the pair-valued cost of pose_refine_kernel (refine_device.h), so that every thread holds the
-// same reduced 6 x 6 system, solves it redundantly in registers and takes the same accept / reject / round decisions.
+// fixed-order cross-wave sum and the pair-valued cost of pose_refine_kernel (refine_device.h, which also holds the per-view
+// math and the 3 x 3 elimination), so that every thread holds the same reduced 6 x 6 system, solves it redundantly in registers
+// and takes the same accept / reject / round decisions.
 // A point is eliminated by the 3 x 3 Cholesky factor of its own block in its lane's registers; one LM iteration is two passes
 // over the points: ba_build (the reduced sums at the accepted estimate and the current damping) and ba_trial (the
 // back-substitution, the trial points, the cost at the trial estimate).  The accepted and the trial points of a pair live in
 // device memory in two buffers swapped by pointer; a point and its flag are only ever touched by the lane that strides over it.
-#include <cstring>
 #include "refine_device.h"
 
 namespace svo {
@@ -21,12 +21,7 @@ constexpr int kBaG = 22, kBaDiag = 28, kBaCount = 34, kBaCostLo = 35, kBaBad = 3
 
 struct BaArgs {
     const float *X3; const float2 *x1l, *x1r, *x2l, *x2r; int64_t stride;     // points of item b at + b * stride (x2r: d = 8 only)
-    int n_fixed, cap;                                                        // stage call: the point count; points per item at most
-    double ML[9], MR[9], p4R[3];                                             // view L: [K1 | 0]; view R: P2 = [MR | p4R]
-    int rounds, iters, min_inliers; double sigma;
-    PnpRecord *pnp;                                                          // fused: the pairs' PnP records
-    double rvec0[3], tvec0[3];                                               // stage call (pnp null): the start pose
-    svo_refine_result *res; uint8_t *flags; int64_t flag_stride;             // per item
+    RefineCommon c;
     double *Xa, *Xb; int64_t x_stride;                                       // the two point buffers of item b at + b * x_stride * 3
 };
 
@@ -42,22 +37,7 @@ __device__ inline void ba_eval(const BaArgs &a, const double (&X)[3], const doub
     for (int k = 0; k < 3; k++) p.Y[k] = ((X[0] * R[k * 3] + X[1] * R[k * 3 + 1]) + X[2] * R[k * 3 + 2]) + t[k];
     p.proj = true;
 #pragma unroll
-    for (int v = 0; v < 2 + V2; v++) {
-        const double *M = (v & 1) ? a.MR : a.ML;
-        const double Z[3] = {v < 2 ? X[0] : p.Y[0], v < 2 ? X[1] : p.Y[1], v < 2 ? X[2] : p.Y[2]};
-        double h[3];
-        for (int k = 0; k < 3; k++) {
-            h[k] = (Z[0] * M[k * 3] + Z[1] * M[k * 3 + 1]) + Z[2] * M[k * 3 + 2];
-            if (v & 1) h[k] = h[k] + a.p4R[k];
-        }
-        const bool ok = h[2] > kRefineMinDepth;
-        p.proj = p.proj && ok;
-        const double h2 = ok ? h[2] : 1.0;
-        const double u = h[0] / h2, w = h[1] / h2;
-        p.r[2 * v] = u - (double)o[v].x;
-        p.r[2 * v + 1] = w - (double)o[v].y;
-        for (int k = 0; k < 3; k++) { p.A[2 * v][k] = (M[k] - u * M[6 + k]) / h2; p.A[2 * v + 1][k] = (M[3 + k] - w * M[6 + k]) / h2; }
-    }
+    for (int v = 0; v < 2 + V2; v++) p.proj = refine_project(a.c.cam, v & 1, v < 2 ? X : p.Y, o[v], p.r + 2 * v, p.A + 2 * v) && p.proj;
 }
 
 template <int V2>
@@ -87,12 +67,10 @@ __device__ inline void ba_system(const BaPoint<V2> &p, const double (&R)[9], dou
 #pragma unroll
     for (int m = 0; m < D2; m++) {
         const double *A = p.A[4 + m];
-        for (int j = 0; j < 3; j++) { Jx[4 + m][j] = (A[0] * R[j] + A[1] * R[3 + j]) + A[2] * R[6 + j]; Jp[m][j] = A[j]; }    // a^T R
-        Jp[m][3] = p.Y[1] * A[2] - p.Y[2] * A[1];                                                  // -a^T [Y]x = (Y x a)^T
-        Jp[m][4] = p.Y[2] * A[0] - p.Y[0] * A[2];
-        Jp[m][5] = p.Y[0] * A[1] - p.Y[1] * A[0];
+        for (int j = 0; j < 3; j++) Jx[4 + m][j] = (A[0] * R[j] + A[1] * R[3 + j]) + A[2] * R[6 + j];      // a^T R
+        refine_pose_row(A, p.Y, Jp[m]);
     }
-    double V[3][3], gx[3], gp[6];
+    double V[6], gx[3], gp[6];                                       // V: 00 10 11 20 21 22
 #pragma unroll
     for (int i = 0; i < 3; i++) {
 #pragma unroll
@@ -100,7 +78,7 @@ __device__ inline void ba_system(const BaPoint<V2> &p, const double (&R)[9], dou
             double v = Jx[0][i] * Jx[0][j];
 #pragma unroll
             for (int k = 1; k < D; k++) v += Jx[k][i] * Jx[k][j];
-            V[i][j] = ws * v;
+            V[i * (i + 1) / 2 + j] = ws * v;
         }
         double g = Jx[0][i] * p.r[0];
 #pragma unroll
@@ -121,34 +99,10 @@ __device__ inline void ba_system(const BaPoint<V2> &p, const double (&R)[9], dou
         for (int m = 1; m < D2; m++) g += Jp[m][q] * p.r[4 + m];
         gp[q] = ws * g;
     }
-    // 3 x 3 Cholesky of V + lam diag V, row by row
-    const double d0 = V[0][0] + lam * V[0][0];
-    bool ok = d0 > 0.0;
-    const double l00 = sqrt(ok ? d0 : 1.0);
-    const double l10 = V[1][0] / l00;
-    const double d1 = (V[1][1] + lam * V[1][1]) - l10 * l10;
-    ok = ok && d1 > 0.0;
-    const double l11 = sqrt(ok ? d1 : 1.0);
-    const double l20 = V[2][0] / l00;
-    const double l21 = (V[2][1] - l20 * l10) / l11;
-    const double d2 = ((V[2][2] + lam * V[2][2]) - l20 * l20) - l21 * l21;
-    ok = ok && d2 > 0.0;
-    const double l22 = sqrt(ok ? d2 : 1.0);
-    s.ok = ok;
-    s.L[0] = l00; s.L[1] = l10; s.L[2] = l11; s.L[3] = l20; s.L[4] = l21; s.L[5] = l22;
+    s.ok = refine_chol3(V, lam, s.L);
 #pragma unroll
-    for (int q = 0; q < 6; q++) {
-        const double t0 = s.T[q][0] / l00;
-        const double t1 = (s.T[q][1] - l10 * t0) / l11;
-        const double t2 = ((s.T[q][2] - l20 * t0) - l21 * t1) / l22;
-        s.T[q][0] = ok ? t0 : 0.0; s.T[q][1] = ok ? t1 : 0.0; s.T[q][2] = ok ? t2 : 0.0;
-    }
-    {
-        const double y0 = gx[0] / l00;
-        const double y1 = (gx[1] - l10 * y0) / l11;
-        const double y2 = ((gx[2] - l20 * y0) - l21 * y1) / l22;
-        s.y[0] = ok ? y0 : 0.0; s.y[1] = ok ? y1 : 0.0; s.y[2] = ok ? y2 : 0.0;
-    }
+    for (int q = 0; q < 6; q++) refine_fwd3(s.L, s.T[q], s.ok, s.T[q]);      // T = W L^-T
+    refine_fwd3(s.L, gx, s.ok, s.y);
     if (ACC) {
         int idx = 1;
 #pragma unroll
@@ -165,31 +119,6 @@ __device__ inline void ba_system(const BaPoint<V2> &p, const double (&R)[9], dou
             acc[kBaG + q] += gp[q] - ((s.T[q][0] * s.y[0] + s.T[q][1] * s.y[1]) + s.T[q][2] * s.y[2]);
         }
     }
-}
-
-__device__ inline void ba_huber(bool robust, double c, double tau, double &w, double &rho)
-{
-    w = 1.0; rho = c;
-    if (robust && c > tau) { w = sqrt(tau / c); rho = 2.0 * sqrt(tau * c) - tau; }
-}
-
-// The cost pair of a pass: the butterfly with pair additions, the wave totals to `red`
-__device__ inline void ba_wave_cost(double cs, double ce, double *red, int wave, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const double os = __shfl_xor(cs, m, 64), oe = __shfl_xor(ce, m, 64);
-        refine_dd_add(cs, ce, os, oe);
-    }
-    if (lane == 0) { red[wave * kBaAcc] = cs; red[wave * kBaAcc + kBaCostLo] = ce; }
-}
-__device__ inline void ba_block_cost(const double *red, double *S)
-{
-    double cs = red[0], ce = red[kBaCostLo];
-    for (int w = 1; w < 4; w++) refine_dd_add(cs, ce, red[w * kBaAcc], red[w * kBaAcc + kBaCostLo]);
-    const double hi = cs + ce;                              // normalised: hi the rounded sum, lo what is left
-    S[0] = hi;
-    S[kBaCostLo] = ce - (hi - cs);
 }
 
 enum { kBaInit = 0, kBaReclass = 1, kBaKeep = 2 };
@@ -232,7 +161,7 @@ __device__ void ba_build(const BaArgs &a, const BaItem &it, double *Xc, const do
         }
         if (!act) continue;
         double w, rho;
-        ba_huber(robust, c, tau, w, rho);
+        refine_huber(robust, c, tau, w, rho);
         refine_dd_add(acc[0], acc[kBaCostLo], rho, 0.0);
         acc[kBaCount] += 1.0;
         BaSys s;
@@ -244,11 +173,12 @@ __device__ void ba_build(const BaArgs &a, const BaItem &it, double *Xc, const do
         const double ws = refine_wave_allsum(acc[k]);
         if (lane == 0) red[wave * kBaAcc + k] = ws;
     }
-    ba_wave_cost(acc[0], acc[kBaCostLo], red, wave, lane);
+    refine_wave_cost(acc[0], acc[kBaCostLo]);
+    if (lane == 0) { red[wave * kBaAcc] = acc[0]; red[wave * kBaAcc + kBaCostLo] = acc[kBaCostLo]; }
     __syncthreads();
     const int k = threadIdx.x;
     if (k >= 1 && k <= kBaCount) S[k] = ((red[k] + red[kBaAcc + k]) + red[2 * kBaAcc + k]) + red[3 * kBaAcc + k];
-    if (k == 0) ba_block_cost(red, S);
+    if (k == 0) refine_block_cost(red, kBaAcc, kBaCostLo, 4, S[0], S[kBaCostLo]);
     __syncthreads();
 }
 
@@ -271,7 +201,7 @@ __device__ void ba_trial(const BaArgs &a, const BaItem &it, const double *Xc, do
             BaPoint<V2> p;
             ba_eval<V2>(a, X, R, t, o, p);                  // (an active point is projectable at the accepted estimate)
             double w, rho;
-            ba_huber(robust, ba_chi<V2>(p, s2), tau, w, rho);
+            refine_huber(robust, ba_chi<V2>(p, s2), tau, w, rho);
             BaSys s;
             ba_system<V2, false>(p, R, w * is2, lam, s, nullptr);
             double z[3];
@@ -281,10 +211,8 @@ __device__ void ba_trial(const BaArgs &a, const BaItem &it, const double *Xc, do
                 for (int q = 1; q < 6; q++) v += s.T[q][j] * xi[q];
                 z[j] = s.y[j] + v;
             }
-            const double e2 = z[2] / s.L[5];
-            const double e1 = (z[1] - s.L[4] * e2) / s.L[2];
-            const double e0 = ((z[0] - s.L[1] * e1) - s.L[3] * e2) / s.L[0];
-            const double dX[3] = {s.ok ? -e0 : 0.0, s.ok ? -e1 : 0.0, s.ok ? -e2 : 0.0};
+            double dX[3];
+            refine_back3(s.L, z, s.ok, dX);
             for (int k = 0; k < 3; k++) X[k] = X[k] + dX[k];
             step = fmax(step, (dX[0] * dX[0] + dX[1] * dX[1]) + dX[2] * dX[2]);
         }
@@ -294,7 +222,7 @@ __device__ void ba_trial(const BaArgs &a, const BaItem &it, const double *Xc, do
         ba_eval<V2>(a, X, Rn, tn, o, pn);
         if (!pn.proj) { bad += 1.0; continue; }
         double w, rho;
-        ba_huber(robust, ba_chi<V2>(pn, s2), tau, w, rho);
+        refine_huber(robust, ba_chi<V2>(pn, s2), tau, w, rho);
         refine_dd_add(cs, ce, rho, 0.0);
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -303,10 +231,11 @@ __device__ void ba_trial(const BaArgs &a, const BaItem &it, const double *Xc, do
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) step = fmax(step, __shfl_xor(step, m, 64));
     if (lane == 0) { red[wave * kBaAcc + kBaBad] = bad; red[wave * kBaAcc + kBaStep] = step; }
-    ba_wave_cost(cs, ce, red, wave, lane);
+    refine_wave_cost(cs, ce);
+    if (lane == 0) { red[wave * kBaAcc] = cs; red[wave * kBaAcc + kBaCostLo] = ce; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        ba_block_cost(red, S);
+        refine_block_cost(red, kBaAcc, kBaCostLo, 4, S[0], S[kBaCostLo]);
         S[kBaBad] = ((red[kBaBad] + red[kBaAcc + kBaBad]) + red[2 * kBaAcc + kBaBad]) + red[3 * kBaAcc + kBaBad];
         S[kBaStep] = fmax(fmax(red[kBaStep], red[kBaAcc + kBaStep]), fmax(red[2 * kBaAcc + kBaStep], red[3 * kBaAcc + kBaStep]));
     }
@@ -319,28 +248,28 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
     __shared__ double red[4 * kBaAcc];
     __shared__ double S[kBaAcc], Sn[kBaAcc];                // the sums at the accepted estimate; the trial's cost, bad count, step
     const int tid = threadIdx.x, b = blockIdx.x;
-    svo_refine_result *res = a.res + b;
+    svo_refine_result *res = a.c.res + b;
     BaItem it;
-    it.flags = a.flags + (int64_t)b * a.flag_stride;
+    it.flags = a.c.flags + (int64_t)b * a.c.flag_stride;
     it.X3 = a.X3 + (int64_t)b * a.stride * 3;
     it.x1l = a.x1l + (int64_t)b * a.stride; it.x1r = a.x1r + (int64_t)b * a.stride; it.x2l = a.x2l + (int64_t)b * a.stride;
     it.x2r = V2 == 2 ? a.x2r + (int64_t)b * a.stride : nullptr;
     double *const X_out = a.Xa + (int64_t)b * a.x_stride * 3;
     double *Xc = X_out, *Xt = a.Xb + (int64_t)b * a.x_stride * 3;
     double R[9], t[3], rv0[3];
-    int n = a.n_fixed;
+    int n = a.c.n_fixed;
     bool skip = false;
-    if (a.pnp) {
-        const PnpRecord &q = a.pnp[b];
+    if (a.c.pnp) {
+        const PnpRecord &q = a.c.pnp[b];
         for (int i = 0; i < 9; i++) R[i] = q.R[i];
         for (int i = 0; i < 3; i++) { t[i] = q.tvec[i]; rv0[i] = q.rvec[i]; }
         n = q.n;
         skip = q.ok == 0;                                   // solvePnPRansac failed (no model, or fewer points than one needs)
     } else {
-        for (int i = 0; i < 3; i++) { t[i] = a.tvec0[i]; rv0[i] = a.rvec0[i]; }
+        for (int i = 0; i < 3; i++) { t[i] = a.c.tvec0[i]; rv0[i] = a.c.rvec0[i]; }
         refine_rodrigues(rv0, R);
     }
-    n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+    n = n < 0 ? 0 : (n > a.c.cap ? a.c.cap : n);
     it.n = n;
     for (int i = tid; i < n; i += kRefineThreads)           // every X_i starts at its triangulation
         for (int k = 0; k < 3; k++) Xc[3 * (int64_t)i + k] = (double)it.X3[3 * i + k];
@@ -356,13 +285,13 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
         return;
     }
     const double tau = V2 == 2 ? 11.070 : 7.815;            // chi-square 95 % points, d - 3 = 5 and 3 degrees of freedom
-    const double s2 = a.sigma * a.sigma;
+    const double s2 = a.c.sigma * a.c.sigma;
     int total = 0;
     double cost_first = 0.0, cost = 0.0, cost_lo = 0.0;
-    for (int rd = 0; rd < a.rounds; rd++) {
+    for (int rd = 0; rd < a.c.rounds; rd++) {
         const bool robust = rd < 2;
         double lam = 1e-4;
-        for (int k = 0; k < a.iters; k++) {
+        for (int k = 0; k < a.c.iters; k++) {
             total++;
             ba_build<V2>(a, it, Xc, R, t, k > 0 ? kBaKeep : (rd == 0 ? kBaInit : kBaReclass), robust, tau, s2, lam, red, S);
             if (k == 0) {
@@ -417,7 +346,7 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
     for (int i = 0; i < 3; i++) fin = fin && refine_finite(t[i]) && refine_finite(rv[i]);
     for (int i = 0; i < 36; i++) fin = fin && refine_finite(info[i]);
     const bool pd = refine_chol6(info, zero, dummy);
-    const bool applied = n_active >= a.min_inliers && pd && fin;
+    const bool applied = n_active >= a.c.min_inliers && pd && fin;
     // the points that stand, at the front buffer: the accepted ones, or the triangulation again when the PnP pose is kept
     if (!applied) {
         for (int i = tid; i < n; i += kRefineThreads)
@@ -428,12 +357,12 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
     }
     if (tid == 0) {
         double R0[9], t0[3];
-        if (a.pnp) {
-            const PnpRecord &q = a.pnp[b];
+        if (a.c.pnp) {
+            const PnpRecord &q = a.c.pnp[b];
             for (int i = 0; i < 9; i++) R0[i] = q.R[i];
             for (int i = 0; i < 3; i++) { t0[i] = q.tvec[i]; rv0[i] = q.rvec[i]; }
         } else {
-            for (int i = 0; i < 3; i++) { t0[i] = a.tvec0[i]; rv0[i] = a.rvec0[i]; }
+            for (int i = 0; i < 3; i++) { t0[i] = a.c.tvec0[i]; rv0[i] = a.c.rvec0[i]; }
             refine_rodrigues(rv0, R0);
         }
         for (int i = 0; i < 3; i++) {
@@ -445,9 +374,9 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
         res->cost_first = cost_first; res->cost_last = cost;
         res->n_points = n; res->n_active = n_active; res->iters = total; res->views = V2;
         res->status = applied ? SVO_REFINE_APPLIED : SVO_REFINE_KEPT_PNP; res->_pad = 0;
-        if (applied && a.pnp) {
+        if (applied && a.c.pnp) {
             // the gates, T_rel_inv and the chain (finalize_*_kernel) read the pair's PnP record: they see the adjusted pose
-            PnpRecord &q = a.pnp[b];
+            PnpRecord &q = a.c.pnp[b];
             for (int i = 0; i < 3; i++) { q.rvec[i] = rv[i]; q.tvec[i] = t[i]; }
             for (int i = 0; i < 9; i++) q.R[i] = R[i];
         }
@@ -480,19 +409,8 @@ int ba_alloc(svo_ctx *ctx)
     return SVO_OK;
 }
 
-static void ba_fill(const svo_ctx *ctx, BaArgs &a, const double P1[12], const double P2[12])
+static void ba_fill(const svo_ctx *ctx, BaArgs &a)
 {
-    const double ML[9] = {P1[0], 0.0, P1[2], 0.0, P1[5], P1[6], 0.0, 0.0, 1.0};
-    for (int i = 0; i < 9; i++) a.ML[i] = ML[i];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) a.MR[i * 3 + j] = P2[i * 4 + j];
-        a.p4R[i] = P2[i * 4 + 3];
-    }
-    a.rounds = ctx->refine_rounds; a.iters = ctx->refine_iters; a.min_inliers = ctx->refine_min_inliers; a.sigma = ctx->refine_sigma;
-    a.cap = ctx->cfg.max_keypoints;
-    a.res = (svo_refine_result *)ctx->refine_buf;
-    a.flags = ctx->refine_buf + refine_cut(ctx->cfg).flags;
-    a.flag_stride = ctx->cfg.max_keypoints;
     a.Xa = (double *)ctx->ba_buf; a.Xb = (double *)(ctx->ba_buf + ba_cut(ctx->cfg).Xb);
     a.x_stride = ctx->cfg.max_keypoints;
 }
@@ -500,11 +418,12 @@ static void ba_fill(const svo_ctx *ctx, BaArgs &a, const double P1[12], const do
 void launch_ba_batch(svo_ctx *ctx, int n_pairs, hipStream_t st)
 {
     BaArgs a{};
-    ba_fill(ctx, a, ctx->cfg.P1, ctx->cfg.P2);
+    refine_fill(ctx, a.c, ctx->cfg.P1, ctx->cfg.P2);
+    ba_fill(ctx, a);
     const bool four = ctx->cfg.track_mode == SVO_MODE_LK;      // ORB mode has no t2_right (zeros): three views
     a.X3 = ctx->X3; a.x1l = ctx->cmp[0]; a.x1r = ctx->cmp[1]; a.x2l = ctx->cmp[3]; a.x2r = four ? ctx->cmp[2] : nullptr;
     a.stride = ctx->cfg.max_keypoints;
-    a.pnp = (PnpRecord *)ctx->pnp_ws;
+    a.c.pnp = (PnpRecord *)ctx->pnp_ws;
     if (four) hipLaunchKernelGGL(pose_ba_kernel<2>, dim3(n_pairs), dim3(kRefineThreads), 0, st, a);
     else hipLaunchKernelGGL(pose_ba_kernel<1>, dim3(n_pairs), dim3(kRefineThreads), 0, st, a);
 }
@@ -519,52 +438,36 @@ int stage_refine_ba(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img1_left
     SVO_ARG(n == 0 || (obj && img1_left && img1_right && img2_left), "null pointer");
     SVO_TRY(ba_alloc(ctx));
     SVO_HIP(hipSetDevice(ctx->device));
-    const svo_config &c = ctx->cfg;
-    const int B = c.max_batch;
     const bool four = img2_right != nullptr;
     BaArgs a{};
-    ba_fill(ctx, a, P1, P2);
-    a.res += B;
-    a.flags += (size_t)B * c.max_keypoints; a.flag_stride = 0;
-    a.Xa += (size_t)B * c.max_keypoints * 3; a.Xb += (size_t)B * c.max_keypoints * 3; a.x_stride = 0;
-    a.stride = 0; a.n_fixed = n; a.pnp = nullptr;
-    for (int i = 0; i < 3; i++) { a.rvec0[i] = rvec0[i]; a.tvec0[i] = tvec0[i]; }
-    const RefineCut o = refine_cut(c);
-    const BaCut ob = ba_cut(c);
+    refine_fill_stage(ctx, a.c, P1, P2, n, rvec0, tvec0);
+    ba_fill(ctx, a);
+    const size_t own = (size_t)ctx->cfg.max_batch * ctx->cfg.max_keypoints * 3;      // item max_batch is the stage call's
+    a.Xa += own; a.Xb += own; a.x_stride = 0;
+    const RefineCut o = refine_cut(ctx->cfg);
+    const BaCut ob = ba_cut(ctx->cfg);
     SVO_TRY(to_device(ctx, (const float *)obj, (float *)(ctx->refine_buf + o.X), (size_t)3 * n, mem, &a.X3));
     SVO_TRY(to_device(ctx, (const float2 *)img1_left, (float2 *)(ctx->ba_buf + ob.x1l), (size_t)n, mem, &a.x1l));
     SVO_TRY(to_device(ctx, (const float2 *)img1_right, (float2 *)(ctx->ba_buf + ob.x1r), (size_t)n, mem, &a.x1r));
     SVO_TRY(to_device(ctx, (const float2 *)img2_left, (float2 *)(ctx->refine_buf + o.xl), (size_t)n, mem, &a.x2l));
     if (four) SVO_TRY(to_device(ctx, (const float2 *)img2_right, (float2 *)(ctx->refine_buf + o.xr), (size_t)n, mem, &a.x2r));
-    if (mem == SVO_MEM_DEVICE && active) a.flags = active;
+    if (mem == SVO_MEM_DEVICE && active) a.c.flags = active;
     if (four) hipLaunchKernelGGL(pose_ba_kernel<2>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
     else hipLaunchKernelGGL(pose_ba_kernel<1>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
     SVO_HIP(hipGetLastError());
-    svo_refine_result *h;                                    // the record comes back to the host in both memory kinds
-    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
-    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)a.res, 1, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, active, (const uint8_t *)a.flags, (size_t)n, mem));                         // (device: the kernel wrote them)
     SVO_TRY(from_device(ctx, X_out, (const double *)a.Xa, (size_t)3 * n, mem));
-    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
-    memcpy(res, h, sizeof(*res));
-    return SVO_OK;
+    return refine_stage_finish(ctx, a.c, n, res, active, mem);
 }
 
 // the points of pair `pair` of the last fused launch, which ran in SVO_REFINE_BA mode; the caller has ordered the pose stage
 // before the context's stream
 int ba_read_points(svo_ctx *ctx, int pair, double *X, int cap, int *n_out)
 {
-    const svo_config &c = ctx->cfg;
     svo_refine_result *h;
-    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
-    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)ctx->refine_buf + pair, 1, SVO_MEM_HOST));
-    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+    SVO_TRY(refine_fetch_record(ctx, pair, X, cap, "point capacity too small", &h, n_out));
     const int n = h->n_points;
-    SVO_ARG(n >= 0 && n <= c.max_keypoints, "corrupt point count");
-    if (n_out) *n_out = n;                                  // also when the capacity is too small: what to size X for
-    SVO_ARG(X == nullptr || n <= cap, "point capacity too small");
     if (!X || n == 0) return SVO_OK;
-    SVO_TRY(from_device(ctx, X, (const double *)ctx->ba_buf + (size_t)pair * c.max_keypoints * 3, (size_t)3 * n, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, X, (const double *)ctx->ba_buf + (size_t)pair * ctx->cfg.max_keypoints * 3, (size_t)3 * n, SVO_MEM_HOST));
     return io_done(ctx, SVO_MEM_HOST);
 }
 

@@ -10,6 +10,8 @@
 // barriers per evaluation, none per solve.  The stage is a chain of about rounds x iters dependent evaluate-and-solve steps of
 // a few hundred kFLOP each: latency, not arithmetic, so a pair gets the four SIMDs of one CU and no more.
 // A point's active flag lives in device memory and is only ever touched by the lane that strides over it.
+// The per-view math, the Huber weight and the cost pair are refine_device.h's leaves (all three optimisers use them); the host
+// plumbing around a launch (RefineCommon; defined below) is shared with ba.hip.  The kernel keeps its own prologue and epilogue.
 #include <cmath>
 #include <cstring>
 #include "refine_device.h"
@@ -20,12 +22,7 @@ constexpr int kRefAcc = 31;                    // cost, H (21, row-major upper t
 constexpr int kRefCount = 28, kRefCostLo = 29, kRefBad = 30;
 struct RefineArgs {
     const float *X3; const float2 *xl, *xr; int64_t stride;      // points of item b at + b * stride (xr: two-view launches only)
-    int n_fixed, cap;                                            // stage call: the point count; points per item at most
-    double ML[9], MR[9], p4R[3];                                 // view L: [K1 | 0]; view R: P2 = [MR | p4R]
-    int rounds, iters, min_inliers; double sigma;
-    PnpRecord *pnp;                                              // fused: the pairs' PnP records (start pose; rewritten when R7 says so)
-    double rvec0[3], tvec0[3];                                   // stage call (pnp null): the start pose
-    svo_refine_result *res; uint8_t *flags; int64_t flag_stride; // per item
+    RefineCommon c;
 };
 
 // One evaluation of a pair's points at (R, t): residuals, c_i, Jacobians (R3, R4), the sums of R5 / R6 over the active set.
@@ -53,25 +50,10 @@ __device__ void refine_pass(const RefineArgs &a, const float *X3, const float2 *
         bool proj = true;
 #pragma unroll
         for (int v = 0; v < V; v++) {
-            const double *M = v == 0 ? a.ML : a.MR;
-            const float2 o = v == 0 ? xl[i] : xr[i];
-            double h[3];
-            for (int k = 0; k < 3; k++) {
-                h[k] = (Y[0] * M[k * 3] + Y[1] * M[k * 3 + 1]) + Y[2] * M[k * 3 + 2];
-                if (v == 1) h[k] = h[k] + a.p4R[k];
-            }
-            const bool ok = h[2] > kRefineMinDepth;
-            proj = proj && ok;
-            const double h2 = ok ? h[2] : 1.0;
-            const double u = h[0] / h2, w = h[1] / h2;
-            r[2 * v] = u - (double)o.x;
-            r[2 * v + 1] = w - (double)o.y;
-            double da[3], db[3];
-            for (int k = 0; k < 3; k++) { da[k] = (M[k] - u * M[6 + k]) / h2; db[k] = (M[3 + k] - w * M[6 + k]) / h2; }
-            for (int k = 0; k < 3; k++) { J[2 * v][k] = da[k]; J[2 * v + 1][k] = db[k]; }
-            J[2 * v][3] = Y[1] * da[2] - Y[2] * da[1];     J[2 * v + 1][3] = Y[1] * db[2] - Y[2] * db[1];      // -a^T [Y]x = (Y x a)^T
-            J[2 * v][4] = Y[2] * da[0] - Y[0] * da[2];     J[2 * v + 1][4] = Y[2] * db[0] - Y[0] * db[2];
-            J[2 * v][5] = Y[0] * da[1] - Y[1] * da[0];     J[2 * v + 1][5] = Y[0] * db[1] - Y[1] * db[0];
+            double A[2][3];
+            proj = refine_project(a.c.cam, v == 1, Y, v == 0 ? xl[i] : xr[i], r + 2 * v, A) && proj;
+            refine_pose_row(A[0], Y, J[2 * v]);
+            refine_pose_row(A[1], Y, J[2 * v + 1]);
         }
         double c = 0.0;
         if (proj) {
@@ -87,8 +69,8 @@ __device__ void refine_pass(const RefineArgs &a, const float *X3, const float2 *
         if (mode != kRefTrial) flags[i] = act ? 1 : 0;
         if (!act) continue;
         if (!proj) { acc[kRefBad] += 1.0; continue; }
-        double w = 1.0, rho = c;
-        if (robust && c > tau) { w = sqrt(tau / c); rho = 2.0 * sqrt(tau * c) - tau; }
+        double w, rho;
+        refine_huber(robust, c, tau, w, rho);
         refine_dd_add(acc[0], acc[kRefCostLo], rho, 0.0);
         acc[kRefCount] += 1.0;
         int q = 1;
@@ -116,26 +98,13 @@ __device__ void refine_pass(const RefineArgs &a, const float *X3, const float2 *
         const double ws = refine_wave_allsum(acc[k]);
         if (lane == 0) red[wave * kRefAcc + k] = ws;
     }
-    {
-        // the cost pair: the same butterfly with pair additions (TwoSum is symmetric, so every lane ends with the same pair)
-        double cs = acc[0], ce = acc[kRefCostLo];
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const double os = __shfl_xor(cs, m, 64), oe = __shfl_xor(ce, m, 64);
-            refine_dd_add(cs, ce, os, oe);
-        }
-        if (lane == 0) { red[wave * kRefAcc] = cs; red[wave * kRefAcc + kRefCostLo] = ce; }
-    }
+    double cs = acc[0], ce = acc[kRefCostLo];
+    refine_wave_cost(cs, ce);
+    if (lane == 0) { red[wave * kRefAcc] = cs; red[wave * kRefAcc + kRefCostLo] = ce; }
     __syncthreads();
     const int k = threadIdx.x;
     if (k >= 1 && k < kRefAcc && k != kRefCostLo) S[k] = ((red[k] + red[kRefAcc + k]) + red[2 * kRefAcc + k]) + red[3 * kRefAcc + k];
-    if (k == 0) {
-        double cs = red[0], ce = red[kRefCostLo];
-        for (int w = 1; w < 4; w++) refine_dd_add(cs, ce, red[w * kRefAcc], red[w * kRefAcc + kRefCostLo]);
-        const double hi = cs + ce;                          // normalised: hi the rounded sum, lo what is left
-        S[0] = hi;
-        S[kRefCostLo] = ce - (hi - cs);
-    }
+    if (k == 0) refine_block_cost(red, kRefAcc, kRefCostLo, 4, S[0], S[kRefCostLo]);
     __syncthreads();
 }
 
@@ -145,25 +114,25 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
     __shared__ double red[4 * kRefAcc];
     __shared__ double tot[2][kRefAcc];                      // the sums at the accepted pose and at the trial pose
     const int tid = threadIdx.x, b = blockIdx.x;
-    svo_refine_result *res = a.res + b;
-    uint8_t *flags = a.flags + (int64_t)b * a.flag_stride;
+    svo_refine_result *res = a.c.res + b;
+    uint8_t *flags = a.c.flags + (int64_t)b * a.c.flag_stride;
     const float *X3 = a.X3 + (int64_t)b * a.stride * 3;
     const float2 *xl = a.xl + (int64_t)b * a.stride;
     const float2 *xr = V == 2 ? a.xr + (int64_t)b * a.stride : nullptr;
     double R[9], t[3], rv0[3];
-    int n = a.n_fixed;
+    int n = a.c.n_fixed;
     bool skip = false;
-    if (a.pnp) {
-        const PnpRecord &q = a.pnp[b];
+    if (a.c.pnp) {
+        const PnpRecord &q = a.c.pnp[b];
         for (int i = 0; i < 9; i++) R[i] = q.R[i];
         for (int i = 0; i < 3; i++) { t[i] = q.tvec[i]; rv0[i] = q.rvec[i]; }
         n = q.n;
         skip = q.ok == 0;                                   // solvePnPRansac failed (no model, or fewer points than one needs)
     } else {
-        for (int i = 0; i < 3; i++) { t[i] = a.tvec0[i]; rv0[i] = a.rvec0[i]; }
+        for (int i = 0; i < 3; i++) { t[i] = a.c.tvec0[i]; rv0[i] = a.c.rvec0[i]; }
         refine_rodrigues(rv0, R);
     }
-    n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+    n = n < 0 ? 0 : (n > a.c.cap ? a.c.cap : n);
     if (skip) {
         for (int i = tid; i < n; i += kRefineThreads) flags[i] = 0;
         if (tid == 0) {
@@ -176,17 +145,17 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
         return;
     }
     const double tau = V == 2 ? 9.488 : 5.991;
-    const double s2 = a.sigma * a.sigma, is2 = 1.0 / s2;
+    const double s2 = a.c.sigma * a.c.sigma, is2 = 1.0 / s2;
     double *S = tot[0], *Sn = tot[1];
     int total = 0;
     double cost_first = 0.0, cost = 0.0, cost_lo = 0.0;
-    for (int rd = 0; rd < a.rounds; rd++) {
+    for (int rd = 0; rd < a.c.rounds; rd++) {
         const bool robust = rd < 2;
         refine_pass<V>(a, X3, xl, xr, flags, n, R, t, rd == 0 ? kRefInit : kRefReclass, robust, tau, s2, red, S);
         cost = S[0]; cost_lo = S[kRefCostLo];
         if (rd == 0) cost_first = cost;
         double lam = 1e-4;
-        for (int it = 0; it < a.iters; it++) {
+        for (int it = 0; it < a.c.iters; it++) {
             total++;
             double A[36], g[6], xi[6];
             {
@@ -236,16 +205,16 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
     for (int i = 0; i < 3; i++) fin = fin && refine_finite(t[i]) && refine_finite(rv[i]);
     for (int i = 0; i < 36; i++) fin = fin && refine_finite(info[i]);
     const bool pd = refine_chol6(info, zero, dummy);
-    const bool applied = n_active >= a.min_inliers && pd && fin;
+    const bool applied = n_active >= a.c.min_inliers && pd && fin;
     if (tid == 0) {
         // the start pose again, from where it came (kept in registers through the rounds it cost the two-view kernel its second wave per SIMD)
         double R0[9], t0[3];
-        if (a.pnp) {
-            const PnpRecord &q = a.pnp[b];
+        if (a.c.pnp) {
+            const PnpRecord &q = a.c.pnp[b];
             for (int i = 0; i < 9; i++) R0[i] = q.R[i];
             for (int i = 0; i < 3; i++) { t0[i] = q.tvec[i]; rv0[i] = q.rvec[i]; }
         } else {
-            for (int i = 0; i < 3; i++) { t0[i] = a.tvec0[i]; rv0[i] = a.rvec0[i]; }
+            for (int i = 0; i < 3; i++) { t0[i] = a.c.tvec0[i]; rv0[i] = a.c.rvec0[i]; }
             refine_rodrigues(rv0, R0);
         }
         for (int i = 0; i < 3; i++) {
@@ -257,9 +226,9 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
         res->cost_first = cost_first; res->cost_last = cost;
         res->n_points = n; res->n_active = n_active; res->iters = total; res->views = V;
         res->status = applied ? SVO_REFINE_APPLIED : SVO_REFINE_KEPT_PNP; res->_pad = 0;
-        if (applied && a.pnp) {
+        if (applied && a.c.pnp) {
             // the gates, T_rel_inv and the chain (finalize_*_kernel) read the pair's PnP record: they see the refined pose
-            PnpRecord &q = a.pnp[b];
+            PnpRecord &q = a.c.pnp[b];
             for (int i = 0; i < 3; i++) { q.rvec[i] = rv[i]; q.tvec[i] = t[i]; }
             for (int i = 0; i < 9; i++) q.R[i] = R[i];
         }
@@ -285,29 +254,57 @@ int refine_alloc(svo_ctx *ctx)
     return SVO_OK;
 }
 
-static void refine_fill(const svo_ctx *ctx, RefineArgs &a, const double P1[12], const double P2[12])
+void refine_fill(const svo_ctx *ctx, RefineCommon &c, const double P1[12], const double P2[12])
 {
-    // K1 = (fx, fy, cx, cy) of P1 as the PnP stage takes it; P2 whole
-    const double ML[9] = {P1[0], 0.0, P1[2], 0.0, P1[5], P1[6], 0.0, 0.0, 1.0};
-    for (int i = 0; i < 9; i++) a.ML[i] = ML[i];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) a.MR[i * 3 + j] = P2 ? P2[i * 4 + j] : 0.0;
-        a.p4R[i] = P2 ? P2[i * 4 + 3] : 0.0;
-    }
-    a.rounds = ctx->refine_rounds; a.iters = ctx->refine_iters; a.min_inliers = ctx->refine_min_inliers; a.sigma = ctx->refine_sigma;
-    a.cap = ctx->cfg.max_keypoints;
-    a.res = (svo_refine_result *)ctx->refine_buf;
-    a.flags = ctx->refine_buf + refine_cut(ctx->cfg).flags;
-    a.flag_stride = ctx->cfg.max_keypoints;
+    c.cam = stereo_cam(P1, P2);
+    c.rounds = ctx->refine_rounds; c.iters = ctx->refine_iters; c.min_inliers = ctx->refine_min_inliers; c.sigma = ctx->refine_sigma;
+    c.cap = ctx->cfg.max_keypoints;
+    c.res = (svo_refine_result *)ctx->refine_buf;
+    c.flags = ctx->refine_buf + refine_cut(ctx->cfg).flags;
+    c.flag_stride = ctx->cfg.max_keypoints;
+}
+
+void refine_fill_stage(const svo_ctx *ctx, RefineCommon &c, const double P1[12], const double P2[12], int n, const double rvec0[3],
+                       const double tvec0[3])
+{
+    refine_fill(ctx, c, P1, P2);
+    const int B = ctx->cfg.max_batch;                        // item B of the block is the stage call's
+    c.res += B;
+    c.flags += (size_t)B * ctx->cfg.max_keypoints; c.flag_stride = 0;
+    c.n_fixed = n; c.pnp = nullptr;
+    for (int i = 0; i < 3; i++) { c.rvec0[i] = rvec0[i]; c.tvec0[i] = tvec0[i]; }
+}
+
+int refine_stage_finish(svo_ctx *ctx, const RefineCommon &c, int n, svo_refine_result *res, uint8_t *active, int mem)
+{
+    svo_refine_result *h;                                    // the record comes back to the host in both memory kinds
+    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
+    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)c.res, 1, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, active, (const uint8_t *)c.flags, (size_t)n, mem));                         // (device: the kernel wrote them)
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+    memcpy(res, h, sizeof(*res));
+    return SVO_OK;
+}
+
+int refine_fetch_record(svo_ctx *ctx, int pair, const void *dst, int cap, const char *too_small, svo_refine_result **h, int *n_out)
+{
+    SVO_TRY(pinned_block(ctx, sizeof(**h), h));
+    SVO_TRY(from_device(ctx, *h, (const svo_refine_result *)ctx->refine_buf + pair, 1, SVO_MEM_HOST));
+    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+    const int n = (*h)->n_points;
+    SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "corrupt point count");
+    if (n_out) *n_out = n;                                  // also when the capacity is too small: what to size dst for
+    SVO_ARG(dst == nullptr || n <= cap, too_small);         // nothing else has been written
+    return SVO_OK;
 }
 
 void launch_refine_batch(svo_ctx *ctx, int n_pairs, hipStream_t st)
 {
     RefineArgs a{};
-    refine_fill(ctx, a, ctx->cfg.P1, ctx->cfg.P2);
+    refine_fill(ctx, a.c, ctx->cfg.P1, ctx->cfg.P2);
     const bool two = ctx->cfg.track_mode == SVO_MODE_LK;       // ORB mode has no t2_right (zeros): view L only
     a.X3 = ctx->X3; a.xl = ctx->cmp[3]; a.xr = two ? ctx->cmp[2] : nullptr; a.stride = ctx->cfg.max_keypoints;
-    a.pnp = (PnpRecord *)ctx->pnp_ws;
+    a.c.pnp = (PnpRecord *)ctx->pnp_ws;
     if (two) hipLaunchKernelGGL(pose_refine_kernel<2>, dim3(n_pairs), dim3(kRefineThreads), 0, st, a);
     else hipLaunchKernelGGL(pose_refine_kernel<1>, dim3(n_pairs), dim3(kRefineThreads), 0, st, a);
 }
@@ -320,33 +317,20 @@ int stage_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img_lef
     SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "n exceeds max_keypoints");
     SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
     SVO_ARG(n == 0 || (obj && img_left), "null pointer");
-    const int rc = refine_alloc(ctx);
-    if (rc) return rc;
+    SVO_TRY(refine_alloc(ctx));
     SVO_HIP(hipSetDevice(ctx->device));
-    const svo_config &c = ctx->cfg;
-    const int B = c.max_batch;
     const bool two = img_right != nullptr;
     RefineArgs a{};
-    refine_fill(ctx, a, P1, two ? P2 : nullptr);
-    a.res += B;
-    uint8_t *own_flags = a.flags + (size_t)B * c.max_keypoints;
-    a.flags = own_flags; a.flag_stride = 0; a.stride = 0; a.n_fixed = n; a.pnp = nullptr;
-    for (int i = 0; i < 3; i++) { a.rvec0[i] = rvec0[i]; a.tvec0[i] = tvec0[i]; }
-    const RefineCut o = refine_cut(c);
+    refine_fill_stage(ctx, a.c, P1, two ? P2 : nullptr, n, rvec0, tvec0);
+    const RefineCut o = refine_cut(ctx->cfg);
     SVO_TRY(to_device(ctx, (const float *)obj, (float *)(ctx->refine_buf + o.X), (size_t)3 * n, mem, &a.X3));
     SVO_TRY(to_device(ctx, (const float2 *)img_left, (float2 *)(ctx->refine_buf + o.xl), (size_t)n, mem, &a.xl));
     if (two) SVO_TRY(to_device(ctx, (const float2 *)img_right, (float2 *)(ctx->refine_buf + o.xr), (size_t)n, mem, &a.xr));
-    if (mem == SVO_MEM_DEVICE && active) a.flags = active;
+    if (mem == SVO_MEM_DEVICE && active) a.c.flags = active;
     if (two) hipLaunchKernelGGL(pose_refine_kernel<2>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
     else hipLaunchKernelGGL(pose_refine_kernel<1>, dim3(1), dim3(kRefineThreads), 0, ctx->stream, a);
     SVO_HIP(hipGetLastError());
-    svo_refine_result *h;                                    // the record comes back to the host in both memory kinds
-    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
-    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)a.res, 1, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, active, (const uint8_t *)a.flags, (size_t)n, mem));                         // (device: the kernel wrote them)
-    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
-    memcpy(res, h, sizeof(*res));
-    return SVO_OK;
+    return refine_stage_finish(ctx, a.c, n, res, active, mem);
 }
 
 // the record and the flags of pair `pair` of the last fused launch; the caller has ordered the pose stage before the context's stream
@@ -354,13 +338,8 @@ int refine_read_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *
 {
     const svo_config &c = ctx->cfg;
     svo_refine_result *h;
-    SVO_TRY(pinned_block(ctx, sizeof(*h), &h));
-    SVO_TRY(from_device(ctx, h, (const svo_refine_result *)ctx->refine_buf + pair, 1, SVO_MEM_HOST));
-    SVO_TRY(io_done(ctx, SVO_MEM_HOST));
+    SVO_TRY(refine_fetch_record(ctx, pair, active, cap, "flag capacity too small", &h, n_out));
     const int n = h->n_points;
-    SVO_ARG(n >= 0 && n <= c.max_keypoints, "corrupt point count");
-    if (n_out) *n_out = n;                                  // also when the capacity is too small: what to size `active` for
-    SVO_ARG(active == nullptr || n <= cap, "flag capacity too small");     // nothing else has been written
     if (res) memcpy(res, h, sizeof(*res));
     if (!active || n == 0) return SVO_OK;
     SVO_TRY(from_device(ctx, active, (const uint8_t *)ctx->refine_buf + refine_cut(c).flags + (size_t)pair * c.max_keypoints, (size_t)n, SVO_MEM_HOST));

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/svo_abi.h"
+#include "refine_device.h"
 
 namespace svo {
 
@@ -46,7 +47,7 @@ constexpr int kWbaRow = 10 + 18 * (kWindowMaxFrames - 1);    // doubles a landma
 struct WindowBaArgs {
     WindowTable tab;                      // poses, X and active are overwritten when the outcome is SVO_REFINE_APPLIED
     int cap;                              // rows the table and the scratch have room for
-    double ML[9], MR[9], p4R[3];          // view L: [K1 | 0]; view R: P2 = [MR | p4R]
+    StereoCam cam;
     int rounds, iters, min_obs; double sigma;
     svo_window_result *res;
     double *Xa, *Xb;                      // the accepted and the trial points, swapped by pointer: 3 x cap doubles each

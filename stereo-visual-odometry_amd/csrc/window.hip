@@ -188,7 +188,8 @@ void launch_window_update(const WindowUpdateArgs &a, hipStream_t st)
 //   wba_chol      the (up to) 42 x 42 factorisation in LDS, column by column; the two triangular solves by one lane
 //   wba_trial     back-substitution, the trial points, the cost at the trial estimate
 // Sums run in a fixed order and there are no floating-point atomics: the same input gives the same bytes (W8).
-constexpr int kWbaAcc = 48;               // sums a lane carries through one reduction
+// The per-view math, the Huber weight, the 3 x 3 elimination and the cost pair are refine_device.h's, as in refine.hip and ba.hip.
+constexpr int kWbaAcc = 48;              // sums a lane carries through one reduction
 constexpr int kWbaWaves = kWbaThreads / 64;
 constexpr double kWbaTau = 9.488;         // chi-square 95 % point, 4 degrees of freedom: one stereo observation
 
@@ -198,35 +199,13 @@ struct WbaObs { double r[4], A[4][3], Y[3]; bool proj; };
 __device__ inline void wba_eval(const WindowBaArgs &a, const double (&X)[3], const double *P, float2 ol, float2 orr, WbaObs &p)
 {
     for (int k = 0; k < 3; k++) p.Y[k] = ((X[0] * P[k * 3] + X[1] * P[k * 3 + 1]) + X[2] * P[k * 3 + 2]) + P[9 + k];
-    p.proj = true;
-#pragma unroll
-    for (int v = 0; v < 2; v++) {
-        const double *M = v ? a.MR : a.ML;
-        double h[3];
-        for (int k = 0; k < 3; k++) {
-            h[k] = (p.Y[0] * M[k * 3] + p.Y[1] * M[k * 3 + 1]) + p.Y[2] * M[k * 3 + 2];
-            if (v) h[k] = h[k] + a.p4R[k];
-        }
-        const bool ok = h[2] > kRefineMinDepth;
-        p.proj = p.proj && ok;
-        const double h2 = ok ? h[2] : 1.0;
-        const double u = h[0] / h2, w = h[1] / h2;
-        const float2 o = v ? orr : ol;
-        p.r[2 * v] = u - (double)o.x;
-        p.r[2 * v + 1] = w - (double)o.y;
-        for (int k = 0; k < 3; k++) { p.A[2 * v][k] = (M[k] - u * M[6 + k]) / h2; p.A[2 * v + 1][k] = (M[3 + k] - w * M[6 + k]) / h2; }
-    }
+    p.proj = refine_project(a.cam, false, p.Y, ol, p.r, p.A);
+    p.proj = refine_project(a.cam, true, p.Y, orr, p.r + 2, p.A + 2) && p.proj;
 }
 
 __device__ inline double wba_chi(const WbaObs &p, double s2)
 {
     return (((p.r[0] * p.r[0] + p.r[1] * p.r[1]) + p.r[2] * p.r[2]) + p.r[3] * p.r[3]) / s2;
-}
-
-__device__ inline void wba_huber(bool robust, double c, double &w, double &rho)
-{
-    w = 1.0; rho = c;
-    if (robust && c > kWbaTau) { w = sqrt(kWbaTau / c); rho = 2.0 * sqrt(kWbaTau * c) - kWbaTau; }
 }
 
 // Jx = A R (d residual / dX), Jp = A [I | -[Y]x] (d residual / d xi)
@@ -239,13 +218,7 @@ __device__ inline void wba_jx(const WbaObs &p, const double *R, double (&Jx)[4][
 __device__ inline void wba_jp(const WbaObs &p, double (&Jp)[4][6])
 {
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const double *A = p.A[k];
-        Jp[k][0] = A[0]; Jp[k][1] = A[1]; Jp[k][2] = A[2];
-        Jp[k][3] = p.Y[1] * A[2] - p.Y[2] * A[1];
-        Jp[k][4] = p.Y[2] * A[0] - p.Y[0] * A[2];
-        Jp[k][5] = p.Y[0] * A[1] - p.Y[1] * A[0];
-    }
+    for (int k = 0; k < 4; k++) refine_pose_row(p.A[k], p.Y, Jp[k]);
 }
 
 // The first K sums of every lane -> out[0 .. K), complete for every lane on return: wave butterfly, then the wave totals in
@@ -257,11 +230,7 @@ __device__ inline void wba_reduce(double (&acc)[kWbaAcc], bool pair, double *red
     __syncthreads();                                        // red and out may still be read from the previous pass
     if (pair) {
         double cs = acc[0], ce = acc[1];
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const double os = __shfl_xor(cs, m, 64), oe = __shfl_xor(ce, m, 64);
-            refine_dd_add(cs, ce, os, oe);
-        }
+        refine_wave_cost(cs, ce);
         if (lane == 0) { red[wave * kWbaAcc] = cs; red[wave * kWbaAcc + 1] = ce; }
     }
 #pragma unroll
@@ -273,10 +242,7 @@ __device__ inline void wba_reduce(double (&acc)[kWbaAcc], bool pair, double *red
     __syncthreads();
     const int k = threadIdx.x;
     if (pair && k == 0) {
-        double cs = red[0], ce = red[1];
-        for (int w = 1; w < kWbaWaves; w++) refine_dd_add(cs, ce, red[w * kWbaAcc], red[w * kWbaAcc + 1]);
-        const double hi = cs + ce;                          // normalised: hi the rounded sum, lo what is left
-        out[0] = hi; out[1] = ce - (hi - cs);
+        refine_block_cost(red, kWbaAcc, 1, kWbaWaves, out[0], out[1]);
     } else if (k < K && !(pair && k == 1)) {
         double s = red[k];
         for (int w = 1; w < kWbaWaves; w++) s += red[w * kWbaAcc + k];
@@ -335,7 +301,7 @@ __device__ void wba_build(const WindowBaArgs &a, WbaShared &sh, int n, int m, do
             WbaObs p;
             wba_eval(a, X, sh.P + f * kWindowPose, ol[f], orr[f], p);
             double w, rho, Jx[4][3];
-            wba_huber(robust, wba_chi(p, s2), w, rho);
+            refine_huber(robust, wba_chi(p, s2), kWbaTau, w, rho);
             refine_dd_add(acc[0], acc[1], rho, 0.0);
             acc[kWbaFrame + f] += 1.0;
             const double ws = w * is2;
@@ -349,34 +315,19 @@ __device__ void wba_build(const WindowBaArgs &a, WbaShared &sh, int n, int m, do
                 gx[r] += ws * (((Jx[0][r] * p.r[0] + Jx[1][r] * p.r[1]) + Jx[2][r] * p.r[2]) + Jx[3][r] * p.r[3]);
             }
         }
-        // 3 x 3 Cholesky of V + lam diag V, row by row
-        const double d0 = V[0] + lam * V[0];
-        bool ok = d0 > 0.0;
-        const double l00 = sqrt(ok ? d0 : 1.0);
-        const double l10 = V[1] / l00;
-        const double d1 = (V[2] + lam * V[2]) - l10 * l10;
-        ok = ok && d1 > 0.0;
-        const double l11 = sqrt(ok ? d1 : 1.0);
-        const double l20 = V[3] / l00;
-        const double l21 = (V[4] - l20 * l10) / l11;
-        const double d2 = ((V[5] + lam * V[5]) - l20 * l20) - l21 * l21;
-        ok = ok && d2 > 0.0;
-        const double l22 = sqrt(ok ? d2 : 1.0);
+        double L[6];
+        const bool ok = refine_chol3(V, lam, L);
         double *row = a.sys + (int64_t)i * kWbaRow;
-        row[0] = l00; row[1] = l10; row[2] = l11; row[3] = l20; row[4] = l21; row[5] = l22;
-        {
-            const double y0 = gx[0] / l00;
-            const double y1 = (gx[1] - l10 * y0) / l11;
-            const double y2 = ((gx[2] - l20 * y0) - l21 * y1) / l22;
-            row[6] = ok ? y0 : 0.0; row[7] = ok ? y1 : 0.0; row[8] = ok ? y2 : 0.0; row[9] = ok ? 1.0 : 0.0;
-        }
+        for (int k = 0; k < 6; k++) row[k] = L[k];
+        refine_fwd3(L, gx, ok, row + 6);
+        row[9] = ok ? 1.0 : 0.0;
 #pragma unroll 1
         for (int f = 1; f < n; f++) {
             if (!(am >> f & 1u)) continue;
             WbaObs p;
             wba_eval(a, X, sh.P + f * kWindowPose, ol[f], orr[f], p);
             double w, rho, Jx[4][3], Jp[4][6];
-            wba_huber(robust, wba_chi(p, s2), w, rho);
+            refine_huber(robust, wba_chi(p, s2), kWbaTau, w, rho);
             const double ws = w * is2;
             wba_jx(p, sh.P + f * kWindowPose, Jx);
             wba_jp(p, Jp);
@@ -385,10 +336,7 @@ __device__ void wba_build(const WindowBaArgs &a, WbaShared &sh, int n, int m, do
             for (int q = 0; q < 6; q++) {
                 double Wq[3];
                 for (int j = 0; j < 3; j++) Wq[j] = ws * (((Jp[0][q] * Jx[0][j] + Jp[1][q] * Jx[1][j]) + Jp[2][q] * Jx[2][j]) + Jp[3][q] * Jx[3][j]);
-                const double t0 = Wq[0] / l00;
-                const double t1 = (Wq[1] - l10 * t0) / l11;
-                const double t2 = ((Wq[2] - l20 * t0) - l21 * t1) / l22;
-                T[q * 3] = ok ? t0 : 0.0; T[q * 3 + 1] = ok ? t1 : 0.0; T[q * 3 + 2] = ok ? t2 : 0.0;
+                refine_fwd3(L, Wq, ok, T + q * 3);
             }
         }
     }
@@ -418,7 +366,7 @@ __device__ void wba_block(const WindowBaArgs &a, WbaShared &sh, int m, const dou
         WbaObs p;
         wba_eval(a, X, sh.P + f * kWindowPose, a.tab.obs_left[(int64_t)i * kWindowMaxFrames + f], a.tab.obs_right[(int64_t)i * kWindowMaxFrames + f], p);
         double w, rho, Jp[4][6];
-        wba_huber(robust, wba_chi(p, s2), w, rho);
+        refine_huber(robust, wba_chi(p, s2), kWbaTau, w, rho);
         const double ws = w * is2;
         wba_jp(p, Jp);
 #pragma unroll
@@ -520,11 +468,8 @@ __device__ void wba_trial(const WindowBaArgs &a, WbaShared &sh, int n, int m, co
                     z[j] += v;
                 }
             }
-            const double e2 = z[2] / row[5];
-            const double e1 = (z[1] - row[4] * e2) / row[2];
-            const double e0 = ((z[0] - row[1] * e1) - row[3] * e2) / row[0];
-            const bool ok = row[9] != 0.0;
-            const double dX[3] = {ok ? -e0 : 0.0, ok ? -e1 : 0.0, ok ? -e2 : 0.0};
+            double dX[3];
+            refine_back3(row, z, row[9] != 0.0, dX);
             for (int k = 0; k < 3; k++) X[k] = X[k] + dX[k];
             step = fmax(step, (dX[0] * dX[0] + dX[1] * dX[1]) + dX[2] * dX[2]);
         }
@@ -536,7 +481,7 @@ __device__ void wba_trial(const WindowBaArgs &a, WbaShared &sh, int n, int m, co
             wba_eval(a, X, sh.Pn + f * kWindowPose, a.tab.obs_left[(int64_t)i * kWindowMaxFrames + f], a.tab.obs_right[(int64_t)i * kWindowMaxFrames + f], p);
             if (!p.proj) { acc[2] += 1.0; continue; }
             double w, rho;
-            wba_huber(robust, wba_chi(p, s2), w, rho);
+            refine_huber(robust, wba_chi(p, s2), kWbaTau, w, rho);
             refine_dd_add(acc[0], acc[1], rho, 0.0);
         }
     }
@@ -672,44 +617,79 @@ __global__ __launch_bounds__(kWbaThreads) void window_ba_kernel(WindowBaArgs a)
     }
 }
 
-static void window_views(WindowBaArgs &a, const double *P1, const double *P2)
-{
-    const double ML[9] = {P1[0], 0.0, P1[2], 0.0, P1[5], P1[6], 0.0, 0.0, 1.0};
-    for (int i = 0; i < 9; i++) a.ML[i] = ML[i];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) a.MR[i * 3 + j] = P2[i * 4 + j];
-        a.p4R[i] = P2[i * 4 + 3];
-    }
-}
-
 void launch_window_ba(const WindowBaArgs &a, hipStream_t st)
 {
     hipLaunchKernelGGL(window_ba_kernel, dim3(1), dim3(kWbaThreads), 0, st, a);
+}
+
+// ---- the landmark table on the host side.  Its eight columns, in WindowTable's (and svo_window_table's) order, are defined
+// HERE and nowhere else: bytes per table and bytes per row, and one bit each for the calls that move only some of them.
+constexpr size_t kTabBytes[8][2] = {{sizeof(int) * 4, 0}, {sizeof(double) * kWindowMaxFrames * kWindowPose, 0}, {0, sizeof(long long)},
+                                    {0, sizeof(double) * 3}, {0, sizeof(uint32_t)}, {0, sizeof(uint32_t)},
+                                    {0, sizeof(float2) * kWindowMaxFrames}, {0, sizeof(float2) * kWindowMaxFrames}};
+enum : unsigned { kTabCounts = 1, kTabPoses = 2, kTabIds = 4, kTabX = 8, kTabActive = 32, kTabAll = 255 };     // bit k = column k
+struct TableCols { uint8_t *p[8]; };
+
+template <typename Table>                                     // svo_window_table or WindowTable: the same eight members
+static TableCols window_cols(const Table &t)
+{
+    return TableCols{{(uint8_t *)t.counts, (uint8_t *)t.poses, (uint8_t *)t.ids, (uint8_t *)t.X, (uint8_t *)t.seen, (uint8_t *)t.active,
+                      (uint8_t *)t.obs_left, (uint8_t *)t.obs_right}};
+}
+static WindowTable window_table_of(const TableCols &c)
+{
+    return WindowTable{(int *)c.p[0], (double *)c.p[1], (long long *)c.p[2], (double *)c.p[3], (uint32_t *)c.p[4], (uint32_t *)c.p[5],
+                       (float2 *)c.p[6], (float2 *)c.p[7]};
+}
+static size_t window_col_bytes(int k, size_t rows) { return kTabBytes[k][0] + kTabBytes[k][1] * rows; }
+
+// room for the columns `cols` of a table of `rows` rows (a column outside `cols` gets none): their offsets
+static void window_table_cut(BlockCut &cut, size_t rows, unsigned cols, size_t (&at)[8])
+{
+    for (int k = 0; k < 8; k++) at[k] = cut.add(cols >> k & 1u ? window_col_bytes(k, rows) : 0);
+}
+static WindowTable window_table_at(uint8_t *s, const size_t (&at)[8])
+{
+    TableCols c;
+    for (int k = 0; k < 8; k++) c.p[k] = s + at[k];
+    return window_table_of(c);
+}
+// the caller's columns `cols`, `rows` rows of them, into the scratch at s + at[] (HOST) or as they are (DEVICE), in column
+// order; a column outside `cols` keeps the caller's pointer
+static int window_table_in(svo_ctx *ctx, const svo_window_table &t, uint8_t *s, const size_t (&at)[8], size_t rows, unsigned cols, int mem,
+                           WindowTable *d)
+{
+    TableCols c = window_cols(t);
+    for (int k = 0; k < 8; k++) {
+        if (!(cols >> k & 1u)) continue;
+        const uint8_t *p;
+        SVO_TRY(to_device(ctx, (const uint8_t *)c.p[k], s + at[k], window_col_bytes(k, rows), mem, &p));
+        c.p[k] = (uint8_t *)p;
+    }
+    *d = window_table_of(c);
+    return SVO_OK;
+}
+// `rows` rows of the device table's columns `cols` into the caller's, in column order; a null column is left out
+static int window_table_out(svo_ctx *ctx, const svo_window_table &t, const WindowTable &d, size_t rows, unsigned cols, int mem)
+{
+    const TableCols dst = window_cols(t), src = window_cols(d);
+    for (int k = 0; k < 8; k++)
+        if (cols >> k & 1u) SVO_TRY(from_device(ctx, dst.p[k], (const uint8_t *)src.p[k], window_col_bytes(k, rows), mem));
+    return SVO_OK;
 }
 
 // ---- the fused step (svo_set_window_ba): the online chain's table, two buffers swapped per step, and both kernels on it
 struct WindowCut { size_t tab[2][8], pre_rows, pre_new, Xa, Xb, sys, act, res, end; };
 static WindowCut window_cut(int frames, int kcap)
 {
-    const size_t rows = (size_t)(frames - 1) * (size_t)kcap, F = kWindowMaxFrames;
+    const size_t rows = (size_t)(frames - 1) * (size_t)kcap;
     BlockCut cut;
     WindowCut c;
-    for (int t = 0; t < 2; t++) {
-        c.tab[t][0] = cut.add(sizeof(int) * 4); c.tab[t][1] = cut.add(sizeof(double) * F * kWindowPose);
-        c.tab[t][2] = cut.add(sizeof(long long) * rows); c.tab[t][3] = cut.add(sizeof(double) * 3 * rows);
-        c.tab[t][4] = cut.add(sizeof(uint32_t) * rows); c.tab[t][5] = cut.add(sizeof(uint32_t) * rows);
-        c.tab[t][6] = cut.add(sizeof(float2) * F * rows); c.tab[t][7] = cut.add(sizeof(float2) * F * rows);
-    }
+    for (int t = 0; t < 2; t++) window_table_cut(cut, rows, kTabAll, c.tab[t]);
     c.pre_rows = cut.add(sizeof(int) * (rows + 1)); c.pre_new = cut.add(sizeof(int) * ((size_t)kcap + 1));
     c.Xa = cut.add(sizeof(double) * 3 * rows); c.Xb = cut.add(sizeof(double) * 3 * rows); c.sys = cut.add(sizeof(double) * kWbaRow * rows);
     c.act = cut.add(sizeof(uint32_t) * rows); c.res = cut.add(sizeof(svo_window_result)); c.end = cut.total();
     return c;
-}
-
-static WindowTable window_table_at(uint8_t *s, const size_t (&at)[8])
-{
-    return WindowTable{(int *)(s + at[0]), (double *)(s + at[1]), (long long *)(s + at[2]), (double *)(s + at[3]), (uint32_t *)(s + at[4]),
-                       (uint32_t *)(s + at[5]), (float2 *)(s + at[6]), (float2 *)(s + at[7])};
 }
 
 int window_alloc(svo_ctx *ctx, int frames)
@@ -740,7 +720,7 @@ int window_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
     timing_mark(ctx, "win_update");
     WindowBaArgs b{};
     b.tab = u.out; b.cap = u.cap;
-    window_views(b, ctx->cfg.P1, ctx->cfg.P2);
+    b.cam = stereo_cam(ctx->cfg.P1, ctx->cfg.P2);
     b.rounds = ctx->win_rounds; b.iters = ctx->win_iters; b.min_obs = ctx->win_min_obs; b.sigma = ctx->win_sigma;
     b.Xa = (double *)(s + c.Xa); b.Xb = (double *)(s + c.Xb); b.sys = (double *)(s + c.sys); b.act = (uint32_t *)(s + c.act);
     b.res = (svo_window_result *)(s + c.res);
@@ -756,20 +736,12 @@ int window_read(svo_ctx *ctx, const svo_window_table *out, int cap)
 {
     const WindowCut c = window_cut(ctx->win_last_frames, ctx->cfg.max_keypoints);
     const WindowTable t = window_table_at(ctx->win_block.base, c.tab[ctx->win_cur]);
-    const size_t F = kWindowMaxFrames;
-    SVO_TRY(from_device(ctx, (int *)out->counts, (const int *)t.counts, (size_t)4, SVO_MEM_HOST));
+    SVO_TRY(window_table_out(ctx, *out, t, 0, kTabCounts, SVO_MEM_HOST));
     SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     const int m = out->counts[1];
     if (!out->ids && !out->X && !out->seen && !out->active && !out->obs_left && !out->obs_right && !out->poses) return SVO_OK;
     SVO_ARG(m <= cap, "row capacity too small");
-    const size_t mo = (size_t)m;
-    SVO_TRY(from_device(ctx, out->poses, (const double *)t.poses, F * kWindowPose, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, (long long *)out->ids, (const long long *)t.ids, mo, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, out->X, (const double *)t.X, 3 * mo, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, out->seen, (const uint32_t *)t.seen, mo, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, out->active, (const uint32_t *)t.active, mo, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, (float2 *)out->obs_left, (const float2 *)t.obs_left, F * mo, SVO_MEM_HOST));
-    SVO_TRY(from_device(ctx, (float2 *)out->obs_right, (const float2 *)t.obs_right, F * mo, SVO_MEM_HOST));
+    SVO_TRY(window_table_out(ctx, *out, t, (size_t)m, kTabAll & ~kTabCounts, SVO_MEM_HOST));
     return io_done(ctx, SVO_MEM_HOST);
 }
 
@@ -801,17 +773,12 @@ int stage_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, co
         SVO_ARG(in->counts[1] >= 0 && in->counts[1] <= cap, "the table holds more rows than `cap`");
         m_in = in->counts[0] > 0 ? (size_t)in->counts[1] : 0;
     }
-    const size_t nt = (size_t)n_trk, nc = (size_t)cap, F = kWindowMaxFrames, hm = host ? m_in : 0, hc = host ? nc : 0, ht = host ? nt : 0;
+    const size_t nt = (size_t)n_trk, nc = (size_t)cap, hm = host ? m_in : 0, ht = host ? nt : 0;
     BlockCut cut;
     const size_t s_rows = cut.add(sizeof(int) * (nc + 1)), s_new = cut.add(sizeof(int) * (nt + 1));
-    size_t at[2][8];                                          // the two tables' columns, in WindowTable's order
-    for (int t = 0; t < 2; t++) {
-        const size_t rows = t == 0 ? hm : hc;
-        at[t][0] = cut.add(host ? sizeof(int) * 4 : 0); at[t][1] = cut.add(host ? sizeof(double) * F * kWindowPose : 0);
-        at[t][2] = cut.add(sizeof(long long) * rows); at[t][3] = cut.add(sizeof(double) * 3 * rows);
-        at[t][4] = cut.add(sizeof(uint32_t) * rows); at[t][5] = cut.add(sizeof(uint32_t) * rows);
-        at[t][6] = cut.add(sizeof(float2) * F * rows); at[t][7] = cut.add(sizeof(float2) * F * rows);
-    }
+    size_t at[2][8];                                          // HOST: the two tables' scratch, m_in and cap rows
+    window_table_cut(cut, hm, host ? kTabAll : 0u, at[0]);
+    window_table_cut(cut, nc, host ? kTabAll : 0u, at[1]);
     const size_t i_t1l = cut.add(sizeof(float2) * ht), i_t1r = cut.add(sizeof(float2) * ht), i_t2l = cut.add(sizeof(float2) * ht),
                  i_t2r = cut.add(sizeof(float2) * ht), i_ids = cut.add(sizeof(long long) * ht), i_tri = cut.add(sizeof(float) * 3 * ht),
                  i_pa = cut.add(host ? sizeof(double) * 16 : 0), i_pb = cut.add(host ? sizeof(double) * 16 : 0);
@@ -821,23 +788,8 @@ int stage_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, co
     WindowUpdateArgs a{};
     a.frames = frames; a.cap = cap; a.n_trk = n_trk;
     a.pre_rows = (int *)(s + s_rows); a.pre_new = (int *)(s + s_new);
-    const int *c_counts; const double *c_poses, *c_X; const long long *c_ids; const uint32_t *c_seen, *c_active; const float2 *c_l, *c_r;
-    SVO_TRY(to_device(ctx, (const int *)in->counts, (int *)(s + at[0][0]), (size_t)4, mem, &c_counts));
-    SVO_TRY(to_device(ctx, (const double *)in->poses, (double *)(s + at[0][1]), F * kWindowPose, mem, &c_poses));
-    SVO_TRY(to_device(ctx, (const long long *)in->ids, (long long *)(s + at[0][2]), hm, mem, &c_ids));
-    SVO_TRY(to_device(ctx, (const double *)in->X, (double *)(s + at[0][3]), 3 * hm, mem, &c_X));
-    SVO_TRY(to_device(ctx, (const uint32_t *)in->seen, (uint32_t *)(s + at[0][4]), hm, mem, &c_seen));
-    SVO_TRY(to_device(ctx, (const uint32_t *)in->active, (uint32_t *)(s + at[0][5]), hm, mem, &c_active));
-    SVO_TRY(to_device(ctx, (const float2 *)in->obs_left, (float2 *)(s + at[0][6]), F * hm, mem, &c_l));
-    SVO_TRY(to_device(ctx, (const float2 *)in->obs_right, (float2 *)(s + at[0][7]), F * hm, mem, &c_r));
-    a.in = WindowTable{(int *)c_counts, (double *)c_poses, (long long *)c_ids, (double *)c_X, (uint32_t *)c_seen, (uint32_t *)c_active,
-                       (float2 *)c_l, (float2 *)c_r};
-    if (host)
-        a.out = WindowTable{(int *)(s + at[1][0]), (double *)(s + at[1][1]), (long long *)(s + at[1][2]), (double *)(s + at[1][3]),
-                            (uint32_t *)(s + at[1][4]), (uint32_t *)(s + at[1][5]), (float2 *)(s + at[1][6]), (float2 *)(s + at[1][7])};
-    else
-        a.out = WindowTable{(int *)out->counts, out->poses, (long long *)out->ids, out->X, out->seen, out->active, (float2 *)out->obs_left,
-                            (float2 *)out->obs_right};
+    SVO_TRY(window_table_in(ctx, *in, s, at[0], hm, kTabAll, mem, &a.in));
+    a.out = host ? window_table_at(s, at[1]) : window_table_of(window_cols(*out));
     SVO_TRY(to_device(ctx, (const float2 *)t1_left, (float2 *)(s + i_t1l), nt, mem, &a.t1_left));
     SVO_TRY(to_device(ctx, (const float2 *)t1_right, (float2 *)(s + i_t1r), nt, mem, &a.t1_right));
     SVO_TRY(to_device(ctx, (const float2 *)t2_left, (float2 *)(s + i_t2l), nt, mem, &a.t2_left));
@@ -854,14 +806,7 @@ int stage_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, co
     SVO_TRY(counts_wait(ctx, &h));
     for (int k = 0; k < 4; k++) out->counts[k] = h[k];
     if (h[2] > cap) { ctx->err = "bad argument: cap is too small for the updated table (rows needed: " + std::to_string(h[2]) + ")"; return SVO_ERR_ARG; }
-    const size_t mo = (size_t)h[1];
-    SVO_TRY(from_device(ctx, out->poses, (const double *)a.out.poses, F * kWindowPose, mem));
-    SVO_TRY(from_device(ctx, (long long *)out->ids, (const long long *)a.out.ids, mo, mem));
-    SVO_TRY(from_device(ctx, out->X, (const double *)a.out.X, 3 * mo, mem));
-    SVO_TRY(from_device(ctx, out->seen, (const uint32_t *)a.out.seen, mo, mem));
-    SVO_TRY(from_device(ctx, out->active, (const uint32_t *)a.out.active, mo, mem));
-    SVO_TRY(from_device(ctx, (float2 *)out->obs_left, (const float2 *)a.out.obs_left, F * mo, mem));
-    SVO_TRY(from_device(ctx, (float2 *)out->obs_right, (const float2 *)a.out.obs_right, F * mo, mem));
+    SVO_TRY(window_table_out(ctx, *out, a.out, (size_t)h[1], kTabAll & ~kTabCounts, mem));
     return io_done(ctx, mem);
 }
 
@@ -884,39 +829,28 @@ int stage_window_ba(svo_ctx *ctx, const svo_window_table *tab, int cap, const do
         SVO_ARG(tab->counts[1] >= 0 && tab->counts[1] <= cap, "the table holds more rows than `cap`");
         hm = (size_t)tab->counts[1];
     }
-    const size_t nc = (size_t)cap, F = kWindowMaxFrames;
+    const size_t nc = (size_t)cap;
+    const unsigned read = kTabAll & ~kTabIds;                 // the optimiser does not read the ids
     BlockCut cut;
     const size_t s_xa = cut.add(sizeof(double) * 3 * nc), s_xb = cut.add(sizeof(double) * 3 * nc), s_sys = cut.add(sizeof(double) * kWbaRow * nc),
-                 s_act = cut.add(sizeof(uint32_t) * nc), s_res = cut.add(host ? sizeof(svo_window_result) : 0),
-                 i_cnt = cut.add(host ? sizeof(int) * 4 : 0), i_pose = cut.add(host ? sizeof(double) * F * kWindowPose : 0),
-                 i_X = cut.add(sizeof(double) * 3 * hm), i_seen = cut.add(sizeof(uint32_t) * hm), i_active = cut.add(sizeof(uint32_t) * hm),
-                 i_l = cut.add(sizeof(float2) * F * hm), i_r = cut.add(sizeof(float2) * F * hm);
+                 s_act = cut.add(sizeof(uint32_t) * nc), s_res = cut.add(host ? sizeof(svo_window_result) : 0);
+    size_t at[8];
+    window_table_cut(cut, hm, host ? read : 0u, at);
     SVO_HIP(hipSetDevice(ctx->device));
     if (dev_reserve(ctx, &ctx->window_ba_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
     uint8_t *s = ctx->window_ba_stage.base;
     WindowBaArgs a{};
     a.cap = cap;
-    window_views(a, P1, P2);
+    a.cam = stereo_cam(P1, P2);
     a.rounds = rounds; a.iters = iters; a.min_obs = min_obs; a.sigma = sigma_px;
     a.Xa = (double *)(s + s_xa); a.Xb = (double *)(s + s_xb); a.sys = (double *)(s + s_sys); a.act = (uint32_t *)(s + s_act);
     a.res = host ? (svo_window_result *)(s + s_res) : res;
-    const int *c_counts; const double *c_poses, *c_X; const uint32_t *c_seen, *c_active; const float2 *c_l, *c_r;
-    SVO_TRY(to_device(ctx, (const int *)tab->counts, (int *)(s + i_cnt), (size_t)4, mem, &c_counts));
-    SVO_TRY(to_device(ctx, (const double *)tab->poses, (double *)(s + i_pose), F * kWindowPose, mem, &c_poses));
-    SVO_TRY(to_device(ctx, (const double *)tab->X, (double *)(s + i_X), 3 * hm, mem, &c_X));
-    SVO_TRY(to_device(ctx, (const uint32_t *)tab->seen, (uint32_t *)(s + i_seen), hm, mem, &c_seen));
-    SVO_TRY(to_device(ctx, (const uint32_t *)tab->active, (uint32_t *)(s + i_active), hm, mem, &c_active));
-    SVO_TRY(to_device(ctx, (const float2 *)tab->obs_left, (float2 *)(s + i_l), F * hm, mem, &c_l));
-    SVO_TRY(to_device(ctx, (const float2 *)tab->obs_right, (float2 *)(s + i_r), F * hm, mem, &c_r));
-    a.tab = WindowTable{(int *)c_counts, (double *)c_poses, (long long *)tab->ids /* not read */, (double *)c_X, (uint32_t *)c_seen,
-                        (uint32_t *)c_active, (float2 *)c_l, (float2 *)c_r};
+    SVO_TRY(window_table_in(ctx, *tab, s, at, hm, read, mem, &a.tab));
     launch_window_ba(a, ctx->stream);
     SVO_HIP(hipGetLastError());
     if (!host) return SVO_OK;
     SVO_TRY(from_device(ctx, res, (const svo_window_result *)a.res, (size_t)1, mem));
-    SVO_TRY(from_device(ctx, tab->poses, (const double *)a.tab.poses, F * kWindowPose, mem));
-    SVO_TRY(from_device(ctx, tab->X, (const double *)a.tab.X, 3 * hm, mem));
-    SVO_TRY(from_device(ctx, tab->active, (const uint32_t *)a.tab.active, hm, mem));
+    SVO_TRY(window_table_out(ctx, *tab, a.tab, hm, kTabPoses | kTabX | kTabActive, mem));
     return io_done(ctx, mem);
 }
 
