@@ -170,7 +170,7 @@ __device__ void ba_build(const BaArgs &a, const BaItem &it, double *Xc, const do
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __syncthreads();                                        // `red` and S may still be read from the previous pass
     for (int k = 1; k <= kBaCount; k++) {
-        const double ws = refine_wave_allsum(acc[k]);
+        const double ws = wave_allsum_f64(acc[k]);
         if (lane == 0) red[wave * kBaAcc + k] = ws;
     }
     refine_wave_cost(acc[0], acc[kBaCostLo]);
@@ -227,7 +227,7 @@ __device__ void ba_trial(const BaArgs &a, const BaItem &it, const double *Xc, do
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __syncthreads();
-    bad = refine_wave_allsum(bad);
+    bad = wave_allsum_f64(bad);
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) step = fmax(step, __shfl_xor(step, m, 64));
     if (lane == 0) { red[wave * kBaAcc + kBaBad] = bad; red[wave * kBaAcc + kBaStep] = step; }

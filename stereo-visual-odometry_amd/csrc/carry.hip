@@ -13,28 +13,9 @@
 // stable order through ballot-free block scans.  Nothing here is tuned: the kernel runs once per step on a few thousand
 // points.
 #include "carry.h"
+#include "svo_device.h"
 
 namespace svo {
-
-// exclusive prefix of v over the workgroup's 1024 lanes; total: the sum.  (two barriers)
-__device__ inline int carry_scan(int v, int *wave_tot, int &total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) wave_tot[wv] = inc;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) { const int t = wave_tot[k]; if (k < wv) pre += t; tot += t; }
-    __syncthreads();
-    total = tot;
-    return pre + inc - v;
-}
 
 __device__ inline bool carry_near(float2 a, float2 b, double min_d2)
 {
@@ -93,7 +74,7 @@ __global__ __launch_bounds__(1024) void carry_merge_kernel(CarryMergeArgs a)
 #pragma unroll
         for (int k = 0; k < 4; k++) { const int c = 4 * tid + k; v[k] = c < ncells ? cell_end[c] : 0; sum += v[k]; }
         int total;
-        int run = carry_scan(sum, wave_tot, total);
+        int run = block1024_excl_scan(sum, wave_tot, total);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int c = 4 * tid + k;
@@ -151,8 +132,8 @@ __global__ __launch_bounds__(1024) void carry_merge_kernel(CarryMergeArgs a)
         const bool in = i < n_p;
         const bool c = in && flag[i] == 2, k = in && keep[i] != 0;
         int tot_c, tot_k;
-        const int rc = carry_scan(c ? 1 : 0, wave_tot, tot_c);
-        const int rk = carry_scan(k ? 1 : 0, wave_tot, tot_k);
+        const int rc = block1024_excl_scan(c ? 1 : 0, wave_tot, tot_c);
+        const int rk = block1024_excl_scan(k ? 1 : 0, wave_tot, tot_k);
         if (k || c) {
             const long long id = fresh ? id0 + i : a.p_id[o + i];
             const int age = fresh ? 0 : a.p_age[o + i];
@@ -172,7 +153,7 @@ __global__ __launch_bounds__(1024) void carry_merge_kernel(CarryMergeArgs a)
         const int k = start + tid;
         const bool kp = k < n_d && dflag[k] != 0;
         int tot;
-        const int r = carry_scan(kp ? 1 : 0, wave_tot, tot);
+        const int r = block1024_excl_scan(kp ? 1 : 0, wave_tot, tot);
         const int dst = n_carried + n_kept + r;
         if (kp && dst < a.out_cap) {
             a.o_xy[o + dst] = s_dxy[k]; a.o_resp[o + dst] = s_dresp[k];

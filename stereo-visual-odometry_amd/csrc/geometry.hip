@@ -129,13 +129,6 @@ struct PnpArgs {
     double *hand;                                           // EPnP hand-over records: per item kPhaseBlocks x 105 x 64 doubles (pnp_hyp_body)
 };
 
-__device__ inline double wave_allsum_f64(double v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
 // cv::RNG draws for RANSACPointSetRegistrator::getSubset.  The generator is a serial chain
 // (multiply-with-carry) and the number of draws per subset depends on the data (a duplicate index is
 // redrawn), so subsets are drawn by ONE wave, and everything is kept wave-uniform: the compiler

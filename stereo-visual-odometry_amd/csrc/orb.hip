@@ -8,7 +8,8 @@
 // off), so keypoints, angles, descriptors and matches are bit-identical to oracle/orb.c.
 //
 // Launch sequence for a batch of images (every kernel covers all images of the batch):
-//   [copy0 -- only where level 0 cannot be read in place from the input frames] -> resize(l) x7 (row-streaming) -> blur (all
+//   [copy0 -- only where level 0 cannot be read in place from the input frames] -> resize(l) x7 (row-streaming; a scale
+//   factor outside (1, 2]: resize.hip's table-driven kernel) -> blur (all
 //   levels) -> cellfast (all levels) -> gather -> distribute -> orient+describe -> assemble.  (No frame is written around the ORB levels: the blur, its only
 //   reader, reflects at the edges itself.)
 // The quadtree (std::list / sort / pointer code in the reference) is restated as an array-based
@@ -74,83 +75,13 @@ __device__ __forceinline__ int level_of_block(const int *first, int nlevels, int
     return l;
 }
 
-// cv::resize(level l-1 -> level l, INTER_LINEAR), 8-bit fixed point (11-bit coefficients)
-// cv::resize(INTER_LINEAR) of level l-1 into level l (ComputePyramid, ORBextractor.cpp:1061-1085).
-// The per-column (sx, alpha) and per-row (sy0, sy1, beta) tables are built once on the host
-// (orb_make_tables: upstream builds the same tables per call), so a thread is four byte loads and
-// the 11-bit fixed-point blend; four output pixels per thread, one dword store.
-constexpr int kResizeRows = 6;               // output rows per workgroup
-// A workgroup produces a 1024-pixel-wide strip of kResizeRows output rows: the source rows they
-// sample (kResizeRows * scale + 2 of them) are staged ONCE as aligned dwords (the byte gathers of a
-// 1.2x resample would otherwise be 16 scattered loads per thread and row), a thread keeps its four
-// columns' table entries in registers for all rows.  One row per workgroup (the first version) was
-// bound by workgroup turnaround: 1.4 M short workgroups per 256 pairs, each load -> barrier -> blend.
-// The LDS image is sized for THIS level's scale (11 KB at 1.2): in overlap mode the previous batch's
-// EPnP workgroups hold 147 of a CU's 160 KB, and a resize workgroup has to fit beside them.
-__global__ __launch_bounds__(256) void orb_resize_kernel(OrbGeom g, uint8_t *slots, int64_t slot_stride, int l,
-                                                         const int2 *xtab, const int4 *ytab, int src_rows_cap, int kResizeDw, OrbL0 z)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t rs_rows[];       // src_rows_cap x kResizeDw
-    const int b = blockIdx.z, tid = threadIdx.x;
-    const bool in_place = l == 1 && z.img != nullptr;                 // level 0 = the input image itself
-    const int dw = g.w[l], dh = g.h[l], sp = in_place ? z.pitch : g.pitch[l - 1];
-    const int dy0 = blockIdx.y * kResizeRows, dy1 = min(dy0 + kResizeRows, dh);
-    const int dx_first = blockIdx.x * 1024, dx_last = min(dx_first + 1023, dw - 1);
-    uint8_t *slot = slots + (int64_t)b * slot_stride;
-    const uint8_t *src = in_place ? orb_level0(z, b) : slot + g.origin[l - 1];
-    const int2 *xt = xtab + g.xtab_off[l];
-    const int4 *yt = ytab + g.ytab_off[l];
-    // source rows [sy_first, sy_last] (the table's rows are monotone), columns [s0, s0 + 4 ndw)
-    const int sy_first = yt[dy0].x, sy_last = yt[dy1 - 1].y;
-    const int nsrc = sy_last - sy_first + 1;
-    // staged as 16-byte chunks (pixel (0,0) of a level and its pitch are 16-byte aligned; kResizeDw is a multiple of 4):
-    // four times the bytes in flight per load of the dword version, which left level 1 (whose source comes from HBM)
-    // at 1.5 TB/s
-    const int s0 = (xt[dx_first].x & 0xFFFF) & ~15;
-    const int ndw = ((((xt[dx_last].x >> 16) - s0) >> 4) + 1) << 2;
-    const bool staged = ndw <= kResizeDw && nsrc <= src_rows_cap;
-    if (staged) {
-        const int n16 = ndw >> 2;
-        const float inv_n16 = 1.0f / (float)n16;
-        for (int i = tid; i < nsrc * n16; i += 256) {
-            const int r = (int)(((float)i + 0.5f) * inv_n16), c = i - r * n16;
-            *(uint4 *)(rs_rows + r * kResizeDw + 4 * c) = *(const uint4 *)(src + (int64_t)(sy_first + r) * sp + s0 + 16 * c);
-        }
-        __syncthreads();
-    }
-    const int dx0 = dx_first + tid * 4;
-    if (dx0 >= dw) return;
-    int sx[4], sx1[4], a0[4], a1[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int2 t = xt[min(dx0 + q, dw - 1)];                    // sx | sx1 << 16, a0 | a1 << 16
-        sx[q] = t.x & 0xFFFF; sx1[q] = t.x >> 16; a0[q] = (short)(t.y & 0xFFFF); a1[q] = t.y >> 16;
-    }
-    for (int dy = dy0; dy < dy1; dy++) {
-        const int4 ty = yt[dy];                                     // y0, y1, b0, b1
-        uint32_t out = 0;
-        auto blend = [&](const auto *R0, const auto *R1, int base) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int r0 = R0[sx[q] - base] * a0[q] + R0[sx1[q] - base] * a1[q];
-                const int r1 = R1[sx[q] - base] * a0[q] + R1[sx1[q] - base] * a1[q];
-                out |= (uint32_t)((((ty.z * (r0 >> 4)) >> 16) + ((ty.w * (r1 >> 4)) >> 16) + 2) >> 2) << (8 * q);
-            }
-        };
-        if (staged)
-            blend((const uint8_t *)(rs_rows + (ty.x - sy_first) * kResizeDw), (const uint8_t *)(rs_rows + (ty.y - sy_first) * kResizeDw), s0);
-        else
-            blend(src + (int64_t)ty.x * sp, src + (int64_t)ty.y * sp, 0);
-        uint8_t *d = slot + g.origin[l] + (int64_t)dy * g.pitch[l] + dx0;       // origin and pitch are 4-byte aligned
-        if (dx0 + 4 <= dw) *(uint32_t *)d = out;
-        else for (int q = 0; dx0 + q < dw; q++) d[q] = (uint8_t)(out >> (8 * q));
-    }
-}
-
-// The same resize with the source rows STREAMED through registers (round 5; the staged kernel above stays for scale
-// factors this one does not cover, OrbGeom::rs_stream).  cv::resize's linear path is two passes -- every source row is
+// cv::resize(INTER_LINEAR) of level l-1 into level l (ComputePyramid, ORBextractor.cpp:1061-1085), 8-bit fixed point with
+// 11-bit coefficients.  The per-column (sx, alpha) and per-row (sy0, sy1, beta) tables are built once on the host
+// (resize_linear_tables, resize.hip: upstream builds the same tables per call).  The source rows are STREAMED through
+// registers; for scale factors this kernel does not cover (OrbGeom::rs_stream) a level comes from resize.hip's table-driven
+// LDS-staged kernel instead (orb_extract_batch).  cv::resize's linear path is two passes -- every source row is
 // blended horizontally ONCE into an int row, an output row blends two of those vertically --, and at a scale of 1.2 a
-// source row serves 1.67 output rows: the staged kernel redid the horizontal blend for both rows of every output row
+// source row serves 1.67 output rows: a staged kernel redoes the horizontal blend for both rows of every output row
 // (4 LDS byte reads + 4 multiplies per pixel).  Here a lane owns four output columns and walks down a band of output
 // rows: per SOURCE row three aligned dwords (the 8-byte window from its first source column holds every tap of its four
 // pixels while sx1[3] - sx[0] <= 7), two v_alignbyte to normalise the alignment, per pixel one v_perm (the two taps as
@@ -2206,38 +2137,10 @@ int orb_make_geom(const svo_config &cfg, OrbGeom *g)
     return SVO_OK;
 }
 
-// cv::resize's coordinate / weight tables for every level l >= 1 (INTER_LINEAR, 11-bit weights;
-// scale = 1 / (dst / src): CANONICAL O3).  x: clamp as upstream's xofs/alpha loop does, y: rows
-// clamped to the source like upstream's vertical pass.
-void orb_make_tables(const OrbGeom &g, std::vector<int2> &xt, std::vector<int4> &yt)
-{
-    xt.assign((size_t)g.xtab_total, make_int2(0, 0));
-    yt.assign((size_t)g.ytab_total, make_int4(0, 0, 0, 0));
-    for (int l = 1; l < g.nlevels; l++) {
-        const int dw = g.w[l], dh = g.h[l], sw = g.w[l - 1], sh = g.h[l - 1];
-        const double inv_sx = (double)dw / sw, inv_sy = (double)dh / sh;
-        const double scale_x = 1. / inv_sx, scale_y = 1. / inv_sy;
-        for (int dx = 0; dx < dw; dx++) {
-            float fx = (float)((dx + 0.5) * scale_x - 0.5);
-            int sx = (int)floorf(fx);
-            fx -= sx;
-            if (sx < 0) { fx = 0; sx = 0; }
-            if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-            const int a0 = (short)lrintf((1.f - fx) * 2048), a1 = (short)lrintf(fx * 2048);
-            const int sx1 = sx + 1 < sw ? sx + 1 : sx;
-            xt[(size_t)g.xtab_off[l] + dx] = make_int2(sx | (sx1 << 16), (a0 & 0xFFFF) | (a1 << 16));
-        }
-        for (int dy = 0; dy < dh; dy++) {
-            float fy = (float)((dy + 0.5) * scale_y - 0.5);
-            int sy = (int)floorf(fy);
-            fy -= sy;
-            const int b0 = (short)lrintf((1.f - fy) * 2048), b1 = (short)lrintf(fy * 2048);
-            const int y0 = sy < 0 ? 0 : (sy >= sh ? sh - 1 : sy);
-            const int y1 = sy + 1 < 0 ? 0 : (sy + 1 >= sh ? sh - 1 : sy + 1);
-            yt[(size_t)g.ytab_off[l] + dy] = make_int4(y0, y1, b0, b1);
-        }
-    }
-}
+// LDS a workgroup of the staged resize kernel (resize.hip) may ask for on a pyramid level.  In overlap mode the previous
+// batch's EPnP workgroups hold 147 of a CU's 160 KB, and a resize workgroup has to fit beside them: 12 KB, which is also below
+// what the kernel this one replaced asked for at the default scale factor (12.6 KB on every level at 1.2).
+constexpr size_t kOrbResizeLdsBytes = 12 * 1024;
 
 // Which levels the row-streaming resize kernel covers: every group of four output columns must find its taps inside the
 // 8-byte window from its first source column, the weights must be non-negative 11-bit values, and the second source row of
@@ -2312,10 +2215,17 @@ int orb_alloc(svo_ctx *ctx)
     SVO_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), svo_bit_pattern_31, 1024));
 #define DA(ptr, bytes) do { if (dev_alloc(ctx, &(ptr), (bytes)) != SVO_OK) return SVO_ERR_HIP; } while (0)
     {
-        std::vector<int2> xt; std::vector<int4> yt;
-        orb_make_tables(g, xt, yt);
+        // cv::resize's tables for every level l >= 1, inv = dst / src (CANONICAL O3), and the staged kernel's shape for them
+        std::vector<int2> xt((size_t)g.xtab_total, make_int2(0, 0));
+        std::vector<int4> yt((size_t)g.ytab_total, make_int4(0, 0, 0, 0));
+        for (int l = 1; l < L; l++) {
+            int2 *x = xt.data() + g.xtab_off[l];
+            int4 *y = yt.data() + g.ytab_off[l];
+            resize_linear_tables(g.w[l - 1], g.h[l - 1], g.w[l], g.h[l], (double)g.w[l] / g.w[l - 1], (double)g.h[l] / g.h[l - 1], x, y);
+            ctx->orb_resize_shape[l] = resize_shape(SVO_INTERP_LINEAR, g.w[l], g.h[l], x, y, kOrbResizeLdsBytes);
+        }
         orb_resize_stream_levels(g, xt, yt);
-        ctx->orb_resize_staged = getenv("SVO_ORB_RESIZE_STAGED") != nullptr;      // the round-4 kernel, for A/B measurements and its test
+        ctx->orb_resize_staged = getenv("SVO_ORB_RESIZE_STAGED") != nullptr;      // resize.hip's staged kernel on every level (A/B measurements, its tests)
         ctx->orb_copy_level0 = getenv("SVO_ORB_COPY_LEVEL0") != nullptr;          // level 0 always copied into the slot (A/B, its test)
         DA(ctx->orb_xtab, sizeof(int2) * (xt.size() + 1));
         DA(ctx->orb_ytab, sizeof(int4) * (yt.size() + 1));
@@ -2413,14 +2323,16 @@ int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int
                                    (const int2 *)ctx->orb_xtab, (const int4 *)ctx->orb_ytab, n, gx, gy, band, z);
                 continue;
             }
-            // source rows a strip of kResizeRows output rows can touch (+3: second tap, rounding), and the
-            // dwords 1024 output columns can span (+3: second tap, alignment slack)
-            int cap_rows = (int)((double)kResizeRows * g.h[l - 1] / g.h[l]) + 3;
-            int row_dw = (((int)(1024.0 * g.w[l - 1] / g.w[l] / 4.0) + 3 + 4) + 3) & ~3;     // + the 16-byte alignment slack, multiple of 4
-            if ((size_t)cap_rows * row_dw * 4 > 60 * 1024) cap_rows = 60 * 1024 / (row_dw * 4);     // beyond it: the unstaged path
-            hipLaunchKernelGGL(orb_resize_kernel, dim3((g.w[l] + 1023) / 1024, (g.h[l] + kResizeRows - 1) / kResizeRows, n), blk,
-                               (size_t)cap_rows * row_dw * 4, st, g, sl, g.slot_bytes, l,
-                               (const int2 *)ctx->orb_xtab, (const int4 *)ctx->orb_ytab, cap_rows, row_dw, z);
+            // resize.hip's table-driven kernel, one launch (at most 65535 images: its grid.z); an in-place level 0 is its
+            // two eyes' frames, every other source the slots' level l - 1
+            const bool l0 = l == 1 && z.img, eyes2 = l0 && z.img2;
+            const uint8_t *s0 = l0 ? z.img : sl + g.origin[l - 1], *s1 = eyes2 ? z.img2 : nullptr;
+            uint8_t *d0 = sl + g.origin[l], *d1 = eyes2 ? d0 + g.slot_bytes : nullptr;
+            const int rc = resize_launch_tab(ctx, ctx->orb_resize_shape[l], SVO_INTERP_LINEAR, (const int2 *)ctx->orb_xtab + g.xtab_off[l],
+                                             (const int4 *)ctx->orb_ytab + g.ytab_off[l], g.w[l], g.h[l], s0, s1, l0 ? z.pitch : g.pitch[l - 1],
+                                             l0 ? z.stride : g.slot_bytes, d0, d1, g.pitch[l], eyes2 ? 2 * g.slot_bytes : g.slot_bytes,
+                                             eyes2 ? n / 2 : n, st);
+            if (rc) return rc;
         }
         // the blurred levels only depend on the pyramid: computed here, before the LDS-hungry kernels,
         // so that in overlap mode the previous batch's pose solver (74 KB of LDS per workgroup) runs

@@ -4,7 +4,7 @@
 // DESIGN.md section 5e; tests/_refine_ref.py is its numpy twin, and the expressions below keep its order of operations.
 //
 // pose_refine_kernel: ONE workgroup of four waves per pair.  Lanes stride the pair's points; every lane keeps 21 + 6 + 1
-// double partial sums (upper triangle of H, g, active count) and the cost as a pair; a wave reduction (refine_wave_allsum) and
+// double partial sums (upper triangle of H, g, active count) and the cost as a pair; a wave reduction (wave_allsum_f64) and
 // a fixed-order sum of the four wave totals through LDS give EVERY thread the same numbers, so the 6 x 6 Cholesky solve, the SE(3) update and all the
 // accept / reject / round decisions are computed redundantly in registers and the control flow is workgroup-uniform: three
 // barriers per evaluation, none per solve.  The stage is a chain of about rounds x iters dependent evaluate-and-solve steps of
@@ -95,7 +95,7 @@ __device__ void refine_pass(const RefineArgs &a, const float *X3, const float2 *
     __syncthreads();                                        // `red` and S may still be read from the previous pass
     for (int k = 1; k < kRefAcc; k++) {
         if (k == kRefCostLo) continue;
-        const double ws = refine_wave_allsum(acc[k]);
+        const double ws = wave_allsum_f64(acc[k]);
         if (lane == 0) red[wave * kRefAcc + k] = ws;
     }
     double cs = acc[0], ce = acc[kRefCostLo];

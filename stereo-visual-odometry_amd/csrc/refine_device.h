@@ -1,6 +1,6 @@
 // refine_device.h -- what the three Levenberg-Marquardt optimisers share (refine.hip: pose_refine_kernel; ba.hip: pose_ba_kernel;
 // window.hip: window_ba_kernel).  All three: the stereo rig, one view of one point (projection, residual, derivative rows), the
-// pose-derivative row, the Huber weight, a point's 3 x 3 Cholesky elimination, the wave butterfly and the pair-valued cost, the
+// pose-derivative row, the Huber weight, a point's 3 x 3 Cholesky elimination, the pair-valued cost and its wave butterfly (the plain one: wave_allsum_f64, svo_device.h), the
 // small SO(3) / SE(3) helpers.  The two-frame kernels also: the 6 x 6 Cholesky solve every thread runs redundantly, the common
 // part of their arguments (RefineCommon), the cut of the stage's device block and the host plumbing around a launch (defined
 // in refine.hip).  The LM loops and the kernels' prologues and epilogues stay in the kernels.  Internal.
@@ -13,13 +13,6 @@ namespace svo {
 
 constexpr int kRefineThreads = 256;
 constexpr double kRefineMinDepth = 1e-6;
-
-__device__ inline double refine_wave_allsum(double v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
 
 // The cost of a round is carried as an unevaluated pair (s, e): TwoSum keeps what every addition rounds away.  "The cost
 // decreases" (R6) is decided on the pair, so the decision does not depend on the order the lanes add in (a plain sum of ~1000

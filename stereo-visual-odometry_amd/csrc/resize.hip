@@ -1,9 +1,11 @@
 // resize.hip -- cv::resize for 8-bit gray frames (reference src/System.cpp:94-97, app/ros/robust-vslam/src/robust_vslam_ros.cpp:
 // 86-89): the downscale in front of tracking, INTER_NEAREST (what the reference wrote) and INTER_LINEAR, bit for bit as
-// include/svo_abi.h restates them.  One launch resizes every image of a call (grid.z = frame x eye).
+// include/svo_abi.h restates them.  One launch resizes every image of a call (grid.z = frame x eye).  The ORB pyramid
+// (orb.hip) builds its INTER_LINEAR tables with resize_linear_tables too, and the levels its row-streaming kernel does not
+// produce come from the table-driven kernel here (resize_shape + resize_launch_tab, under an LDS budget of its own).
 //
-//   - no double arithmetic on the device: resize_plan builds the tap tables on the host (a source column and two 11-bit weights
-//     per destination column, two source rows and two weights per destination row) and uploads them once per geometry;
+//   - no double arithmetic on the device: the tap tables are built on the host (a source column and two 11-bit weights
+//     per destination column, two source rows and two weights per destination row) and uploaded once per geometry;
 //   - nearest / bilinear: a workgroup produces a tile of destination rows; the source row segments the tile samples are staged in
 //     LDS with 16-byte loads of the aligned granules that hold them (any base address and pitch: the misalignment of a row is
 //     added to the LDS offset, not taken out of the loads), the gather and the blend run from LDS, a lane makes 4 consecutive
@@ -36,7 +38,7 @@ struct ResizeArgs {
 };
 
 // SVO_INTERP_NEAREST (LINEAR = false): dst[dy][dx] = src[yt[dy].x][xt[dx].x & 0xFFFF].
-// SVO_INTERP_LINEAR: cv::resize's two-pass 11-bit fixed point, as orb_resize_kernel (orb.hip) and oracle/orb.c have it.
+// SVO_INTERP_LINEAR: cv::resize's two-pass 11-bit fixed point, as orb_resize_stream_kernel (orb.hip) and oracle/orb.c have it.
 // STAGED = false (a reduction too steep for the LDS budget): the same gather straight from global memory.
 template <bool LINEAR, bool STAGED>
 __global__ __launch_bounds__(256) void resize_tab_kernel(ResizeArgs a)
@@ -167,73 +169,83 @@ static bool resize_scales(int sw, int sh, int dw, int dh, double fx, double fy, 
     return *inv_x > 0 && *inv_x <= 1 && *inv_y > 0 && *inv_y <= 1;
 }
 
-static void resize_tables(const ResizeTab &t, std::vector<int2> &xt, std::vector<int4> &yt)
+// cv::resize's INTER_LINEAR coordinate / weight tables (11-bit weights, scale = 1 / inv: orc_resize_linear_u8 of oracle/orb.c).
+// x: clamped as upstream's xofs / alpha loop does, y: rows clamped to the source like upstream's vertical pass.
+void resize_linear_tables(int sw, int sh, int dw, int dh, double inv_x, double inv_y, int2 *xt, int4 *yt)
 {
-    const double scale_x = 1. / t.inv_x, scale_y = 1. / t.inv_y;
-    xt.resize((size_t)t.dw); yt.resize((size_t)t.dh);
-    if (t.interp == SVO_INTERP_NEAREST) {
-        for (int dx = 0; dx < t.dw; dx++) {
-            int sx = (int)floor(dx * scale_x);
-            sx = sx < t.sw - 1 ? sx : t.sw - 1;
-            xt[(size_t)dx] = make_int2(sx | (sx << 16), 0);
-        }
-        for (int dy = 0; dy < t.dh; dy++) {
-            int sy = (int)floor(dy * scale_y);
-            sy = sy < t.sh - 1 ? sy : t.sh - 1;
-            yt[(size_t)dy] = make_int4(sy, sy, 0, 0);
-        }
-        return;
-    }
-    // INTER_LINEAR: orb_make_tables (orb.hip) / orc_resize_linear_u8 (oracle/orb.c) with this call's scale
-    for (int dx = 0; dx < t.dw; dx++) {
+    const double scale_x = 1. / inv_x, scale_y = 1. / inv_y;
+    for (int dx = 0; dx < dw; dx++) {
         float fx = (float)((dx + 0.5) * scale_x - 0.5);
         int sx = (int)floorf(fx);
         fx -= sx;
         if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= t.sw - 1) { fx = 0; sx = t.sw - 1; }
+        if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
         const int a0 = (short)lrintf((1.f - fx) * 2048), a1 = (short)lrintf(fx * 2048);
-        const int sx1 = sx + 1 < t.sw ? sx + 1 : sx;
-        xt[(size_t)dx] = make_int2(sx | (sx1 << 16), (a0 & 0xFFFF) | (a1 << 16));
+        const int sx1 = sx + 1 < sw ? sx + 1 : sx;
+        xt[dx] = make_int2(sx | (sx1 << 16), (a0 & 0xFFFF) | (a1 << 16));
     }
-    for (int dy = 0; dy < t.dh; dy++) {
+    for (int dy = 0; dy < dh; dy++) {
         float fy = (float)((dy + 0.5) * scale_y - 0.5);
         int sy = (int)floorf(fy);
         fy -= sy;
         const int b0 = (short)lrintf((1.f - fy) * 2048), b1 = (short)lrintf(fy * 2048);
-        const int y0 = sy < 0 ? 0 : (sy >= t.sh ? t.sh - 1 : sy);
-        const int y1 = sy + 1 < 0 ? 0 : (sy + 1 >= t.sh ? t.sh - 1 : sy + 1);
-        yt[(size_t)dy] = make_int4(y0, y1, b0, b1);
+        const int y0 = sy < 0 ? 0 : (sy >= sh ? sh - 1 : sy);
+        const int y1 = sy + 1 < 0 ? 0 : (sy + 1 >= sh ? sh - 1 : sy + 1);
+        yt[dy] = make_int4(y0, y1, b0, b1);
+    }
+}
+
+static void resize_tables(const ResizeTab &t, std::vector<int2> &xt, std::vector<int4> &yt)
+{
+    xt.resize((size_t)t.dw); yt.resize((size_t)t.dh);
+    if (t.interp == SVO_INTERP_LINEAR) {
+        resize_linear_tables(t.sw, t.sh, t.dw, t.dh, t.inv_x, t.inv_y, xt.data(), yt.data());
+        return;
+    }
+    const double scale_x = 1. / t.inv_x, scale_y = 1. / t.inv_y;
+    for (int dx = 0; dx < t.dw; dx++) {
+        int sx = (int)floor(dx * scale_x);
+        sx = sx < t.sw - 1 ? sx : t.sw - 1;
+        xt[(size_t)dx] = make_int2(sx | (sx << 16), 0);
+    }
+    for (int dy = 0; dy < t.dh; dy++) {
+        int sy = (int)floor(dy * scale_y);
+        sy = sy < t.sh - 1 ? sy : t.sh - 1;
+        yt[(size_t)dy] = make_int4(sy, sy, 0, 0);
     }
 }
 
 // The workgroup shape and the LDS it needs, from the tables: exactly the tiles resize_tab_kernel forms.
-static void resize_shape(ResizeTab &t, const std::vector<int2> &xt, const std::vector<int4> &yt)
+ResizeShape resize_shape(int interp, int dw, int dh, const int2 *xt, const int4 *yt, size_t lds_budget)
 {
-    const int lanes = (t.dw + 3) / 4;
-    t.bx_shift = lanes <= 64 ? 6 : (lanes <= 128 ? 7 : 8);
-    const int tile_w = 4 << t.bx_shift;
+    ResizeShape s;
+    const int lanes = (dw + 3) / 4;
+    s.bx_shift = lanes <= 64 ? 6 : (lanes <= 128 ? 7 : 8);
+    const int tile_w = 4 << s.bx_shift;
     int span = 0;
-    for (int x0 = 0; x0 < t.dw; x0 += tile_w) {
-        const int x1 = (x0 + tile_w < t.dw ? x0 + tile_w : t.dw) - 1;
-        const int s = (xt[(size_t)x1].x >> 16) - (xt[(size_t)x0].x & 0xFFFF) + 1;
-        span = s > span ? s : span;
+    for (int x0 = 0; x0 < dw; x0 += tile_w) {
+        const int x1 = (x0 + tile_w < dw ? x0 + tile_w : dw) - 1;
+        const int n = (xt[x1].x >> 16) - (xt[x0].x & 0xFFFF) + 1;
+        span = n > span ? n : span;
     }
-    t.lds_pitch = ((span + 14) / 16 + 1) * 16;         // the segment's granules at the worst misalignment (15)
-    if (t.lds_pitch % 256 == 0) t.lds_pitch += 16;      // rows of the tile on different banks
-    // 8 rows per lane where the LDS budget allows it (measured on 128 pairs 1920x1080 -> 960x540 nearest: 158 us at 4, 139 at 8,
-    // 168 at 16)
-    for (t.rpt = 8; t.rpt >= 1; t.rpt >>= 1) {
-        const int rows_wg = (256 >> t.bx_shift) * t.rpt;
+    s.lds_pitch = ((span + 14) / 16 + 1) * 16;         // the segment's granules at the worst misalignment (15)
+    if (s.lds_pitch % 256 == 0) s.lds_pitch += 16;      // rows of the tile on different banks
+    // 8 rows per lane, or as many as the LDS budget allows (measured on 128 pairs 1920x1080 -> 960x540 nearest: 158 us at 4,
+    // 139 at 8, 168 at 16; the ORB pyramid at 1.2 with the kernel forced on every level: 1.281 ms per 514 images where levels 1
+    // and 5 fell from 8 to 4, 1.294 where all but one level did)
+    for (s.rpt = 8; s.rpt >= 1; s.rpt--) {
+        const int rows_wg = (256 >> s.bx_shift) * s.rpt;
         int nsrc = 0;
-        for (int y0 = 0; y0 < t.dh; y0 += rows_wg) {
-            const int y1 = (y0 + rows_wg < t.dh ? y0 + rows_wg : t.dh) - 1;
-            const int n = t.interp == SVO_INTERP_LINEAR ? yt[(size_t)y1].y - yt[(size_t)y0].x + 1 : y1 - y0 + 1;
+        for (int y0 = 0; y0 < dh; y0 += rows_wg) {
+            const int y1 = (y0 + rows_wg < dh ? y0 + rows_wg : dh) - 1;
+            const int n = interp == SVO_INTERP_LINEAR ? yt[y1].y - yt[y0].x + 1 : y1 - y0 + 1;
             nsrc = n > nsrc ? n : nsrc;
         }
-        t.lds_rows = nsrc;
-        if ((size_t)nsrc * t.lds_pitch <= (size_t)kResizeLdsBytes) return;
+        s.lds_rows = nsrc;
+        if ((size_t)nsrc * s.lds_pitch <= lds_budget) return s;
     }
-    t.rpt = 1; t.lds_rows = 0;                          // a reduction too steep to stage: gathered from global memory
+    s.rpt = 1; s.lds_rows = 0;                          // a reduction too steep to stage: gathered from global memory
+    return s;
 }
 
 int resize_plan(svo_ctx *ctx, int sw, int sh, int dw, int dh, int interp, double fx, double fy, int *tab)
@@ -258,7 +270,7 @@ int resize_plan(svo_ctx *ctx, int sw, int sh, int dw, int dh, int interp, double
         std::vector<int2> xt;
         std::vector<int4> yt;
         resize_tables(t, xt, yt);
-        resize_shape(t, xt, yt);
+        t.shape = resize_shape(interp, dw, dh, xt.data(), yt.data(), kResizeLdsBytes);
         SVO_HIP(hipSetDevice(ctx->device));
         if (dev_alloc(ctx, &t.xt, sizeof(int2) * xt.size()) != SVO_OK) return SVO_ERR_HIP;
         if (dev_alloc(ctx, &t.yt, sizeof(int4) * yt.size()) != SVO_OK) return SVO_ERR_HIP;
@@ -270,43 +282,64 @@ int resize_plan(svo_ctx *ctx, int sw, int sh, int dw, int dh, int interp, double
     return SVO_OK;
 }
 
-int resize_launch(svo_ctx *ctx, int tab, const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
-                  uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st)
+// What both kernels are told about a call's images; grid.z = frame x eye, so one launch takes 65535 images at most.
+static int resize_args(svo_ctx *ctx, ResizeArgs &a, const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
+                       uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int dw, int dh, int n_frames)
 {
-    const ResizeTab &t = ctx->resize_tabs[(size_t)tab];
-    ResizeArgs a{};
     a.src[0] = src0; a.src[1] = src1; a.dst[0] = dst0; a.dst[1] = dst1;
     a.eyes = src1 ? 2 : 1;
     a.spitch = spitch; a.dpitch = dpitch;
     a.sstride = n_frames > 1 ? sstride : 0; a.dstride = n_frames > 1 ? dstride : 0;
-    a.dw = t.dw; a.dh = t.dh;
-    const int nz = n_frames * a.eyes;
-    SVO_ARG(nz >= 1 && nz <= 65535, "resize: too many frames for one launch");
-    auto misalign = [&](int src_al, int dst_al) {
-        uintptr_t s = (uintptr_t)src0 | (uintptr_t)src1 | (uintptr_t)spitch | (uintptr_t)a.sstride;
-        uintptr_t d = (uintptr_t)dst0 | (uintptr_t)dst1 | (uintptr_t)dpitch | (uintptr_t)a.dstride;
-        return (s & (uintptr_t)(src_al - 1)) | (d & (uintptr_t)(dst_al - 1));
-    };
-    if (t.box) {
-        a.aligned = misalign(16, 8) == 0;
-        const dim3 grid((unsigned)((t.dw + 8 * 64 - 1) / (8 * 64)), (unsigned)((t.dh + 4 * kBoxRows - 1) / (4 * kBoxRows)), (unsigned)nz);
-        hipLaunchKernelGGL(resize_box2_kernel, grid, dim3(64, 4), 0, st, a);
+    a.dw = dw; a.dh = dh;
+    SVO_ARG(n_frames >= 1 && n_frames * a.eyes <= 65535, "resize: too many frames for one launch");
+    return SVO_OK;
+}
+
+static bool resize_aligned(const ResizeArgs &a, int src_al, int dst_al)
+{
+    const uintptr_t s = (uintptr_t)a.src[0] | (uintptr_t)a.src[1] | (uintptr_t)a.spitch | (uintptr_t)a.sstride;
+    const uintptr_t d = (uintptr_t)a.dst[0] | (uintptr_t)a.dst[1] | (uintptr_t)a.dpitch | (uintptr_t)a.dstride;
+    return ((s & (uintptr_t)(src_al - 1)) | (d & (uintptr_t)(dst_al - 1))) == 0;
+}
+
+int resize_launch_tab(svo_ctx *ctx, const ResizeShape &sh, int interp, const int2 *xt, const int4 *yt, int dw, int dh,
+                      const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
+                      uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st)
+{
+    ResizeArgs a{};
+    const int rc = resize_args(ctx, a, src0, src1, spitch, sstride, dst0, dst1, dpitch, dstride, dw, dh, n_frames);
+    if (rc) return rc;
+    a.xt = xt; a.yt = yt;
+    a.bx_shift = sh.bx_shift; a.rpt = sh.rpt; a.lds_pitch = sh.lds_pitch;
+    a.aligned = resize_aligned(a, 1, 4);
+    const int tile_w = 4 << sh.bx_shift, rows_wg = (256 >> sh.bx_shift) * sh.rpt;
+    const dim3 grid((unsigned)((dw + tile_w - 1) / tile_w), (unsigned)((dh + rows_wg - 1) / rows_wg), (unsigned)(n_frames * a.eyes));
+    const size_t lds = (size_t)sh.lds_rows * sh.lds_pitch;
+    const bool lin = interp == SVO_INTERP_LINEAR;
+    if (lds > 0) {
+        if (lin) hipLaunchKernelGGL((resize_tab_kernel<true, true>), grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((resize_tab_kernel<false, true>), grid, dim3(256), lds, st, a);
     } else {
-        a.xt = (const int2 *)t.xt; a.yt = (const int4 *)t.yt;
-        a.bx_shift = t.bx_shift; a.rpt = t.rpt; a.lds_pitch = t.lds_pitch;
-        a.aligned = misalign(1, 4) == 0;
-        const int tile_w = 4 << t.bx_shift, rows_wg = (256 >> t.bx_shift) * t.rpt;
-        const dim3 grid((unsigned)((t.dw + tile_w - 1) / tile_w), (unsigned)((t.dh + rows_wg - 1) / rows_wg), (unsigned)nz);
-        const size_t lds = (size_t)t.lds_rows * t.lds_pitch;
-        const bool lin = t.interp == SVO_INTERP_LINEAR;
-        if (lds > 0) {
-            if (lin) hipLaunchKernelGGL((resize_tab_kernel<true, true>), grid, dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((resize_tab_kernel<false, true>), grid, dim3(256), lds, st, a);
-        } else {
-            if (lin) hipLaunchKernelGGL((resize_tab_kernel<true, false>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((resize_tab_kernel<false, false>), grid, dim3(256), 0, st, a);
-        }
+        if (lin) hipLaunchKernelGGL((resize_tab_kernel<true, false>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((resize_tab_kernel<false, false>), grid, dim3(256), 0, st, a);
     }
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
+}
+
+int resize_launch(svo_ctx *ctx, int tab, const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
+                  uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st)
+{
+    const ResizeTab &t = ctx->resize_tabs[(size_t)tab];
+    if (!t.box)
+        return resize_launch_tab(ctx, t.shape, t.interp, (const int2 *)t.xt, (const int4 *)t.yt, t.dw, t.dh, src0, src1, spitch, sstride,
+                                 dst0, dst1, dpitch, dstride, n_frames, st);
+    ResizeArgs a{};
+    const int rc = resize_args(ctx, a, src0, src1, spitch, sstride, dst0, dst1, dpitch, dstride, t.dw, t.dh, n_frames);
+    if (rc) return rc;
+    a.aligned = resize_aligned(a, 16, 8);
+    const dim3 grid((unsigned)((t.dw + 8 * 64 - 1) / (8 * 64)), (unsigned)((t.dh + 4 * kBoxRows - 1) / (4 * kBoxRows)), (unsigned)(n_frames * a.eyes));
+    hipLaunchKernelGGL(resize_box2_kernel, grid, dim3(64, 4), 0, st, a);
     SVO_HIP(hipGetLastError());
     return SVO_OK;
 }

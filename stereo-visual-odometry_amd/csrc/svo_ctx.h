@@ -58,6 +58,12 @@ struct StreamSet {
     int call = 0;
 };
 
+// The launch shape of the table-driven resize kernel (resize.hip), derived from one geometry's tap tables: resize_shape.
+struct ResizeShape {
+    int bx_shift = 8, rpt = 8;        // workgroup = 2^bx_shift lanes along x (4 pixels each) x 256 >> bx_shift lane rows x rpt rows per lane
+    int lds_pitch = 0, lds_rows = 0;  // staged source rows: bytes per row (multiple of 16), rows; 0 rows: gathered from global memory
+};
+
 // One cv::resize geometry (resize.hip): the tap tables of (source size, destination size, interpolation, factors), built on
 // the host in double exactly as include/svo_abi.h states them and uploaded once, and the launch shape derived from them.
 struct ResizeTab {
@@ -66,8 +72,7 @@ struct ResizeTab {
     double inv_x = 1, inv_y = 1;
     bool box = false;                 // INTER_LINEAR at exactly 2x: the 2x2 mean, no tables
     void *xt = nullptr, *yt = nullptr;   // int2 per destination column (sx | sx1 << 16, a0 | a1 << 16), int4 per row (y0, y1, b0, b1)
-    int bx_shift = 8, rpt = 8;        // workgroup = 2^bx_shift lanes along x (4 pixels each) x 256 >> bx_shift lane rows x rpt rows per lane
-    int lds_pitch = 0, lds_rows = 0;  // staged source rows: bytes per row (multiple of 16), rows; 0 rows: gathered from global memory
+    ResizeShape shape;
 };
 
 // The ingest stage of a context (svo_ingest_create): source-size frames -> the context's width x height.
@@ -137,7 +142,8 @@ struct svo_ctx {
     bool orb_ready = false;
     bool orb_qt_parallel = false;            // the node-parallel quadtree kernel is usable for this configuration
     bool orb_level0_in_slot = false;         // the last extraction copied level 0 into the image slots (false: read in place, OrbL0)
-    bool orb_resize_staged = false;          // SVO_ORB_RESIZE_STAGED: the LDS-staged resize kernel on every level (A/B measurements, its test)
+    bool orb_resize_staged = false;          // SVO_ORB_RESIZE_STAGED: the table-driven staged kernel (resize.hip) on every level (A/B measurements, its tests)
+    ResizeShape orb_resize_shape[svo::kOrbMaxLevels];    // that kernel's launch shape for level l >= 1
     bool orb_copy_level0 = false;            // SVO_ORB_COPY_LEVEL0: level 0 copied into the slot even where it could be read in place (A/B, its test)
     svo::OrbGeom orb_geom;
     uint8_t *orb_slots = nullptr, *orb_blur = nullptr;
@@ -315,8 +321,15 @@ int orbm_alloc(svo_ctx *ctx);                            // its device blocks, o
 int orbm_stereo_frames(svo_ctx *ctx, int slot0, int n_frames, hipStream_t st);      // stage S on frames just extracted into image slots slot0 ..
 int orbm_track_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, hipStream_t st, int *idx_prev = nullptr, int *idx_cur = nullptr);
 // resize.hip
+// cv::resize's INTER_LINEAR tap tables, xt[dw] and yt[dh], for inv = the destination's size over the source's
+void resize_linear_tables(int sw, int sh, int dw, int dh, double inv_x, double inv_y, int2 *xt, int4 *yt);
+// the workgroup shape for tables xt[dw], yt[dh], its staged rows within lds_budget bytes
+ResizeShape resize_shape(int interp, int dw, int dh, const int2 *xt, const int4 *yt, size_t lds_budget);
 int resize_plan(svo_ctx *ctx, int sw, int sh, int dw, int dh, int interp, double fx, double fy, int *tab);
-// n_frames images per eye (eye 1 may be null), frame f at base + f * stride; one launch
+// n_frames images per eye (eye 1 may be null), frame f at base + f * stride; one launch (n_frames x eyes <= 65535: grid.z)
+int resize_launch_tab(svo_ctx *ctx, const ResizeShape &shape, int interp, const int2 *xt, const int4 *yt, int dw, int dh,
+                      const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
+                      uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st);
 int resize_launch(svo_ctx *ctx, int tab, const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
                   uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st);
 // One step of a stream set: item i of a launch works for stream id[i]; init[i]: the stream's first frame (no previous one).

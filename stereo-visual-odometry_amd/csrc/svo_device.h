@@ -66,6 +66,35 @@ __device__ __forceinline__ int wave_incl_scan(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
     return v;
 }
+// exclusive prefix of v over a workgroup of 1024 lanes (carry.hip, window.hip); wave_tot: 16 ints of LDS; total: the sum.
+// (two barriers)
+__device__ inline int block1024_excl_scan(int v, int *wave_tot, int &total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) wave_tot[wv] = inc;
+    __syncthreads();
+    int pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) { const int t = wave_tot[k]; if (k < wv) pre += t; tot += t; }
+    __syncthreads();
+    total = tot;
+    return pre + inc - v;
+}
+
+// the wave's sum of v in every lane: a butterfly, so the additions' order (part of the results) is the same for all lanes
+__device__ inline double wave_allsum_f64(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
 __host__ __device__ inline int refl101(int i, int n)
 {
     if (n == 1) return 0;

@@ -19,26 +19,6 @@
 
 namespace svo {
 
-// exclusive prefix of v over the workgroup's 1024 lanes; total: the sum.  (two barriers)
-__device__ inline int window_scan(int v, int *wave_tot, int &total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) wave_tot[wv] = inc;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) { const int t = wave_tot[k]; if (k < wv) pre += t; tot += t; }
-    __syncthreads();
-    total = tot;
-    return pre + inc - v;
-}
-
 // first index in [0, n) whose id is >= id (n: none)
 __device__ inline int window_lower_bound(const long long *ids, int n, long long id)
 {
@@ -100,7 +80,7 @@ __global__ __launch_bounds__(1024) void window_update_kernel(WindowUpdateArgs a)
         const int r = start + tid;
         const bool s = r < m && (a.in.seen[r] >> shift) != 0;
         int tot;
-        const int ex = window_scan(s ? 1 : 0, wave_tot, tot);
+        const int ex = block1024_excl_scan(s ? 1 : 0, wave_tot, tot);
         if (r < m) a.pre_rows[r] = n_rows + ex;
         n_rows += tot;
     }
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(1024) void window_update_kernel(WindowUpdateArgs a)
             fresh = !(r < m && a.in.ids[r] == id && (a.in.seen[r] >> shift) != 0);
         }
         int tot;
-        const int ex = window_scan(fresh ? 1 : 0, wave_tot, tot);
+        const int ex = block1024_excl_scan(fresh ? 1 : 0, wave_tot, tot);
         if (k < nt) a.pre_new[k] = n_new + ex;
         n_new += tot;
     }
@@ -236,7 +216,7 @@ __device__ inline void wba_reduce(double (&acc)[kWbaAcc], bool pair, double *red
 #pragma unroll
     for (int k = 0; k < K; k++) {
         if (pair && k < 2) continue;
-        const double ws = refine_wave_allsum(acc[k]);
+        const double ws = wave_allsum_f64(acc[k]);
         if (lane == 0) red[wave * kWbaAcc + k] = ws;
     }
     __syncthreads();

@@ -289,3 +289,82 @@ def test_orb_level0_in_place_is_not_in_the_slot(pkg, oracle, tc, synth):
     c.orb_extract(left)                                                                 # the stage API copies level 0
     assert np.array_equal(c.orb_read_level(0), left)
     c.close()
+
+
+def test_orb_staged_resize_reads_level0_in_place_both_eyes(pkg, oracle, tc, synth, monkeypatch):
+    """The table-driven staged resize (SVO_ORB_RESIZE_STAGED=1) on a batch whose level 0 is read IN PLACE from both eyes'
+    frames (rows padded to pitch w + 32, the padding holds 0xA5): the records are byte-equal to those of the default path on
+    unpadded frames (which test_orb_mode_online_and_batch_parity checks against the oracle), and level 1 of image slot 0 --
+    the first left frame -- is the oracle's."""
+    seq = synth.StereoSequence(width=832, height=256, n_frames=4, seed=5)
+    frames = [tuple(x.numpy() for x in seq.render(t)) for t in range(4)]
+    h, w = frames[0][0].shape
+    P1s, P2s = seq.proj()
+    kw = dict(P1=P1s, P2=P2s, track_mode=pkg.MODE_ORB, min_move2=0.05 ** 2, max_move2=10.0 ** 2, max_batch=3)
+    L = tc.stack([tc.from_numpy(f[0]) for f in frames]).cuda()
+    R = tc.stack([tc.from_numpy(f[1]) for f in frames]).cuda()
+    monkeypatch.delenv("SVO_ORB_RESIZE_STAGED", raising=False)
+    c = pkg.Context(w, h, device=0, **kw)
+    res = c.track_batch(L, R)
+    c.close()
+    assert all(int(r["ok"]) for r in res)
+    Lp = tc.full((4, h, w + 32), 0xA5, dtype=tc.uint8, device="cuda")
+    Rp = tc.full((4, h, w + 32), 0xA5, dtype=tc.uint8, device="cuda")
+    Lp[:, :, :w] = L
+    Rp[:, :, :w] = R
+    monkeypatch.setenv("SVO_ORB_RESIZE_STAGED", "1")
+    c = pkg.Context(w, h, device=0, **kw)
+    assert c.track_batch(Lp[:, :, :w], Rp[:, :, :w]).tobytes() == res.tobytes()
+    with pytest.raises(pkg.SvoError):
+        c.orb_read_level(0)                                   # level 0 was read in place
+    assert np.array_equal(c.orb_read_level(1), oracle.orb_pyramid_level(frames[0][0], 1))
+    c.close()
+
+
+def test_orb_staged_resize_second_tile_column(pkg, oracle, tc, monkeypatch):
+    """The staged resize on a level wider than one tile: 1241x376 at 1.2 makes level 1 1034 pixels wide, one full
+    1024-pixel tile column and a ragged one of 10 pixels.  Byte-equal to the oracle's cv::resize restatement."""
+    img = rand_image(376, 1241, 11)
+    monkeypatch.setenv("SVO_ORB_RESIZE_STAGED", "1")
+    ctx = pkg.Context(1241, 376, device=0, track_mode=pkg.MODE_ORB, orb_nlevels=2)
+    ctx.orb_extract(img)
+    lvl = ctx.orb_read_level(1)
+    ctx.close()
+    assert lvl.shape == (313, 1034)
+    assert np.array_equal(lvl, oracle.orb_pyramid_level(img, 1, nlevels=2))
+
+
+@pytest.mark.parametrize("sf,nl", [(1.2, 8), (2.0, 4), (2.7, 3)])
+def test_orb_pyramid_and_resize_agree(pkg, tc, sf, nl):
+    """cv::resize(INTER_LINEAR) has two users, the ORB pyramid and svo_resize: level l read back must be the size-form resize
+    of level l - 1 read back, byte for byte.  1.2: the row-streaming kernel against the staged one; 2.7: the staged kernel
+    launched by both; 2.0: the levels are 333x201, 166x100, 83x50, 42x25, and level 2 halves level 1 exactly, where
+    svo_resize takes the 2x2 mean and the pyramid its tables.  (The two CPU references agree on exactly these inputs.)"""
+    img = rand_image(201, 333, 7)
+    ctx = pkg.Context(333, 201, device=0, track_mode=pkg.MODE_ORB, max_keypoints=8192, orb_nlevels=nl, orb_scale_factor=sf)
+    ctx.orb_extract(img)
+    levels = [ctx.orb_read_level(l) for l in range(nl)]
+    assert np.array_equal(levels[0], img)
+    for l in range(1, nl):
+        dh, dw = levels[l].shape
+        assert np.array_equal(ctx.resize(levels[l - 1], dw, dh, "linear"), levels[l]), (sf, l)
+    ctx.close()
+
+
+def test_orb_resize_level_too_steep_to_stage(pkg, oracle, tc):
+    """A pyramid level whose shape comes out unstaged under the pyramid's LDS budget of 12 KB (12288 bytes): 2045x403 at a
+    scale factor of 4.0 (outside (1, 2], so the table-driven kernel is taken by itself).  Level 1 is 511x101: 128 lanes of 4
+    pixels, so a workgroup is 128 lanes x 2 lane rows and one 512-pixel tile column covers the level.  Its source columns run
+    from floor(0.5 * 2045/511 - 0.5) = 1 to floor(510.5 * 2045/511 - 0.5) + 1 = 2043: a span of 2043 bytes, staged at a
+    pitch of ((2043 + 14) / 16 + 1) * 16 = 2064.  At one row per lane a workgroup makes 2 output rows, whose taps span up to
+    6 source rows (403/101 = 3.99 rows apart, two taps each): 6 * 2064 = 12384 > 12288, so nothing is staged and the level
+    is gathered from global memory.  Level, keypoints and descriptors byte-equal to the oracle's."""
+    img = rand_image(403, 2045, 13)
+    ctx = pkg.Context(2045, 403, device=0, track_mode=pkg.MODE_ORB, max_keypoints=8192, orb_nlevels=2, orb_scale_factor=4.0)
+    kps, desc, _ = ctx.orb_extract(img)
+    lvl = ctx.orb_read_level(1)
+    ctx.close()
+    assert lvl.shape == (101, 511)
+    assert np.array_equal(lvl, oracle.orb_pyramid_level(img, 1, scale_factor=4.0, nlevels=2))
+    rk, rd, _ = oracle.orb_extract(img, nlevels=2, scale_factor=4.0, nfeatures=2000, ini_th=20, min_th=7)
+    assert kps.tobytes() == rk.tobytes() and desc.tobytes() == rd.tobytes()
