@@ -920,6 +920,98 @@ int svo_get_window_result(svo_ctx *ctx, svo_window_result *res);
 int svo_window_ba(svo_ctx *ctx, const svo_window_table *table, int cap, const double P1[12], const double P2[12], int rounds, int iters,
                   double sigma_px, int min_obs, svo_window_result *res, int mem);
 
+/* ---- Keyframe-relative pose on the online chain over carried LK tracks (additive; detected by symbol, the ABI version stays 9
+ * and svo_config / svo_step_result are unchanged) ---------------------------------------------------------------------------
+ * Every pose the chain reports is a product of one relative motion per frame (frame_pose_ = frame_pose_ * T.inv(),
+ * src/tracking.cpp:318).  With keyframe mode on, the current frame is ALSO localised by solvePnPRansac against 3-D points
+ * triangulated once, at a keyframe several frames back, and where that solve is accepted its pose replaces the chained one:
+ * error then accumulates per keyframe, and the baseline of a solve is longer.  Off by default; with it off every step runs
+ * exactly the launches it ran before and every record is byte for byte what it was.
+ *
+ * State of a chain, on the device: valid; kf_index (the chain's frame counter at the keyframe; frames count from 0 at a
+ * chain's first frame); pose_K (world from camera, 4 x 4 row-major) and inv_K (camera from world, rule T4's closed form);
+ * n_rows; ids int64[n_rows], strictly ascending; X float32[n_rows][3] in the keyframe's camera frame.
+ * Rules (the numpy twin is tests/_keyframe_ref.py; the kernels equal it bit for bit in every integer, list and table, and to
+ * the chain's bar in poses).  One step is a pair a -> b.  Its record r is the record as the gates -- and the refinement stage,
+ * if on -- leave it; its tracks are those of svo_get_last_tracks, their ids those of svo_get_last_track_ids (ascending, rule
+ * C5); tri is the pose stage's float32 triangulation of (t1_left, t1_right), in a's camera frame; pose_a is the chain pose
+ * before the step; index(b) is b's frame counter.
+ *   K1 cleared.  The state becomes not valid on a chain's first frame and on svo_reset, svo_set_pose, svo_set_keyframe and
+ *      svo_set_track_carry.  A failed step (r.ok = 0) does NOT clear it: the carry goes on whatever the outcome (C8) and the
+ *      gap simply grows.
+ *   K2 join.  With a valid state, for every track i in ascending order whose id has a row j, the joined lists gain
+ *      (X[j], t2_left[i]) and the index pair (i, j); n_join is their length.  The result is the merge of two id-sorted lists
+ *      and contains nothing else; ids compare as 64-bit integers.  With an invalid state n_join = 0.
+ *   K3 solve.  With a valid state and n_join >= min_tracks: solvePnPRansac(joined X, joined t2_left) with the context's K,
+ *      iterationsCount, reprojectionError and confidence -- exactly the pair's solve on other lists, from the same cv::RNG(-1)
+ *      state -- gives [R t], X_b = R X_K + t.  Otherwise nothing is solved (n_inliers, ransac_iters, lm_iters, rvec, tvec are
+ *      0) and the status is SVO_KF_SHORT, or SVO_KF_NONE with an invalid state.
+ *   K4 accept.  SVO_KF_APPLIED iff r.ok = 1, the solve succeeded, (double)n_inliers / (double)n_join >= inlier_rate, and the
+ *      motion a -> b that the keyframe pose implies passes the pair's own gates: F = ([R t; 0 0 0 1] inv_K) pose_a, both
+ *      products in chain_relative's association order (k ascending, separate multiply and add, from 0); on F's rotation the
+ *      three Euler angles of rotationMatrixToEulerAngles as the pair's gate computes them must each be below 0.1 in absolute
+ *      value; on F's translation |t|^2 < max_move2 (t0 t0 + t1 t1 + t2 t2, left to right).  There is no lower bound: the pair
+ *      has passed it.  Otherwise SVO_KF_REJECTED, or SVO_KF_PAIR_FAILED when r.ok = 0.
+ *   K5 apply.  On APPLIED r.pose := pose_K inverse([R t]), the inverse in the closed form of T_rel_inv (R^T, -(R^T t) summed
+ *      left to right), the product in the chain's order; frame_pose_ (svo_get_pose) follows.  T_rel_inv, rvec, tvec, R, every
+ *      count, every track and the inlier mask stay the pair's.  With any other status the record is untouched, bit for bit.
+ *   K6 switch.  After K5 and only when r.ok = 1: a new keyframe is taken iff the state is not valid, or the status is not
+ *      APPLIED, or max_gap > 0 and gap >= max_gap, gap = index(b) - kf_index.  The new keyframe is frame a: kf_index =
+ *      index(b) - 1, pose_K = pose_a, inv_K by T4; the table becomes this pair's tracks whose three tri floats are finite,
+ *      in list order, as (id, tri).  Frame a because its stereo triangulation already exists; the step that switches reports
+ *      the pair's own pose, and that pose IS the keyframe solution for K = a.  The smallest gap of a solve is therefore 2.
+ *   K7 with r.ok = 0 the state keeps everything.  The join and the solve are still launched (no host decision is added) and
+ *      reported; they are not used.
+ *   K8 the same input gives the same bytes on every run: no floating-point atomics, the lists are in id order.
+ *   svo_set_keyframe : LK mode, the online chain (svo_add_frame / svo_ingest_add_frame) with track carry on.  on = 0 (the
+ *      default): off, the other arguments are ignored.  While on, every step with a previous frame runs keyframe_join_kernel,
+ *      one solvePnPRansac on the joined lists (item 1 of the pose workspace) and keyframe_update_kernel after the gates and the
+ *      pose chain, on the step's stream, before the record is delivered (timing marks kf_join, kf_pnp, kf_update); no host
+ *      synchronisation is added.  max_gap = 0: no limit.  SVO_ERR_ARG (nothing changes): an ORB-mode context, min_tracks < 4
+ *      or > max_keypoints, max_gap < 0 or = 1, max_batch < 2.  SVO_ERR_STATE: track carry is off, or the sliding window is on
+ *      (both would rewrite `pose`).  While it is on, svo_set_window_ba(on), svo_set_track_carry(off), svo_streams_step and
+ *      svo_ingest_streams_step return SVO_ERR_STATE (stream sets have no keyframe yet).  The refinement stage is independent:
+ *      the pair's record is refined as before, the keyframe solve never is.  Memory: the first enabling call allocates ONE
+ *      block -- 20 bytes x max_keypoints for the table, 36 bytes x max_keypoints for the joined lists, the state and the
+ *      result -- and waits for the device; a context that never enables it allocates nothing.
+ *   svo_get_keyframe : what is set (0, 0, 0 while off).  Any pointer may be NULL.
+ *   svo_keyframe_result: status; switched (K6 took a new keyframe); kf_index, gap, n_rows and pose_K of the keyframe the step
+ *      joined against (-1, 0, 0 and zeros when there was none); n_join; n_inliers, ransac_iters, lm_iters, rvec, tvec of the
+ *      solve; pose_pair, the chained pair pose the record held before K5.
+ *   Read-backs (HOST; they wait for the step).  SVO_ERR_ARG when keyframe mode was off for the last svo_add_frame step or no
+ *   pair has been tracked.  Every list pointer NULL: *n_out only; otherwise SVO_ERR_ARG when cap is too small (*n_out is still
+ *   set); a NULL list is left out.
+ *      svo_get_keyframe_result  : the last step's svo_keyframe_result.
+ *      svo_get_keyframe_matches : the joined lists -- id, X, t2_left, track index i, and the solve's inlier mask (zeros when
+ *                                 nothing was solved) -- n_join entries each.
+ *      svo_get_keyframe_table   : the table after the step (ids, X), n_rows entries.
+ *   svo_keyframe_join (stage API): keyframe_join_kernel on a caller's arrays, independent of the context's size and mode.
+ *      Table tab_ids / tab_X (n_rows x 3 floats), tracks trk_ids / trk_xy; both id lists strictly ascending (unspecified rows,
+ *      but no access outside the arrays, otherwise).  Outputs, cap >= min(n_rows, n_trk) entries each: out_X, out_xy, out_trk
+ *      (i), out_row (j), *n_out.  `mem` says where every array AND the count live; SVO_MEM_DEVICE: one launch in stream order
+ *      on the context's stream, no host synchronisation, inputs and outputs must not overlap; SVO_MEM_HOST: returns when the
+ *      outputs are complete (scratch grows on demand; a call that grows it waits for the device).  SVO_ERR_ARG: a count < 0 or
+ *      > 2^20, a null pointer, cap < min(n_rows, n_trk).
+ *   Host mirror: YAML keyframe: 0 | 1 with keyframe_max_gap; min_tracks is num_features_needed_for_keyframe. */
+#define SVO_KF_NONE        0
+#define SVO_KF_SHORT       1
+#define SVO_KF_PAIR_FAILED 2
+#define SVO_KF_REJECTED    3
+#define SVO_KF_APPLIED     4
+typedef struct {
+    int32_t status, switched, kf_index, gap, n_rows, n_join, n_inliers, ransac_iters, lm_iters, _pad;
+    double rvec[3], tvec[3];
+    double pose_K[16], pose_pair[16];
+} svo_keyframe_result;
+int svo_set_keyframe(svo_ctx *ctx, int on, int min_tracks, int max_gap);
+int svo_get_keyframe(const svo_ctx *ctx, int *on, int *min_tracks, int *max_gap);
+int svo_get_keyframe_result(svo_ctx *ctx, svo_keyframe_result *res);
+int svo_get_keyframe_matches(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, svo_pt2f *xy, int32_t *trk_index, uint8_t *mask, int cap, int *n_out);
+int svo_get_keyframe_table(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, int cap, int *n_out);
+int svo_keyframe_join(svo_ctx *ctx, const int64_t *tab_ids, const svo_pt3f *tab_X, int n_rows, const int64_t *trk_ids,
+                      const svo_pt2f *trk_xy, int n_trk, svo_pt3f *out_X, svo_pt2f *out_xy, int32_t *out_trk, int32_t *out_row,
+                      int cap, int *n_out, int mem);
+
 /* Serial prefix product of n inverse relative motions (svo_step_result.T_rel_inv, row-major 4x4),
  * skipping pairs with ok == 0:  poses_out[p] = pose0 * prod_{q <= p, ok[q]} T[q]  -- the
  * `frame_pose_ = frame_pose_ * T.inv()` recurrence of reference src/tracking.cpp:318 for frame

@@ -13,10 +13,12 @@ from .binding import (Context, Config, StepResult, PnPResult, KP_DTYPE, STEP_DTY
                       build_library, library_path, load_library, MEM_HOST, MEM_DEVICE, MODE_LK, MODE_ORB, LK_ACCUM_EXACT, LK_ACCUM_SSE2, LK_ACCUM_SIMD128, LK_ACCUM_SSE2_LEGACY,
                       INTERP_NEAREST, INTERP_LINEAR, scale_projection,
                       RefineResult, REFINE_OFF, REFINE_REPROJ, REFINE_BA, REFINE_APPLIED, REFINE_KEPT_PNP, REFINE_SKIPPED,
-                      ORB_MATCHER_BRUTE, ORB_MATCHER_GUIDED)
+                      ORB_MATCHER_BRUTE, ORB_MATCHER_GUIDED,
+                      KeyframeResult, KF_NONE, KF_SHORT, KF_PAIR_FAILED, KF_REJECTED, KF_APPLIED)
 
 __all__ = ["Context", "Config", "StepResult", "PnPResult", "KP_DTYPE", "STEP_DTYPE", "SvoError",
            "build_library", "library_path", "load_library", "MEM_HOST", "MEM_DEVICE", "MODE_LK", "MODE_ORB", "LK_ACCUM_EXACT", "LK_ACCUM_SSE2", "LK_ACCUM_SIMD128", "LK_ACCUM_SSE2_LEGACY",
            "INTERP_NEAREST", "INTERP_LINEAR", "scale_projection",
            "RefineResult", "REFINE_OFF", "REFINE_REPROJ", "REFINE_BA", "REFINE_APPLIED", "REFINE_KEPT_PNP", "REFINE_SKIPPED",
-           "ORB_MATCHER_BRUTE", "ORB_MATCHER_GUIDED"]
+           "ORB_MATCHER_BRUTE", "ORB_MATCHER_GUIDED",
+           "KeyframeResult", "KF_NONE", "KF_SHORT", "KF_PAIR_FAILED", "KF_REJECTED", "KF_APPLIED"]

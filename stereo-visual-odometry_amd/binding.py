@@ -94,6 +94,22 @@ class WindowResult(C.Structure):
         return d
 
 
+KF_NONE, KF_SHORT, KF_PAIR_FAILED, KF_REJECTED, KF_APPLIED = 0, 1, 2, 3, 4
+
+
+class KeyframeResult(C.Structure):
+    """svo_keyframe_result: what keyframe mode did in the last add_frame step."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "switched", "kf_index", "gap", "n_rows", "n_join", "n_inliers", "ransac_iters",
+                                         "lm_iters", "_pad")] + [
+        ("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("pose_K", C.c_double * 16), ("pose_pair", C.c_double * 16)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("status", "switched", "kf_index", "gap", "n_rows", "n_join", "n_inliers", "ransac_iters", "lm_iters")}
+        d["rvec"], d["tvec"] = np.array(self.rvec, np.float64), np.array(self.tvec, np.float64)
+        d["pose_K"], d["pose_pair"] = np.array(self.pose_K, np.float64).reshape(4, 4), np.array(self.pose_pair, np.float64).reshape(4, 4)
+        return d
+
+
 def library_path():
     return os.path.join(_HERE, "libsvo_hip.so")
 
@@ -214,6 +230,13 @@ def load_library():
                                   C.c_void_p, C.c_int]
     lib.svo_window_update.argtypes = ([C.c_void_p, C.c_int, C.POINTER(WindowTable), C.POINTER(WindowTable), C.c_int] + [C.c_void_p] * 6 +
                                       [C.c_int, C.c_void_p, C.c_void_p, C.c_int])
+    lib.svo_set_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.svo_get_keyframe.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.svo_get_keyframe_result.argtypes = [C.c_void_p, C.POINTER(KeyframeResult)]
+    lib.svo_get_keyframe_matches.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_int)]
+    lib.svo_get_keyframe_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.svo_keyframe_join.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 +
+                                      [C.c_int, C.c_void_p, C.c_int])
     _LIB = lib
     return lib
 
@@ -945,6 +968,89 @@ class Context:
         if ordered:
             self._order_out(res)
         return res, table
+
+    # ---- keyframe-relative pose on the online chain (svo_set_keyframe / svo_keyframe_join and the read-backs) ----------
+    def set_keyframe(self, on=True, min_tracks=60, max_gap=0):
+        """LK mode, add_frame / ingest_add_frame with track carry on: localise every frame by solvePnPRansac against the
+        points triangulated at a keyframe several frames back as well, and report that pose where it passes the pair's own
+        gates (svo_set_keyframe).  min_tracks: joined tracks a solve needs; max_gap: frames a keyframe serves at most (0: no
+        limit).  While on, set_window_ba(on), set_track_carry(False) and streams_step refuse."""
+        if on and (int(min_tracks) < 4 or int(max_gap) < 0 or int(max_gap) == 1):
+            raise ValueError("min_tracks must be >= 4 and max_gap 0 (no limit) or >= 2")
+        self._check(self.lib.svo_set_keyframe(self.h, 1 if on else 0, int(min_tracks), int(max_gap)))
+
+    def keyframe(self):
+        """(on, min_tracks, max_gap) as set; (False, 0, 0) while off."""
+        on, mt, mg = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.svo_get_keyframe(self.h, C.byref(on), C.byref(mt), C.byref(mg)))
+        return bool(on.value), mt.value, mg.value
+
+    def keyframe_result(self):
+        """The last add_frame step's svo_keyframe_result as a dict (poses 4 x 4)."""
+        res = KeyframeResult()
+        self._check(self.lib.svo_get_keyframe_result(self.h, C.byref(res)))
+        return res.as_dict()
+
+    def keyframe_matches(self):
+        """The last step's joined lists: dict(ids, X (n, 3), xy (n, 2), trk (the track's index in last_tracks()), mask (the
+        keyframe solve's inliers; zeros when nothing was solved))."""
+        n = C.c_int(0)
+        self._check(self.lib.svo_get_keyframe_matches(self.h, None, None, None, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        out = {"ids": np.zeros(m, np.int64), "X": np.zeros((m, 3), np.float32), "xy": np.zeros((m, 2), np.float32),
+               "trk": np.zeros(m, np.int32), "mask": np.zeros(m, np.uint8)}
+        self._check(self.lib.svo_get_keyframe_matches(self.h, *[C.c_void_p(out[k].ctypes.data) for k in ("ids", "X", "xy", "trk", "mask")],
+                                                      m, C.byref(n)))
+        return {k: v[:n.value].copy() for k, v in out.items()}
+
+    def keyframe_table(self):
+        """The chain's keyframe table after the last step: (ids, X (n, 3) float32 in the keyframe's camera frame)."""
+        n = C.c_int(0)
+        self._check(self.lib.svo_get_keyframe_table(self.h, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        ids, X = np.zeros(m, np.int64), np.zeros((m, 3), np.float32)
+        self._check(self.lib.svo_get_keyframe_table(self.h, C.c_void_p(ids.ctypes.data), C.c_void_p(X.ctypes.data), m, C.byref(n)))
+        return ids[:n.value].copy(), X[:n.value].copy()
+
+    def keyframe_join(self, tab_ids, tab_X, trk_ids, trk_xy, cap=None):
+        """svo_keyframe_join: the tracks whose id has a row in the table, in track order.  numpy inputs: returns a dict of
+        numpy arrays X (n, 3), xy (n, 2), trk, row (n entries).  torch cuda inputs: the same keys as `cap`-entry tensors plus
+        n_out as an int32 tensor, all filled in stream order without a host synchronisation."""
+        host = isinstance(tab_ids, np.ndarray)
+        if host:
+            conv = lambda a, dt, shape: np.ascontiguousarray(a, dt).reshape(shape)
+            new = lambda shape, dt: np.zeros(shape, dt)
+            f32, i64, i32 = np.float32, np.int64, np.int32
+            ptr = lambda a: C.c_void_p(a.ctypes.data)
+        else:
+            import torch
+            dev = tab_ids.device
+            conv = lambda a, dt, shape: a.to(dt).contiguous().reshape(shape)
+            new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            f32, i64, i32 = torch.float32, torch.int64, torch.int32
+            ptr = lambda a: C.c_void_p(a.data_ptr())
+        ti, tx, ki, kx = conv(tab_ids, i64, (-1,)), conv(tab_X, f32, (-1, 3)), conv(trk_ids, i64, (-1,)), conv(trk_xy, f32, (-1, 2))
+        n_rows, n_trk = int(ti.shape[0]), int(ki.shape[0])
+        if int(tx.shape[0]) != n_rows or int(kx.shape[0]) != n_trk:
+            raise ValueError("tab_X / trk_xy must have one row per id")
+        cap = min(n_rows, n_trk) if cap is None else int(cap)
+        m = max(cap, 1)
+        out = {"X": new((m, 3), f32), "xy": new((m, 2), f32), "trk": new((m,), i32), "row": new((m,), i32)}
+        if host:
+            n_out = C.c_int(0)
+            pn = C.cast(C.byref(n_out), C.c_void_p)
+        else:
+            n_out = new((1,), i32)
+            pn = ptr(n_out)
+            ordered = self._order_in(n_out)
+        self._check(self.lib.svo_keyframe_join(self.h, ptr(ti), ptr(tx), n_rows, ptr(ki), ptr(kx), n_trk, ptr(out["X"]), ptr(out["xy"]),
+                                               ptr(out["trk"]), ptr(out["row"]), cap, pn, MEM_HOST if host else MEM_DEVICE))
+        if host:
+            return {k: v[:n_out.value].copy() for k, v in out.items()}
+        if ordered:
+            self._order_out(n_out)
+        out["n_out"] = n_out
+        return out
 
     def _ids(self, fn, *head, cap=65536):
         ids, ages, n = np.zeros(cap, np.int64), np.zeros(cap, np.int32), C.c_int(0)

@@ -1087,17 +1087,18 @@ int geom_workspace_init(svo_ctx *ctx)
 
 // The launch sequence of one solvePnPRansac for n_items items (see the kernel comments above).
 // max_pts bounds the points of any item (grid.z of the scoring kernel).
-static void launch_pnp_pipeline(svo_ctx *ctx, PnpArgs a, int n_items, int max_pts, hipStream_t st, bool begun = false)
+// item0: the workspace item the first of the n_items solves uses (the caller's X3 / img / mask / n_pts are item item0's).
+static void launch_pnp_pipeline(svo_ctx *ctx, PnpArgs a, int n_items, int max_pts, hipStream_t st, bool begun = false, int item0 = 0)
 {
     const svo_config &cfg = ctx->cfg;
     char *ws = (char *)ctx->pnp_ws;
     const int B = cfg.max_batch;
-    a.out = (PnpRecord *)ws;
-    a.state = (PnpState *)(ws + ws_off_state(cfg, B));
-    a.hyp = (PnpHyp *)(ws + ws_off_hyp(cfg, B));
-    a.counts = (int *)(ws + ws_off_counts(cfg, B));
-    a.subsets = (int *)(ws + ws_off_subsets(cfg, B));
-    a.hand = (double *)(ws + ws_off_hand(cfg, B));
+    a.out = (PnpRecord *)ws + item0;
+    a.state = (PnpState *)(ws + ws_off_state(cfg, B)) + item0;
+    a.hyp = (PnpHyp *)(ws + ws_off_hyp(cfg, B)) + (int64_t)item0 * kPhaseHyps;
+    a.counts = (int *)(ws + ws_off_counts(cfg, B)) + (int64_t)item0 * kPhaseHyps;
+    a.subsets = (int *)(ws + ws_off_subsets(cfg, B)) + (int64_t)item0 * 2 * kPhaseHyps * 5;
+    a.hand = (double *)(ws + ws_off_hand(cfg, B)) + (int64_t)item0 * kPhaseBlocks * (kEpnpHandDoubles * 64);
     a.stream = (const uint64_t *)(ws + ws_off_stream(cfg, B));
     if (!begun) hipLaunchKernelGGL(pnp_begin_kernel, dim3(n_items), dim3(64), 0, st, a);
     const int niters = a.iterations > 1 ? a.iterations : 1;
@@ -1183,6 +1184,22 @@ void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n
     a.mask = (uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch);
     launch_pnp_pipeline(ctx, a, n_items, ctx->cfg.max_keypoints, st, /*begun by launch_triangulate_batch*/ true);
 }
+
+// One more solvePnPRansac of the online step, on lists of its own (svo_set_keyframe): workspace item `item` (< max_batch), the
+// context's K and RANSAC settings, the point count read on the device.  The same launches as a lone pair's solve.
+void launch_pnp_item(svo_ctx *ctx, int item, const float *X3, const float2 *img, const int *n_pts, hipStream_t st)
+{
+    PnpArgs a{};
+    a.X3 = X3; a.img = img; a.stride = ctx->cfg.max_keypoints;
+    a.n_pts = n_pts; a.n_fixed = 0;
+    a.fx = ctx->cfg.P1[0]; a.fy = ctx->cfg.P1[5]; a.cx = ctx->cfg.P1[2]; a.cy = ctx->cfg.P1[6];
+    a.iterations = ctx->cfg.iterations; a.reproj_err = ctx->cfg.reproj_err;
+    a.first_cap = pnp_first_cap(ctx->cfg);
+    a.confidence = (double)ctx->cfg.confidence;
+    a.mask = (uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch) + (size_t)item * ctx->cfg.max_keypoints;
+    launch_pnp_pipeline(ctx, a, 1, ctx->cfg.max_keypoints, st, false, item);
+}
+const PnpRecord *pnp_record(const svo_ctx *ctx, int item) { return (const PnpRecord *)ctx->pnp_ws + item; }
 
 void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
                            const double *pose0_host, hipStream_t st)

@@ -429,6 +429,8 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
     }
     // svo_set_window_ba: the online chain's landmark table moves on by this pair and is adjusted; an applied result rewrites the record's pose
     if (ctx->win_step) SVO_TRY(window_fused_step(ctx, pose0_host, bs));
+    // svo_set_keyframe: the pair's tracks joined with the keyframe's table, one more solve, and where it is accepted its pose in the record
+    if (ctx->kf_step) SVO_TRY(keyframe_fused_step(ctx, pose0_host, bs));
     const int rc = deliver_records(ctx, ctx->d_results, n_pairs, results_dev, SVO_MEM_DEVICE, bs);
     if (rc) return rc;
     if (side) {
@@ -515,6 +517,7 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     ctx->carry_ids[cur] = ctx->carry_on;
     if (ctx->online_frames == 0) {
         ctx->win_clear = true; ctx->win_last = false;      // svo_set_window_ba, T1: a chain's first frame
+        ctx->kf_clear = true; ctx->kf_last = false;        // svo_set_keyframe, K1
         // StereoInit_f2f (:78-92): detect only
         SVO_TRY(count_read(ctx, ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur, &res->n_cur_kps));
         if (ctx->carry_on) {                     // svo_set_track_carry: the chain's first list gets its ids (the count above stays the detector's)
@@ -530,8 +533,10 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     }
     ctx->win_step = ctx->win_frames > 0 && ctx->carry_on;
     ctx->win_last = false; ctx->win_last_frames = ctx->win_frames;
+    ctx->kf_step = ctx->kf_on && ctx->carry_on;
+    ctx->kf_last = false;
     rc = run_pairs(ctx, 1, prev, cur, 0, ctx->pose, nullptr);
-    ctx->win_step = false;
+    ctx->win_step = false; ctx->kf_step = false;
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
     rc = deliver_records(ctx, ctx->d_results, 1, res, SVO_MEM_HOST, ctx->stream);

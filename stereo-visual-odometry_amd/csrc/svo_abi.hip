@@ -738,6 +738,7 @@ extern "C" int svo_reset(svo_ctx *ctx)
     ctx->online_frames = 0; ctx->online_cur = 0;
     ctx->carry_restart = true;                   // svo_set_track_carry: the next chain's ids start at 0
     ctx->win_clear = true;                       // svo_set_window_ba, T1
+    ctx->kf_clear = true;                        // svo_set_keyframe, K1
     for (int i = 0; i < 16; i++) ctx->pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
     return SVO_OK;
 }
@@ -754,6 +755,7 @@ extern "C" int svo_set_pose(svo_ctx *ctx, const double pose[16])
     if (!ctx || !pose) return SVO_ERR_ARG;
     memcpy(ctx->pose, pose, sizeof(double) * 16);
     ctx->win_clear = true;                       // svo_set_window_ba, T1: the window's poses belong to the chain that was
+    ctx->kf_clear = true;                        // svo_set_keyframe, K1: so does the keyframe's
     return SVO_OK;
 }
 
@@ -1127,6 +1129,7 @@ static int streams_step(svo_ctx *ctx, int w, int h, bool resize, const int32_t *
                         const uint8_t *rights, int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
 {
     if (ctx->win_frames > 0) { ctx->err = "the sliding window (svo_set_window_ba) works on the online chain only: stream sets have no table yet"; return SVO_ERR_STATE; }
+    if (ctx->kf_on) { ctx->err = "keyframe mode (svo_set_keyframe) works on the online chain only: stream sets have no keyframe yet"; return SVO_ERR_STATE; }
     SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
     SVO_ARG(stream_ids && lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
     SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
@@ -1693,6 +1696,7 @@ extern "C" int svo_set_track_carry(svo_ctx *ctx, int on, double min_distance, in
 {
     if (!ctx) return SVO_ERR_ARG;
     if (!on && ctx->win_frames > 0) { ctx->err = "the sliding window is on and needs track carry (svo_set_window_ba(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
+    if (!on && ctx->kf_on) { ctx->err = "keyframe mode is on and needs track carry (svo_set_keyframe(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
     if (!on) { ctx->carry_on = false; return SVO_OK; }               // off: the other arguments are ignored
     SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "track carry is an LK-mode option (ORB mode matches descriptors frame to frame)");
     SVO_ARG(carry_params_ok(min_distance, max_age), "min_distance must be finite and in [1, 256], max_age >= 0");
@@ -1700,6 +1704,7 @@ extern "C" int svo_set_track_carry(svo_ctx *ctx, int on, double min_distance, in
     SVO_TRY(carry_alloc(ctx));                                       // first enabling call: the working frames' and an existing stream set's share
     ctx->carry_on = true; ctx->carry_min_distance = min_distance; ctx->carry_max_age = max_age;
     ctx->win_clear = true;                                           // svo_set_window_ba, T1
+    ctx->kf_clear = true;                                            // svo_set_keyframe, K1
     return SVO_OK;
 }
 
@@ -1794,6 +1799,7 @@ extern "C" int svo_set_window_ba(svo_ctx *ctx, int frames, int rounds, int iters
     SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
     SVO_ARG(min_obs >= 1, "min_obs < 1");
     if (!ctx->carry_on) { ctx->err = "the sliding window needs track carry (svo_set_track_carry) on"; return SVO_ERR_STATE; }
+    if (ctx->kf_on) { ctx->err = "keyframe mode is on and rewrites the step's pose too (svo_set_keyframe(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
     SVO_TRY(window_alloc(ctx, frames));
     ctx->win_frames = frames; ctx->win_rounds = rounds; ctx->win_iters = iters; ctx->win_sigma = sigma_px; ctx->win_min_obs = min_obs;
     ctx->win_clear = true;
@@ -1837,6 +1843,74 @@ extern "C" int svo_window_ba(svo_ctx *ctx, const svo_window_table *table, int ca
 {
     if (!ctx) return SVO_ERR_ARG;
     return stage_window_ba(ctx, table, cap, P1, P2, rounds, iters, sigma_px, min_obs, res, mem);
+}
+
+// ---- keyframe-relative pose on the online chain (keyframe.hip: keyframe_join_kernel, keyframe_update_kernel) -----------------
+extern "C" int svo_set_keyframe(svo_ctx *ctx, int on, int min_tracks, int max_gap)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (!on) { ctx->kf_on = false; ctx->kf_clear = true; return SVO_OK; }                 // off: the other arguments are ignored
+    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "keyframe mode is an LK-mode option");
+    SVO_ARG(min_tracks >= 4 && min_tracks <= ctx->cfg.max_keypoints, "min_tracks outside 4..max_keypoints");
+    SVO_ARG(max_gap >= 0 && max_gap != 1, "max_gap must be 0 (no limit) or >= 2: the smallest gap of a solve is 2");
+    SVO_ARG(ctx->cfg.max_batch >= 2, "keyframe mode solves on item 1 of the pose workspace: max_batch must be >= 2");
+    if (!ctx->carry_on) { ctx->err = "keyframe mode needs track carry (svo_set_track_carry) on"; return SVO_ERR_STATE; }
+    if (ctx->win_frames > 0) { ctx->err = "the sliding window is on and rewrites the step's pose too (svo_set_window_ba(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
+    SVO_TRY(keyframe_alloc(ctx));
+    ctx->kf_on = true; ctx->kf_min_tracks = min_tracks; ctx->kf_max_gap = max_gap;
+    ctx->kf_clear = true;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_keyframe(const svo_ctx *ctx, int *on, int *min_tracks, int *max_gap)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    if (on) *on = ctx->kf_on ? 1 : 0;
+    if (min_tracks) *min_tracks = ctx->kf_on ? ctx->kf_min_tracks : 0;
+    if (max_gap) *max_gap = ctx->kf_on ? ctx->kf_max_gap : 0;
+    return SVO_OK;
+}
+
+// the read-backs' common start: the mode ran in the last online step, and that step is complete
+static int keyframe_last_step(svo_ctx *ctx)
+{
+    SVO_ARG(ctx->online_frames >= 2 && ctx->kf_last && ctx->kf_buf, "keyframe mode was off for the last svo_add_frame step, or no pair has been tracked (svo_set_keyframe)");
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_keyframe_result(svo_ctx *ctx, svo_keyframe_result *res)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(res, "null result");
+    SVO_TRY(keyframe_last_step(ctx));
+    return keyframe_read_result(ctx, res);
+}
+
+extern "C" int svo_get_keyframe_matches(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, svo_pt2f *xy, int32_t *trk_index, uint8_t *mask, int cap,
+                                        int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(n_out && cap >= 0, "null output");
+    SVO_TRY(keyframe_last_step(ctx));
+    return keyframe_read_matches(ctx, ids, X, xy, trk_index, mask, cap, n_out);
+}
+
+extern "C" int svo_get_keyframe_table(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, int cap, int *n_out)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    SVO_ARG(n_out && cap >= 0, "null output");
+    SVO_TRY(keyframe_last_step(ctx));
+    return keyframe_read_table(ctx, ids, X, cap, n_out);
+}
+
+extern "C" int svo_keyframe_join(svo_ctx *ctx, const int64_t *tab_ids, const svo_pt3f *tab_X, int n_rows, const int64_t *trk_ids,
+                                 const svo_pt2f *trk_xy, int n_trk, svo_pt3f *out_X, svo_pt2f *out_xy, int32_t *out_trk,
+                                 int32_t *out_row, int cap, int *n_out, int mem)
+{
+    if (!ctx) return SVO_ERR_ARG;
+    return stage_keyframe_join(ctx, tab_ids, tab_X, n_rows, trk_ids, trk_xy, n_trk, out_X, out_xy, out_trk, out_row, cap, n_out, mem);
 }
 
 // n ids and ages at `offset` of two device lists -> the caller's.  Capacity rule of the read-backs below: ids / ages null asks

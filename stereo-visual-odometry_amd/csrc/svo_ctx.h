@@ -237,6 +237,14 @@ struct svo_ctx {
     bool win_clear = true;                               // T1: the next step starts from a cleared table
     bool win_step = false;                               // set by pipeline_add_frame around its run_pairs: run_back runs the two kernels
     bool win_last = false; int win_last_frames = 0;      // the last online step ran them (with this W): what the read-backs return
+    // ---- keyframe-relative pose (svo_set_keyframe / svo_keyframe_join, keyframe.hip; off and nothing allocated until it is first enabled)
+    bool kf_on = false;
+    int kf_min_tracks = 60, kf_max_gap = 0;
+    uint8_t *kf_buf = nullptr;                           // ONE block: the chain's state, its table, the joined lists, the result
+    bool kf_clear = true;                                // K1: the next step starts without a keyframe
+    bool kf_step = false;                                // set by pipeline_add_frame around its run_pairs: run_back runs the keyframe stage
+    bool kf_last = false;                                // the last online step ran it: what the read-backs return
+    DevScratch kf_stage;                                 // svo_keyframe_join: the caller's lists and the outputs (HOST calls)
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -292,6 +300,8 @@ void launch_triangulate_batch(svo_ctx *ctx, int n_items, int max_pts, const floa
                               const int *n_pts, int n_fixed, const SnapSpec *snap = nullptr, hipStream_t st = nullptr);   // st null: the context's stream
 void launch_snap_counts(svo_ctx *ctx, int n_items, const SnapSpec &snap, hipStream_t st);
 void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n_pts, int n_fixed, hipStream_t st);
+void launch_pnp_item(svo_ctx *ctx, int item, const float *X3, const float2 *img, const int *n_pts, hipStream_t st);    // one more solve, workspace item `item`
+const PnpRecord *pnp_record(const svo_ctx *ctx, int item);
 // refine.hip: pose_refine_kernel, one workgroup per pair, on the records solvePnPRansac left in ctx->pnp_ws
 int refine_alloc(svo_ctx *ctx);                          // the stage's device block, on first use (waits for the device)
 void launch_refine_batch(svo_ctx *ctx, int n_pairs, hipStream_t st);
@@ -356,6 +366,15 @@ int window_read(svo_ctx *ctx, const svo_window_table *out, int cap);
 int window_read_result(svo_ctx *ctx, svo_window_result *res);
 int stage_window_ba(svo_ctx *ctx, const svo_window_table *tab, int cap, const double *P1, const double *P2, int rounds, int iters,
                     double sigma_px, int min_obs, svo_window_result *res, int mem);
+// keyframe.hip: the keyframe stage of the online chain and the join kernel on a caller's arrays
+int keyframe_alloc(svo_ctx *ctx);
+int keyframe_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st);
+int keyframe_read_result(svo_ctx *ctx, svo_keyframe_result *res);
+int keyframe_read_matches(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, svo_pt2f *xy, int32_t *trk_index, uint8_t *mask, int cap, int *n_out);
+int keyframe_read_table(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, int cap, int *n_out);
+int stage_keyframe_join(svo_ctx *ctx, const int64_t *tab_ids, const svo_pt3f *tab_X, int n_rows, const int64_t *trk_ids,
+                        const svo_pt2f *trk_xy, int n_trk, svo_pt3f *out_X, svo_pt2f *out_xy, int32_t *out_trk, int32_t *out_row,
+                        int cap, int *n_out, int mem);
 int carry_alloc(svo_ctx *ctx);                           // track carry: its block and, for an existing stream set, the store's share
 int pipeline_streams_create(svo_ctx *ctx, int n_streams);
 int pipeline_streams_reset(svo_ctx *ctx, int id);

@@ -87,6 +87,23 @@ __device__ inline int block1024_excl_scan(int v, int *wave_tot, int &total)
     return pre + inc - v;
 }
 
+// the same for a predicate (keyframe.hip): the number of lanes before this one, in a workgroup of 1024, where p holds -- one
+// ballot per wave, the bits below the lane, the totals of the waves before it.  wave_tot: 16 ints of LDS; total: the count.
+// (two barriers)
+__device__ inline int block1024_ballot_rank(bool p, int *wave_tot, int &total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(p);
+    if (lane == 0) wave_tot[wv] = __popcll(m);
+    __syncthreads();
+    int pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) { const int t = wave_tot[k]; if (k < wv) pre += t; tot += t; }
+    __syncthreads();
+    total = tot;
+    return pre + __popcll(m & ((1ull << lane) - 1ull));
+}
+
 // the wave's sum of v in every lane: a butterfly, so the additions' order (part of the results) is the same for all lanes
 __device__ inline double wave_allsum_f64(double v)
 {

@@ -71,6 +71,7 @@ public:
     const std::string &YamlTracksFile() const { return yaml_tracks_file_; }
     static void DeferYamlOutputs(bool on) { s_defer_yaml_outputs = on; }
     int BatchSize() const { return batch_size_; }
+    bool Keyframe() const { return tracking_ && tracking_->Keyframe(); }          // YAML key keyframe: 1 (the per-frame loop only)
     bool TrackCarry() const { return tracking_ && tracking_->TrackCarry(); }      // YAML key track_carry: 1 (per-frame paths only)
     bool Failed() const { return run_failed_; }
     void CloseOutputs();                                     // flushes and closes the pose / tracks files, waits for the device (fast exit)              // a stream / batch submission failed: the pose file is short

@@ -86,6 +86,14 @@ public:
     // and window_ba_min_obs (10): the sliding-window bundle adjustment of the per-frame chain (svo_set_window_ba).  Refused like
     // the keys above: W outside 0, 2..8, values outside svo_set_window_ba's ranges, and window_ba without track_carry: 1.
     static bool ReadWindowBa(int *frames, int *rounds, int *iters, double *sigma, int *min_obs, std::string *err);
+    // additive YAML keys keyframe: 0 | 1 (absent: 0) and keyframe_max_gap (0 = no limit; else >= 2): the keyframe-relative pose of
+    // the per-frame chain (svo_set_keyframe); the tracks a solve needs come from the reference's own key
+    // num_features_needed_for_keyframe.  Refused like the keys above: a switch that is neither 0 nor 1, a gap that is negative or
+    // 1, keyframe: 1 without track_carry: 1 or together with window_ba (both rewrite the pose), or with
+    // num_features_needed_for_keyframe < 4.  System refuses it together with batch_size > 1, stream_depth > 0, --split-pairs and
+    // --interleave.
+    static bool ReadKeyframe(int *on, int *min_tracks, int *max_gap, std::string *err);
+    bool Keyframe() const { return keyframe_ != 0; }
     bool TrackCarry() const { return track_carry_ != 0; }
     // id and age at t1 of every track GetLastTracks returns, in its order (track carry on; false otherwise)
     bool GetLastTrackIds(std::vector<int64_t> &ids, std::vector<int32_t> &ages);
@@ -154,6 +162,7 @@ private:
     int orb_matcher_ = SVO_ORB_MATCHER_BRUTE, orb_match_th_stereo_ = 75, orb_match_th_track_ = 100;                     // orb_matcher / orb_match_*
     double orb_match_ratio_ = 0.9, orb_match_radius_ = 0.0, orb_max_disparity_ = 0.0;
     int window_ba_ = 0, window_ba_rounds_ = 4, window_ba_iters_ = 5, window_ba_min_obs_ = 10; double window_ba_sigma_ = 1.0;   // additive YAML keys window_ba*
+    int keyframe_ = 0, keyframe_min_tracks_ = 60, keyframe_max_gap_ = 0;     // additive YAML keys keyframe / keyframe_max_gap (+ num_features_needed_for_keyframe)
     int track_carry_ = 0, track_carry_max_age_ = 0;          // additive YAML keys track_carry / track_carry_max_age
     double track_carry_min_distance_ = 3.0;                  // ... and track_carry_min_distance
     int lk_accum_ = SVO_LK_ACCUM_EXACT;                      // additive YAML key lk_accum: exact (default) | sse2 | simd128

@@ -360,6 +360,12 @@ System::System(std::string &config_path) : config_file_path_(config_path)
     batch_size_ = Config::Has("batch_size") ? Config::Get<int>("batch_size") : 1;
     decode_threads_ = Config::Has("decode_threads") ? Config::Get<int>("decode_threads") : 0;    // 0: the usable cores
     stream_depth_ = Config::Has("stream_depth") ? Config::Get<int>("stream_depth") : 0;           // 0: Step_ros is synchronous
+    // keyframe: 1 belongs to the per-frame chain alone (svo_set_keyframe); named before track_carry, which it implies
+    if (tracking_->Keyframe() && (batch_size_ > 1 || stream_depth_ > 0)) {
+        fprintf(stderr, "%s: keyframe: 1 with %s (the keyframe belongs to the per-frame loop; a batch treats its pairs as independent)\n",
+                config_file_path_.c_str(), batch_size_ > 1 ? "batch_size > 1" : "stream_depth > 0");
+        exit(2);
+    }
     // track_carry is a feature of the per-frame paths: a batch treats its pairs as independent (svo_set_track_carry)
     if (tracking_->TrackCarry() && (batch_size_ > 1 || stream_depth_ > 0)) {
         fprintf(stderr, "%s: track_carry: 1 with %s (tracks are carried by the per-frame loop and --interleave only; a batch treats "
@@ -931,6 +937,11 @@ int RunSplitPairs(const std::string &yaml, const std::string &pose_file, int n_p
     const int n_pairs = n_frames - 1;
     const int default_batch = probe->BatchSize() > 1 ? probe->BatchSize() : 256;
     const std::string out_path = !pose_file.empty() ? pose_file : probe->YamlPoseFile();
+    if (probe->Keyframe()) {
+        System::DeferYamlOutputs(false);
+        fprintf(stderr, "%s: keyframe: 1 with --split-pairs (the chunks are tracked as batches of independent pairs)\n", yaml.c_str());
+        exit(2);
+    }
     if (probe->TrackCarry()) {
         System::DeferYamlOutputs(false);
         fprintf(stderr, "%s: track_carry: 1 with --split-pairs (the chunks are tracked as batches of independent pairs)\n", yaml.c_str());

@@ -169,6 +169,10 @@ int RunInterleaved(const std::vector<std::string> &yamls, const std::vector<std:
         int wf, wr, wi, wm; double ws;
         if (!Tracking::ReadWindowBa(&wf, &wr, &wi, &ws, &wm, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
         if (wf) { fprintf(stderr, "--interleave: %s: window_ba: %d with --interleave (the sliding window works on the per-frame chain only)\n", yamls[0].c_str(), wf); return 2; }
+        // ... and keyframe: like the window, the keyframe belongs to the per-frame chain
+        int kon, kmt, kgap;
+        if (!Tracking::ReadKeyframe(&kon, &kmt, &kgap, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
+        if (kon) { fprintf(stderr, "--interleave: %s: keyframe: 1 with --interleave (keyframe mode works on the per-frame chain only)\n", yamls[0].c_str()); return 2; }
         if (!Tracking::ReadOrbMatcher(&mmode, &mts, &mtt, &mra, &mrd, &mmd, &err)) { fprintf(stderr, "--interleave: %s: %s\n", yamls[0].c_str(), err.c_str()); return 2; }
     }
     for (int s = 0; s < n; s++) {

@@ -156,6 +156,25 @@ bool Tracking::ReadWindowBa(int *frames, int *rounds, int *iters, double *sigma,
     return true;
 }
 
+bool Tracking::ReadKeyframe(int *on, int *min_tracks, int *max_gap, std::string *err)
+{
+    *on = 0; *min_tracks = 60; *max_gap = 0;
+    const int k = Config::Has("keyframe") ? Config::Get<int>("keyframe") : 0;
+    const int g = Config::Has("keyframe_max_gap") ? Config::Get<int>("keyframe_max_gap") : 0;
+    const int mt = Config::Has("num_features_needed_for_keyframe") ? Config::Get<int>("num_features_needed_for_keyframe") : 60;
+    const int carry = Config::Has("track_carry") ? Config::Get<int>("track_carry") : 0;
+    const int window = Config::Has("window_ba") ? Config::Get<int>("window_ba") : 0;
+    char msg[240] = "";
+    if (k != 0 && k != 1) snprintf(msg, sizeof(msg), "keyframe: %d is neither 0 nor 1", k);
+    else if (g < 0 || g == 1) snprintf(msg, sizeof(msg), "keyframe_max_gap: %d is neither 0 (no limit) nor >= 2 (the smallest gap of a keyframe solve is 2)", g);
+    else if (k == 1 && carry != 1) snprintf(msg, sizeof(msg), "keyframe: 1 without track_carry: 1 (the keyframe's points are found again by their carried ids)");
+    else if (k == 1 && window != 0) snprintf(msg, sizeof(msg), "keyframe: 1 with window_ba: %d (both rewrite the step's pose: choose one)", window);
+    else if (k == 1 && mt < 4) snprintf(msg, sizeof(msg), "keyframe: 1 with num_features_needed_for_keyframe: %d (a keyframe solve needs at least 4 tracks)", mt);
+    if (msg[0]) { if (err) *err = msg; return false; }
+    *on = k; *min_tracks = mt; *max_gap = g;
+    return true;
+}
+
 bool Tracking::G2O_EstimatePose_PnP(const double projMatrl[12], const double projMatrr[12], const std::vector<cv::Point2f> &pointsLeft_t2,
                                     const std::vector<cv::Point2f> *pointsRight_t2, const std::vector<cv::Point3f> &points3D_t0,
                                     double rotation[3], double translation[3], svo_refine_result *result)
@@ -226,6 +245,11 @@ Tracking::Tracking(System *system, Parameter::Ptr parameter, Sensors::Ptr sensor
     } else if (window_ba_)
         LZB_LOG("INFO", "window_ba: %d (window_ba_rounds %d, window_ba_iters %d, window_ba_sigma %g, window_ba_min_obs %d)", window_ba_,
                 window_ba_rounds_, window_ba_iters_, window_ba_sigma_, window_ba_min_obs_);
+    std::string keyframe_error;
+    if (!ReadKeyframe(&keyframe_, &keyframe_min_tracks_, &keyframe_max_gap_, &keyframe_error)) {
+        if (config_error_.empty()) config_error_ = keyframe_error;
+    } else if (keyframe_)
+        LZB_LOG("INFO", "keyframe: 1 (num_features_needed_for_keyframe %d, keyframe_max_gap %d)", keyframe_min_tracks_, keyframe_max_gap_);
     std::string matcher_error;
     if (!ReadOrbMatcher(&orb_matcher_, &orb_match_th_stereo_, &orb_match_th_track_, &orb_match_ratio_, &orb_match_radius_,
                         &orb_max_disparity_, &matcher_error)) {
@@ -292,7 +316,7 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
     if (Ingest()) { width = (int)std::nearbyint(src_w * image_scale_); height = (int)std::nearbyint(src_h * image_scale_); }
     svo_config cfg;
     svo_default_config(&cfg, width, height);
-    cfg.max_batch = max_batch;
+    cfg.max_batch = keyframe_ && max_batch < 2 ? 2 : max_batch;      // keyframe: 1 solves on item 1 of the pose workspace (svo_set_keyframe)
     // cv::FAST is uncapped in the reference; the device buffers are not.  Capacity per image: the additive
     // YAML key max_keypoints, else one keypoint per 24 pixels (NMS keeps at most one corner per 3x3
     // block; textured KITTI frames hold 2-5 k, i.e. one per ~100-200 pixels), never less than 8192 or
@@ -393,6 +417,13 @@ bool Tracking::EnsureContext(int width, int height, int max_batch)
     }
     if (window_ba_ && (rc = svo_set_window_ba(ctx_, window_ba_, window_ba_rounds_, window_ba_iters_, window_ba_sigma_, window_ba_min_obs_)) != SVO_OK) {
         LZB_LOG("ERROR", "svo_set_window_ba (window_ba %d) failed (%d): %s", window_ba_, rc, svo_last_error(ctx_));
+        svo_destroy(ctx_);
+        ctx_ = nullptr;
+        return false;
+    }
+    if (keyframe_ && (rc = svo_set_keyframe(ctx_, 1, keyframe_min_tracks_, keyframe_max_gap_)) != SVO_OK) {
+        LZB_LOG("ERROR", "svo_set_keyframe (keyframe 1, num_features_needed_for_keyframe %d, keyframe_max_gap %d) failed (%d): %s",
+                keyframe_min_tracks_, keyframe_max_gap_, rc, svo_last_error(ctx_));
         svo_destroy(ctx_);
         ctx_ = nullptr;
         return false;
