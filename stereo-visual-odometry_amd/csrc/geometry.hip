@@ -1,8 +1,7 @@
-// geometry.hip -- triangulation, RANSAC-EPnP + Levenberg-Marquardt pose solver, motion gates and
-// pose chaining for gfx950; replaces cv::triangulatePoints / cv::convertPointsFromHomogeneous
-// (reference src/tracking.cpp:292-294), cv::solvePnPRansac + cv::Rodrigues (:485-488) and the
-// gating / accumulation code (:305-329, 440-463).  "g2o" in the reference is link-only; the live
-// solver is the one restated here.
+// geometry.hip -- triangulation and the RANSAC-EPnP + Levenberg-Marquardt pose solver for gfx950; replaces
+// cv::triangulatePoints / cv::convertPointsFromHomogeneous (reference src/tracking.cpp:292-294) and cv::solvePnPRansac +
+// cv::Rodrigues (:485-488).  "g2o" in the reference is link-only; the live solver is the one restated here (SURVEY.md
+// section 0 fact 2).  What follows a solve -- the motion gates and the pose chain -- is pose_chain.hip.
 //
 // Kernels
 //   triangulate_kernel : one thread per point, 4x4 DLT + one-sided Jacobi SVD in f64.
@@ -13,8 +12,7 @@
 //       winner, adaptive stop and mask; the cv::RNG multiply-with-carry sequence, seed 2^64-1, is
 //       drawn serially); LM refit on the inliers with 256 threads per pair.  Details above
 //       struct PnpRecord.
-//   finalize_kernel    : per pair failure staging, Euler / translation gates, inv([R t;0 1]).
-//   chain_kernel       : frame_pose_ *= T^-1 over the batch, skipping failed steps.
+//   snap_counts_kernel : the keypoint counts of a batch's frames, frozen for the pose stage's gates.
 #include <cstring>
 #include <cstdlib>
 #include "abi_io.h"
@@ -799,261 +797,28 @@ __global__ __launch_bounds__(kRefitThreads) void pnp_refit_kernel(PnpArgs a)
 }
 
 // ------------------------------------------------------------------------------------------
-struct FinalizeArgs {
-    const PnpRecord *pnp; const int *n_prev, *n_cur, *n_tracked;   // per pair
-    const int *ovf;                // per pair (ORB mode): an image of the pair overflowed a capacity; may be null
-    int n_pairs;
-    int mode;                      // SVO_MODE_LK checks "< 30 FAST corners" first (src/tracking.cpp:261)
-    int cap;                       // max_keypoints: a frame with more corners was truncated -> SVO_FAIL_CAPACITY
-    int num_features_tracking; double inlier_rate, min_move2, max_move2;
-    svo_step_result *res;
-};
-
-__device__ inline void finalize_pair(const FinalizeArgs &a, int p)
-{
-    svo_step_result r;
-    const PnpRecord &q = a.pnp[p];
-    r.n_prev_kps = a.n_prev[p]; r.n_cur_kps = a.n_cur[p];
-    r.n_tracked = 0; r.n_inliers = 0; r.ransac_iters = 0; r.lm_iters = 0;
-    for (int i = 0; i < 3; i++) { r.rvec[i] = 0; r.tvec[i] = 0; }
-    for (int i = 0; i < 9; i++) r.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int i = 0; i < 16; i++) { r.T_rel_inv[i] = (i % 5 == 0) ? 1.0 : 0.0; r.pose[i] = 0; }
-    int fail = 0;
-    if (r.n_prev_kps > a.cap || r.n_cur_kps > a.cap || (a.ovf && a.ovf[p])) fail = SVO_FAIL_CAPACITY;   // never silently track a truncated set
-    else if (a.mode == SVO_MODE_LK && r.n_cur_kps < 30) fail = SVO_FAIL_FEW_KEYPOINTS;     // src/tracking.cpp:261
-    else {
-        const int m = a.n_tracked[p];
-        r.n_tracked = m;
-        if (m < a.num_features_tracking) fail = SVO_FAIL_FEW_TRACKS;         // :274
-        else {
-            r.n_inliers = q.n_inliers; r.ransac_iters = q.ransac_iters; r.lm_iters = q.lm_iters;
-            for (int i = 0; i < 3; i++) { r.rvec[i] = q.rvec[i]; r.tvec[i] = q.tvec[i]; }
-            for (int i = 0; i < 9; i++) r.R[i] = q.R[i];
-            if ((double)q.n_inliers / (double)m < a.inlier_rate) fail = SVO_FAIL_INLIER_RATIO;   // :491
-            else {
-                // rotationMatrixToEulerAngles (:440-463): floats holding double expressions
-                const double *R = q.R;
-                const float sy = (float)sqrt(R[0] * R[0] + R[3] * R[3]);
-                const bool singular = (double)sy < 1e-6;
-                float ex, ey, ez;
-                if (!singular) {
-                    ex = (float)atan2(R[7], R[8]); ey = (float)atan2(-R[6], (double)sy); ez = (float)atan2(R[3], R[0]);
-                } else {
-                    ex = (float)atan2(-R[5], R[4]); ey = (float)atan2(-R[6], (double)sy); ez = 0.f;
-                }
-                if (!((double)fabsf(ey) < 0.1 && (double)fabsf(ex) < 0.1 && (double)fabsf(ez) < 0.1))
-                    fail = SVO_FAIL_ROTATION_GATE;                           // :308
-                else {
-                    const double *t = q.tvec;
-                    const double n2 = t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
-                    if (!(n2 < a.max_move2 && n2 > a.min_move2)) fail = SVO_FAIL_TRANSL_GATE;   // :311
-                    else {
-                        double *Ti = r.T_rel_inv;      // inv([R t; 0 1]) in closed form
-                        Ti[0] = R[0]; Ti[1] = R[3]; Ti[2] = R[6];
-                        Ti[4] = R[1]; Ti[5] = R[4]; Ti[6] = R[7];
-                        Ti[8] = R[2]; Ti[9] = R[5]; Ti[10] = R[8];
-                        Ti[3] = -(R[0] * t[0] + R[3] * t[1] + R[6] * t[2]);
-                        Ti[7] = -(R[1] * t[0] + R[4] * t[1] + R[7] * t[2]);
-                        Ti[11] = -(R[2] * t[0] + R[5] * t[1] + R[8] * t[2]);
-                        Ti[12] = 0; Ti[13] = 0; Ti[14] = 0; Ti[15] = 1;
-                    }
-                }
-            }
-        }
-    }
-    r.fail_stage = fail;
-    r.ok = fail == 0;
-    a.res[p] = r;
-}
-
-// frame_pose_ = frame_pose_ * T^-1 over consecutive pairs; failed steps are skipped (:59-68).
-// The seed pose travels BY VALUE in the kernel argument block: a launch queued behind many others
-// (callers of svo_track_batch with device results never synchronise) keeps the seed it was given.
-// One wave: lanes (i, j) hold P[i][j], row elements travel by quad DPP broadcast (see
-// chain_relative_kernel below: same association order -- k ascending, separate multiply and add --
-// as a plain triple loop, so chunked and whole-sequence chaining agree bit for bit).
-struct Pose16 { double m[16]; };
-template <int K>
-__device__ __forceinline__ double quad_bcast_f64(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), K * 0x55, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), K * 0x55, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// The gates of every pair, then the chain, in ONE launch of one workgroup (the pose stage ends with it: two launches were
-// 10 us of a lone pair's 750).  ONE WAVE (round 6): the launch is queued on the side stream while the NEXT batch's LK grid
-// fills the chip; behind lk_sse2_kernel's single-wave workgroups (two a SIMD, all 160 KB of LDS) wave slots come free one at
-// a time, and a four-wave workgroup never found four at once until that grid drained -- the poses of a batch arrived up to a
-// whole LK launch (20 ms) late (profiles/r06_sse2_timeline_before.csv).  A lone wave takes the first slot that frees; the 256
-// pairs of a batch are four trips of finalize_pair instead of one.
-constexpr int kFinThreads = 64;
-__global__ __launch_bounds__(kFinThreads) void finalize_chain_kernel(FinalizeArgs a, Pose16 pose0, const double *seed_dev)
-{
-    __shared__ double sT[64 * 16];
-    __shared__ int sOk[64];
-    for (int p = threadIdx.x; p < a.n_pairs; p += kFinThreads) finalize_pair(a, p);
-    __threadfence_block();
-    svo_step_result *res = a.res;
-    const int n_pairs = a.n_pairs;
-    const int lane = threadIdx.x & 63, i = (lane >> 2) & 3, j = lane & 3;
-    const bool first = true;
-    double P = seed_dev ? seed_dev[i * 4 + j] : pose0.m[i * 4 + j];     // device seed: the previous batch's last pose
-    for (int base = 0; base < n_pairs; base += 64) {
-        // the records of 64 pairs are fetched together (one dependent global load per pair made the
-        // serial product cost a memory round trip per step)
-        const int cnt = min(64, n_pairs - base);
-        __syncthreads();
-        if (first) {
-            for (int e = lane; e < cnt * 16; e += 64) sT[e] = res[base + (e >> 4)].T_rel_inv[e & 15];
-            if (lane < cnt) sOk[lane] = res[base + lane].ok;
-        }
-        __syncthreads();
-        if (!first) continue;
-        for (int p = 0; p < cnt; p++) {
-            const double p0 = quad_bcast_f64<0>(P), p1 = quad_bcast_f64<1>(P), p2 = quad_bcast_f64<2>(P), p3 = quad_bcast_f64<3>(P);
-            if (sOk[p]) {
-                const double *t = sT + p * 16 + j;
-                double s = 0;
-                s += p0 * t[0]; s += p1 * t[4]; s += p2 * t[8]; s += p3 * t[12];
-                P = s;
-            }
-            if (lane < 16) res[base + p].pose[lane] = P;
-        }
-    }
-}
-
-// The pose stage of a stream-set step (svo_streams_step): the pairs of one launch belong to DIFFERENT streams, so nothing is
-// chained along the batch.  finalize_pair decides the gates exactly as for a batch; then pose_s = pose_s * T_rel_inv per stream,
-// read from and written to the stream store on the device (a queued step depends on no host memory), 16 lanes per stream, four
-// streams per wave, one wave per workgroup; the association order is the chain's (k ascending, separate multiply and add).
-// A stream whose first frame this is gets the StereoInit_f2f record (src/tracking.cpp:78-92) instead: detect only, ok = 1.
-constexpr int kFinStreams = 4;                          // streams per workgroup
-__global__ __launch_bounds__(64) void finalize_streams_kernel(FinalizeArgs a, int item0, StreamTable tab, double *pose_store)
-{
-    const int g = threadIdx.x >> 4, e = threadIdx.x & 15, i = e >> 2, j = e & 3;
-    const int t = blockIdx.x * kFinStreams + g;         // entry of this launch's table
-    const int p = item0 + t;                            // item of the step
-    const bool live = t < kStreamChunk && p < a.n_pairs;
-    const bool init = live && tab.init[t] != 0;
-    if (live && e == 0) {
-        if (!init) finalize_pair(a, p);
-        else {
-            svo_step_result r;
-            r.ok = 1; r.fail_stage = 0;
-            r.n_prev_kps = 0; r.n_cur_kps = a.n_cur[p]; r.n_tracked = 0; r.n_inliers = 0; r.ransac_iters = 0; r.lm_iters = 0;
-            for (int k = 0; k < 3; k++) { r.rvec[k] = 0; r.tvec[k] = 0; }
-            for (int k = 0; k < 9; k++) r.R[k] = (k % 4 == 0) ? 1.0 : 0.0;
-            for (int k = 0; k < 16; k++) { r.T_rel_inv[k] = (k % 5 == 0) ? 1.0 : 0.0; r.pose[k] = 0; }
-            a.res[p] = r;
-        }
-    }
-    __threadfence_block();
-    __syncthreads();                                    // the record lane 0 wrote is visible to the 16 lanes of its stream
-    double out = 0;
-    if (live) {
-        const svo_step_result *r = a.res + p;
-        const double *P = pose_store + (size_t)tab.id[t] * 16;
-        out = P[e];
-        if (!init && r->ok) {
-            const double p0 = P[i * 4 + 0], p1 = P[i * 4 + 1], p2 = P[i * 4 + 2], p3 = P[i * 4 + 3];
-            const double *T = r->T_rel_inv + j;
-            double s = 0;
-            s += p0 * T[0]; s += p1 * T[4]; s += p2 * T[8]; s += p3 * T[12];
-            out = s;
-        }
-    }
-    __syncthreads();                                    // every lane has read the old pose before any writes the new one
-    if (live) {
-        a.res[p].pose[e] = out;
-        pose_store[(size_t)tab.id[t] * 16 + e] = out;
-    }
-}
-
-__global__ __launch_bounds__(256) void streams_set_pose_kernel(double *pose_store, int n, Pose16 pose)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k < n * 16) pose_store[k] = pose.m[k & 15];
-}
-
-// The same product for relative motions gathered from independently tracked chunks (other
-// launches, contexts or GPUs): lanes (i, j) of one wave hold P[i][j]; row elements travel by quad
-// broadcast, the T matrices are staged through LDS 64 pairs at a time.  Same association order
-// as chain_kernel (k ascending, separate multiply and add).
-
-__global__ __launch_bounds__(64) void chain_relative_kernel(const double *T, const int *ok, int n, Pose16 pose0,
-                                                            double *out)
-{
-    __shared__ double sT[64 * 16];
-    __shared__ int sOk[64];
-    const int lane = threadIdx.x, i = (lane >> 2) & 3, j = lane & 3;
-    double P = pose0.m[i * 4 + j];
-    for (int base = 0; base < n; base += 64) {
-        const int cnt = min(64, n - base);
-        __syncthreads();
-        for (int e = lane; e < cnt * 16; e += 64) sT[e] = T[(int64_t)base * 16 + e];
-        if (lane < cnt) sOk[lane] = ok[base + lane];
-        __syncthreads();
-        for (int p = 0; p < cnt; p++) {
-            const double p0 = quad_bcast_f64<0>(P), p1 = quad_bcast_f64<1>(P), p2 = quad_bcast_f64<2>(P), p3 = quad_bcast_f64<3>(P);
-            if (sOk[p]) {
-                const double *t = sT + p * 16 + j;
-                double s = 0;
-                s += p0 * t[0]; s += p1 * t[4]; s += p2 * t[8]; s += p3 * t[12];
-                P = s;
-            }
-            if (lane < 16) out[(int64_t)(base + p) * 16 + lane] = P;
-        }
-    }
-}
-
-int stage_chain_relative(svo_ctx *ctx, const double *T, const int32_t *ok, int n, const double *pose0_host, double *out,
-                         int mem)
-{
-    SVO_ARG(T && ok && out && n >= 0, "null pointer / negative count");
-    SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "bad mem");
-    if (n == 0) return SVO_OK;
-    Pose16 p0;                                     // travels as a kernel argument: no copy, no allocation
-    for (int q = 0; q < 16; q++) p0.m[q] = pose0_host ? pose0_host[q] : (q % 5 == 0 ? 1.0 : 0.0);
-    // host operands: temporaries released on every exit path (device operands: stream-ordered, nothing allocated or waited for)
-    struct DevBuf {
-        void *p = nullptr;
-        ~DevBuf() { if (p) (void)hipFree(p); }
-    } bT, bOut, bOk;
-    if (mem == SVO_MEM_HOST) {
-        SVO_HIP(hipMalloc(&bT.p, sizeof(double) * 16 * (size_t)n));
-        SVO_HIP(hipMalloc(&bOut.p, sizeof(double) * 16 * (size_t)n));
-        SVO_HIP(hipMalloc(&bOk.p, sizeof(int) * (size_t)n));
-    }
-    const double *dT;
-    const int *dOk;
-    SVO_TRY(to_device(ctx, T, (double *)bT.p, (size_t)16 * n, mem, &dT));
-    SVO_TRY(to_device(ctx, (const int *)ok, (int *)bOk.p, (size_t)n, mem, &dOk));
-    double *dOut = mem == SVO_MEM_HOST ? (double *)bOut.p : out;
-    hipLaunchKernelGGL(chain_relative_kernel, dim3(1), dim3(64), 0, ctx->stream, dT, dOk, n, p0, dOut);
-    SVO_HIP(hipGetLastError());
-    SVO_TRY(from_device(ctx, out, (const double *)dOut, (size_t)16 * n, mem));
-    return io_done(ctx, mem);
-}
-
-// ------------------------------------------------------------------------------------------
 // workspace layout inside ctx->pnp_ws (n = max_batch items):
 //   [PnpRecord x n][mask bytes x n*cap][PnpState x n][PnpHyp x n*512][counts x n*512][subsets x n*2*512*5]
 //   [EPnP hand-over records x n * 8 blocks * 105 * 64 doubles][cv::RNG(-1) states x kRngStream]
 // (kPhaseHyps = 512 hypotheses per phase in kPhaseBlocks = 8 blocks of 64.)  The hand-over records are the large part:
 // 430 KB per item, 110 MB for a 256-pair context, in BOTH modes -- a later phase of an LK-mode solve launches all eight
 // blocks too.  INTEGRATION.md lists a context's device memory.
-static size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-static size_t ws_off_mask(int n_items) { return al256(sizeof(PnpRecord) * (size_t)n_items); }
-static size_t ws_off_state(const svo_config &cfg, int n_items) { return al256(ws_off_mask(n_items) + (size_t)n_items * cfg.max_keypoints); }
-static size_t ws_off_hyp(const svo_config &cfg, int n_items) { return al256(ws_off_state(cfg, n_items) + sizeof(PnpState) * (size_t)n_items); }
-static size_t ws_off_counts(const svo_config &cfg, int n_items) { return al256(ws_off_hyp(cfg, n_items) + sizeof(PnpHyp) * (size_t)n_items * kPhaseHyps); }
-static size_t ws_off_subsets(const svo_config &cfg, int n_items) { return al256(ws_off_counts(cfg, n_items) + sizeof(int) * (size_t)n_items * kPhaseHyps); }
-static size_t ws_off_hand(const svo_config &cfg, int n_items) { return al256(ws_off_subsets(cfg, n_items) + sizeof(int) * 2 * 5 * (size_t)n_items * kPhaseHyps); }
-static size_t ws_off_stream(const svo_config &cfg, int n_items) { return al256(ws_off_hand(cfg, n_items) + sizeof(double) * (size_t)n_items * kPhaseBlocks * kEpnpHandDoubles * 64); }
-static size_t ws_end(const svo_config &cfg, int n_items) { return al256(ws_off_stream(cfg, n_items) + sizeof(uint64_t) * kRngStream); }
+struct PnpCut { size_t rec, mask, state, hyp, counts, subsets, hand, stream, total; };
+static PnpCut pnp_cut(const svo_config &cfg, int n_items)
+{
+    const size_t n = (size_t)n_items;
+    BlockCut cut; PnpCut c;
+    c.rec = cut.add(sizeof(PnpRecord) * n); c.mask = cut.add(n * cfg.max_keypoints); c.state = cut.add(sizeof(PnpState) * n);
+    c.hyp = cut.add(sizeof(PnpHyp) * n * kPhaseHyps); c.counts = cut.add(sizeof(int) * n * kPhaseHyps);
+    c.subsets = cut.add(sizeof(int) * 2 * 5 * n * kPhaseHyps); c.hand = cut.add(sizeof(double) * n * kPhaseBlocks * kEpnpHandDoubles * 64);
+    c.stream = cut.add(sizeof(uint64_t) * kRngStream); c.total = cut.total() + 256;
+    return c;
+}
+static PnpCut pnp_cut(const svo_ctx *ctx) { return pnp_cut(ctx->cfg, ctx->cfg.max_batch); }     // the context's workspace
 
 // RANSAC inlier flags of batch item 0 (the online pair): max_keypoints bytes
-const uint8_t *pnp_inlier_mask(const svo_ctx *ctx) { return (const uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch); }
+const uint8_t *pnp_inlier_mask(const svo_ctx *ctx) { return (const uint8_t *)ctx->pnp_ws + pnp_cut(ctx).mask; }
+const PnpRecord *pnp_record(const svo_ctx *ctx, int item) { return (const PnpRecord *)ctx->pnp_ws + item; }
 
 int geom_workspace_bytes(const svo_config &cfg, int n_items, size_t *bytes)
 {
@@ -1069,7 +834,7 @@ int geom_workspace_bytes(const svo_config &cfg, int n_items, size_t *bytes)
     if (hipFuncSetAttribute((const void *)pnp_refit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kRefitLdsBytes) != hipSuccess)
         return SVO_ERR_HIP;
-    *bytes = ws_end(cfg, n_items) + 256;
+    *bytes = pnp_cut(cfg, n_items).total;
     return SVO_OK;
 }
 
@@ -1079,7 +844,7 @@ int geom_workspace_init(svo_ctx *ctx)
     std::vector<uint64_t> st(kRngStream);
     uint64_t x = ~0ull;
     for (int i = 0; i < kRngStream; i++) { x = (uint64_t)(uint32_t)x * 4164903690u + (uint32_t)(x >> 32); st[i] = x; }
-    if (hipMemcpy((char *)ctx->pnp_ws + ws_off_stream(ctx->cfg, ctx->cfg.max_batch), st.data(), sizeof(uint64_t) * kRngStream,
+    if (hipMemcpy((char *)ctx->pnp_ws + pnp_cut(ctx).stream, st.data(), sizeof(uint64_t) * kRngStream,
                   hipMemcpyHostToDevice) != hipSuccess)
         return SVO_ERR_HIP;
     return SVO_OK;
@@ -1090,16 +855,15 @@ int geom_workspace_init(svo_ctx *ctx)
 // item0: the workspace item the first of the n_items solves uses (the caller's X3 / img / mask / n_pts are item item0's).
 static void launch_pnp_pipeline(svo_ctx *ctx, PnpArgs a, int n_items, int max_pts, hipStream_t st, bool begun = false, int item0 = 0)
 {
-    const svo_config &cfg = ctx->cfg;
     char *ws = (char *)ctx->pnp_ws;
-    const int B = cfg.max_batch;
-    a.out = (PnpRecord *)ws + item0;
-    a.state = (PnpState *)(ws + ws_off_state(cfg, B)) + item0;
-    a.hyp = (PnpHyp *)(ws + ws_off_hyp(cfg, B)) + (int64_t)item0 * kPhaseHyps;
-    a.counts = (int *)(ws + ws_off_counts(cfg, B)) + (int64_t)item0 * kPhaseHyps;
-    a.subsets = (int *)(ws + ws_off_subsets(cfg, B)) + (int64_t)item0 * 2 * kPhaseHyps * 5;
-    a.hand = (double *)(ws + ws_off_hand(cfg, B)) + (int64_t)item0 * kPhaseBlocks * (kEpnpHandDoubles * 64);
-    a.stream = (const uint64_t *)(ws + ws_off_stream(cfg, B));
+    const PnpCut c = pnp_cut(ctx);
+    a.out = (PnpRecord *)(ws + c.rec) + item0;
+    a.state = (PnpState *)(ws + c.state) + item0;
+    a.hyp = (PnpHyp *)(ws + c.hyp) + (int64_t)item0 * kPhaseHyps;
+    a.counts = (int *)(ws + c.counts) + (int64_t)item0 * kPhaseHyps;
+    a.subsets = (int *)(ws + c.subsets) + (int64_t)item0 * 2 * kPhaseHyps * 5;
+    a.hand = (double *)(ws + c.hand) + (int64_t)item0 * kPhaseBlocks * (kEpnpHandDoubles * 64);
+    a.stream = (const uint64_t *)(ws + c.stream);
     if (!begun) hipLaunchKernelGGL(pnp_begin_kernel, dim3(n_items), dim3(64), 0, st, a);
     const int niters = a.iterations > 1 ? a.iterations : 1;
     // 1024 points per scoring workgroup; a launch that leaves the chip mostly empty (the online path) takes
@@ -1159,29 +923,36 @@ void launch_triangulate_batch(svo_ctx *ctx, int n_items, int max_pts, const floa
     gx = gx < 0 ? 0 : gx;
     // + one workgroup per item that prepares the item's solvePnPRansac (launch_pnp_batch follows on every path)
     char *ws = (char *)ctx->pnp_ws;
-    const int B = ctx->cfg.max_batch;
+    const PnpCut c = pnp_cut(ctx);
     a.fuse_begin = 1;
-    a.begin.state = (PnpState *)(ws + ws_off_state(ctx->cfg, B));
-    a.begin.counts = (int *)(ws + ws_off_counts(ctx->cfg, B));
-    a.begin.subsets = (int *)(ws + ws_off_subsets(ctx->cfg, B));
+    a.begin.state = (PnpState *)(ws + c.state);
+    a.begin.counts = (int *)(ws + c.counts);
+    a.begin.subsets = (int *)(ws + c.subsets);
     a.begin.iterations = ctx->cfg.iterations;
     a.begin.first_cap = pnp_first_cap(ctx->cfg);
-    a.begin.stream = (const uint64_t *)(ws + ws_off_stream(ctx->cfg, B));
+    a.begin.stream = (const uint64_t *)(ws + c.stream);
     if (snap) a.begin.snap = SnapArgs{snap->n, snap->ovf, snap->fp0, snap->fc0, snap->fstep, snap->per, n_items, ctx->kp_n_snap};
     hipLaunchKernelGGL(triangulate_kernel, dim3(gx + 1, n_items), dim3(64), 0, st, a);
 }
 
-void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n_pts, int n_fixed, hipStream_t st)
+// What every solve of the fused paths takes from the context: K = P1[:, :3] (src/tracking.cpp:476-477), the RANSAC
+// settings, max_keypoints points per item, and workspace item 0's inlier flags
+static PnpArgs pnp_args_from_ctx(const svo_ctx *ctx)
 {
     PnpArgs a{};
-    a.X3 = ctx->X3; a.img = img; a.stride = ctx->cfg.max_keypoints;
-    a.n_pts = n_pts; a.n_fixed = n_fixed;
-    // K = P1[:, :3] (src/tracking.cpp:476-477)
+    a.stride = ctx->cfg.max_keypoints;
     a.fx = ctx->cfg.P1[0]; a.fy = ctx->cfg.P1[5]; a.cx = ctx->cfg.P1[2]; a.cy = ctx->cfg.P1[6];
     a.iterations = ctx->cfg.iterations; a.reproj_err = ctx->cfg.reproj_err;
     a.first_cap = pnp_first_cap(ctx->cfg);
     a.confidence = (double)ctx->cfg.confidence;
-    a.mask = (uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch);
+    a.mask = (uint8_t *)ctx->pnp_ws + pnp_cut(ctx).mask;
+    return a;
+}
+
+void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n_pts, int n_fixed, hipStream_t st)
+{
+    PnpArgs a = pnp_args_from_ctx(ctx);
+    a.X3 = ctx->X3; a.img = img; a.n_pts = n_pts; a.n_fixed = n_fixed;
     launch_pnp_pipeline(ctx, a, n_items, ctx->cfg.max_keypoints, st, /*begun by launch_triangulate_batch*/ true);
 }
 
@@ -1189,52 +960,10 @@ void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n
 // context's K and RANSAC settings, the point count read on the device.  The same launches as a lone pair's solve.
 void launch_pnp_item(svo_ctx *ctx, int item, const float *X3, const float2 *img, const int *n_pts, hipStream_t st)
 {
-    PnpArgs a{};
-    a.X3 = X3; a.img = img; a.stride = ctx->cfg.max_keypoints;
-    a.n_pts = n_pts; a.n_fixed = 0;
-    a.fx = ctx->cfg.P1[0]; a.fy = ctx->cfg.P1[5]; a.cx = ctx->cfg.P1[2]; a.cy = ctx->cfg.P1[6];
-    a.iterations = ctx->cfg.iterations; a.reproj_err = ctx->cfg.reproj_err;
-    a.first_cap = pnp_first_cap(ctx->cfg);
-    a.confidence = (double)ctx->cfg.confidence;
-    a.mask = (uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch) + (size_t)item * ctx->cfg.max_keypoints;
+    PnpArgs a = pnp_args_from_ctx(ctx);
+    a.X3 = X3; a.img = img; a.n_pts = n_pts; a.n_fixed = 0;
+    a.mask += (size_t)item * ctx->cfg.max_keypoints;
     launch_pnp_pipeline(ctx, a, 1, ctx->cfg.max_keypoints, st, false, item);
-}
-const PnpRecord *pnp_record(const svo_ctx *ctx, int item) { return (const PnpRecord *)ctx->pnp_ws + item; }
-
-void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
-                           const double *pose0_host, hipStream_t st)
-{
-    FinalizeArgs f{};
-    f.pnp = (const PnpRecord *)ctx->pnp_ws; f.n_prev = n_prev; f.n_cur = n_cur; f.n_tracked = ctx->m_out; f.ovf = ovf;
-    f.cap = ctx->cfg.max_keypoints;
-    f.n_pairs = n_pairs; f.mode = ctx->cfg.track_mode; f.num_features_tracking = ctx->cfg.num_features_tracking;
-    f.inlier_rate = ctx->cfg.inlier_rate; f.min_move2 = ctx->cfg.min_move2; f.max_move2 = ctx->cfg.max_move2;
-    f.res = ctx->d_results;
-    Pose16 p0;
-    for (int i = 0; i < 16; i++) p0.m[i] = pose0_host ? pose0_host[i] : ((i % 5 == 0) ? 1.0 : 0.0);
-    hipLaunchKernelGGL(finalize_chain_kernel, dim3(1), dim3(kFinThreads), 0, st, f, p0, ctx->seed_dev);
-}
-
-void launch_finalize_streams(svo_ctx *ctx, int item0, int n_items, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
-                             const StreamTable &tab, hipStream_t st)
-{
-    FinalizeArgs f{};
-    f.pnp = (const PnpRecord *)ctx->pnp_ws; f.n_prev = n_prev; f.n_cur = n_cur; f.n_tracked = ctx->m_out; f.ovf = ovf;
-    f.cap = ctx->cfg.max_keypoints;
-    f.n_pairs = item0 + n_items < n_pairs ? item0 + n_items : n_pairs;
-    f.mode = ctx->cfg.track_mode; f.num_features_tracking = ctx->cfg.num_features_tracking;
-    f.inlier_rate = ctx->cfg.inlier_rate; f.min_move2 = ctx->cfg.min_move2; f.max_move2 = ctx->cfg.max_move2;
-    f.res = ctx->d_results;
-    hipLaunchKernelGGL(finalize_streams_kernel, dim3((n_items + kFinStreams - 1) / kFinStreams), dim3(64), 0, st, f, item0, tab,
-                       ctx->streams.pose);
-}
-
-void launch_streams_set_pose(svo_ctx *ctx, int id0, int n, const double *pose_host)
-{
-    Pose16 p;
-    for (int i = 0; i < 16; i++) p.m[i] = pose_host ? pose_host[i] : ((i % 5 == 0) ? 1.0 : 0.0);
-    hipLaunchKernelGGL(streams_set_pose_kernel, dim3((n * 16 + 255) / 256), dim3(256), 0, ctx->stream,
-                       ctx->streams.pose + (size_t)id0 * 16, n, p);
 }
 
 // ---- stage API ------------------------------------------------------------------------------
@@ -1274,7 +1003,7 @@ int stage_pnp_ransac(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *img, int
     a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
     a.iterations = iterations; a.reproj_err = reproj_err; a.confidence = confidence;
     a.first_cap = pnp_first_cap(ctx->cfg);                   // (the stage call of a context follows its track_mode too)
-    uint8_t *ws_mask = (uint8_t *)ctx->pnp_ws + ws_off_mask(ctx->cfg.max_batch);
+    uint8_t *ws_mask = (uint8_t *)ctx->pnp_ws + pnp_cut(ctx).mask;
     SVO_TRY(to_device(ctx, (const float *)obj, ctx->X3, (size_t)3 * n, mem, &a.X3));
     SVO_TRY(to_device(ctx, (const float2 *)img, ctx->cmp[3], (size_t)n, mem, &a.img));
     a.mask = mem == SVO_MEM_DEVICE && inlier_mask ? inlier_mask : ws_mask;

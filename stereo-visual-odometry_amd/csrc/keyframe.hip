@@ -15,6 +15,7 @@
 #include <cstring>
 #include "abi_io.h"
 #include "keyframe.h"
+#include "pose_device.h"
 #include "svo_device.h"
 
 namespace svo {
@@ -83,18 +84,7 @@ void launch_keyframe_join(const KeyframeJoinArgs &a, hipStream_t st)
     hipLaunchKernelGGL(keyframe_join_kernel, dim3(1), dim3(1024), 0, st, a);
 }
 
-// C = A B, 4 x 4 row-major, in the chain's association order: k ascending, separate multiply and add, from 0
-__device__ inline void kf_mul4(const double *A, const double *B, double *C)
-{
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            double s = 0;
-            for (int k = 0; k < 4; k++) s += A[i * 4 + k] * B[k * 4 + j];
-            C[i * 4 + j] = s;
-        }
-}
-
-// K4-K6.  Lane 0 decides -- the gates on the implied motion, the composition, the switch -- and writes the result record; on a
+// K4-K6.  Lane 0 decides -- the gates on the implied motion, the composition, the switch (pose_device.h) -- and writes the result record; on a
 // switch all lanes rebuild the table from the pair's lists (the same ballot rank keeps the list order).
 __global__ __launch_bounds__(1024) void keyframe_update_kernel(KeyframeUpdateArgs a)
 {
@@ -130,30 +120,13 @@ __global__ __launch_bounds__(1024) void keyframe_update_kernel(KeyframeUpdateArg
                     M[i * 4 + 3] = q.tvec[i];
                 }
                 M[12] = 0; M[13] = 0; M[14] = 0; M[15] = 1;
-                kf_mul4(M, S->inv_K, A);
-                kf_mul4(A, a.pose_a, F);
-                // rotationMatrixToEulerAngles as finalize_pair has it, on F's rotation
-                const float sy = (float)sqrt(F[0] * F[0] + F[4] * F[4]);
-                const bool singular = (double)sy < 1e-6;
-                float ex, ey, ez;
-                if (!singular) {
-                    ex = (float)atan2(F[9], F[10]); ey = (float)atan2(-F[8], (double)sy); ez = (float)atan2(F[4], F[0]);
-                } else {
-                    ex = (float)atan2(-F[6], F[5]); ey = (float)atan2(-F[8], (double)sy); ez = 0.f;
-                }
-                const double n2 = F[3] * F[3] + F[7] * F[7] + F[11] * F[11];
-                if ((double)fabsf(ey) < 0.1 && (double)fabsf(ex) < 0.1 && (double)fabsf(ez) < 0.1 && n2 < a.max_move2) {
+                pose_mul4(M, S->inv_K, A);
+                pose_mul4(A, a.pose_a, F);
+                if (pose_euler_gate(F, 4) && pose_norm2_t(F + 3, 4) < a.max_move2) {
                     status = SVO_KF_APPLIED;
-                    const double *R = q.R, *t = q.tvec;
-                    double Ti[16], P[16];                     // inv([R t; 0 1]) in finalize_pair's closed form
-                    Ti[0] = R[0]; Ti[1] = R[3]; Ti[2] = R[6];
-                    Ti[4] = R[1]; Ti[5] = R[4]; Ti[6] = R[7];
-                    Ti[8] = R[2]; Ti[9] = R[5]; Ti[10] = R[8];
-                    Ti[3] = -(R[0] * t[0] + R[3] * t[1] + R[6] * t[2]);
-                    Ti[7] = -(R[1] * t[0] + R[4] * t[1] + R[7] * t[2]);
-                    Ti[11] = -(R[2] * t[0] + R[5] * t[1] + R[8] * t[2]);
-                    Ti[12] = 0; Ti[13] = 0; Ti[14] = 0; Ti[15] = 1;
-                    kf_mul4(S->pose_K, Ti, P);
+                    double Ti[16], P[16];
+                    pose_inv_rt(q.R, q.tvec, Ti);
+                    pose_mul4(S->pose_K, Ti, P);
                     for (int i = 0; i < 16; i++) r->pose[i] = P[i];
                 }
             }
@@ -164,14 +137,8 @@ __global__ __launch_bounds__(1024) void keyframe_update_kernel(KeyframeUpdateArg
         *a.res = out;
         if (sw) {
             S->valid = 1; S->kf_index = a.index_b - 1;
-            const double *Pw = a.pose_a;
-            for (int i = 0; i < 16; i++) S->pose_K[i] = Pw[i];
-            for (int i = 0; i < 3; i++) {                     // T4: R = Rw^T, t_i = -((R_i0 tw_0 + R_i1 tw_1) + R_i2 tw_2)
-                const double r0 = Pw[i], r1 = Pw[4 + i], r2 = Pw[8 + i];
-                S->inv_K[i * 4] = r0; S->inv_K[i * 4 + 1] = r1; S->inv_K[i * 4 + 2] = r2;
-                S->inv_K[i * 4 + 3] = -((r0 * Pw[3] + r1 * Pw[7]) + r2 * Pw[11]);
-            }
-            S->inv_K[12] = 0; S->inv_K[13] = 0; S->inv_K[14] = 0; S->inv_K[15] = 1;
+            for (int i = 0; i < 16; i++) S->pose_K[i] = a.pose_a[i];
+            pose_inv_t4(a.pose_a, S->inv_K);
         } else if (!valid) {
             S->valid = 0; S->kf_index = -1; S->n_rows = 0;    // K1: the host's clear, made to last
         }
@@ -259,7 +226,7 @@ int keyframe_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
     KeyframeUpdateArgs u{};
     u.state = state; u.tab_ids = (long long *)(s + c.ids); u.tab_X = (float *)(s + c.X);
     u.clear = j.clear; u.index_b = ctx->online_frames; u.min_tracks = ctx->kf_min_tracks; u.max_gap = ctx->kf_max_gap; u.cap = K;
-    for (int i = 0; i < 16; i++) u.pose_a[i] = pose0_host ? pose0_host[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    memcpy(u.pose_a, pose_from_host(pose0_host).m, sizeof(u.pose_a));
     u.inlier_rate = ctx->cfg.inlier_rate; u.max_move2 = ctx->cfg.max_move2;
     u.rec = ctx->d_results; u.pnp = pnp_record(ctx, 1); u.counts = counts;
     u.trk_ids = ctx->trk_id; u.tri = ctx->X3; u.trk_n = ctx->m_out;

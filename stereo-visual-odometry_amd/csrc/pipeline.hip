@@ -12,6 +12,7 @@
 #include <cstring>
 #include "abi_io.h"
 #include "carry.h"
+#include "pose_device.h"
 
 namespace svo {
 
@@ -519,15 +520,16 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
         ctx->win_clear = true; ctx->win_last = false;      // svo_set_window_ba, T1: a chain's first frame
         ctx->kf_clear = true; ctx->kf_last = false;        // svo_set_keyframe, K1
         // StereoInit_f2f (:78-92): detect only
-        SVO_TRY(count_read(ctx, ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur, &res->n_cur_kps));
+        int n_cur;
+        SVO_TRY(count_read(ctx, ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur, &n_cur));
         if (ctx->carry_on) {                     // svo_set_track_carry: the chain's first list gets its ids (the count above stays the detector's)
             launch_carry_pairs(ctx, 1, prev, cur, 0, nullptr, /*no_prev*/ true);
             mark(ctx, kTCarry);
             SVO_HIP(hipGetLastError());
         }
-        res->ok = 1;
-        for (int i = 0; i < 9; i++) res->R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        for (int i = 0; i < 16; i++) { res->T_rel_inv[i] = (i % 5 == 0) ? 1.0 : 0.0; res->pose[i] = ctx->pose[i]; }
+        step_record_clear(*res);
+        res->ok = 1; res->n_cur_kps = n_cur;
+        memcpy(res->pose, ctx->pose, sizeof(res->pose));
         ctx->online_frames = 1; ctx->online_cur = cur; ctx->online_tracked = 0;
         return SVO_OK;
     }

@@ -11,6 +11,7 @@
 #include "abi_io.h"
 #include "carry.h"
 #include "fast_scratch.h"
+#include "pose_device.h"
 
 using namespace svo;
 
@@ -208,7 +209,7 @@ extern "C" int svo_create(const svo_config *cfg, int device, svo_ctx **out)
     if (!ctx) return SVO_ERR_NOMEM;
     ctx->cfg = *cfg;
     ctx->device = device;
-    for (int i = 0; i < 16; i++) ctx->pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    pose_identity16(ctx->pose);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
         // fail loudly: this library has no CPU path
@@ -739,7 +740,7 @@ extern "C" int svo_reset(svo_ctx *ctx)
     ctx->carry_restart = true;                   // svo_set_track_carry: the next chain's ids start at 0
     ctx->win_clear = true;                       // svo_set_window_ba, T1
     ctx->kf_clear = true;                        // svo_set_keyframe, K1
-    for (int i = 0; i < 16; i++) ctx->pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    pose_identity16(ctx->pose);
     return SVO_OK;
 }
 

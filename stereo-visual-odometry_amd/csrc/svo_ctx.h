@@ -123,10 +123,11 @@ struct svo_ctx {
     uint8_t *keep = nullptr;
     float2 *cmp[4] = {nullptr, nullptr, nullptr, nullptr};    // compacted t1l, t1r, t2r, t2l
     int *m_out = nullptr;
-    // ---- geometry buffers (geometry.hip)
+    // ---- pose stage buffers (geometry.hip solves into them; pose_chain.hip, refine.hip and ba.hip work on its records)
     float *X3 = nullptr;              // triangulated points, 3 floats per point
     void *pnp_ws = nullptr; size_t pnp_ws_bytes = 0;
     svo_step_result *d_results = nullptr;
+    DevScratch chain_stage;           // svo_chain_relative: the caller's motions and flags and the poses (HOST calls)
     // ---- batch-mode pyramid slots: 2 * n_img
     uint8_t *bslots = nullptr;
     // ---- online state (svo_add_frame)
@@ -287,7 +288,7 @@ int dev_reserve(svo_ctx *ctx, DevScratch *s, size_t bytes);
 // make *ev / *st unless it exists already
 int dev_event(svo_ctx *ctx, hipEvent_t *ev, unsigned flags = hipEventDisableTiming);
 int dev_stream(svo_ctx *ctx, hipStream_t *st);
-// geometry.hip
+// geometry.hip: triangulation and solvePnPRansac
 int geom_workspace_bytes(const svo_config &cfg, int n_items, size_t *bytes);
 int geom_workspace_init(svo_ctx *ctx);
 int stage_triangulate(svo_ctx *ctx, const double P1[12], const double P2[12], const svo_pt2f *x1, const svo_pt2f *x2, int n,
@@ -302,6 +303,7 @@ void launch_snap_counts(svo_ctx *ctx, int n_items, const SnapSpec &snap, hipStre
 void launch_pnp_batch(svo_ctx *ctx, int n_items, const float2 *img, const int *n_pts, int n_fixed, hipStream_t st);
 void launch_pnp_item(svo_ctx *ctx, int item, const float *X3, const float2 *img, const int *n_pts, hipStream_t st);    // one more solve, workspace item `item`
 const PnpRecord *pnp_record(const svo_ctx *ctx, int item);
+const uint8_t *pnp_inlier_mask(const svo_ctx *ctx);
 // refine.hip: pose_refine_kernel, one workgroup per pair, on the records solvePnPRansac left in ctx->pnp_ws
 int refine_alloc(svo_ctx *ctx);                          // the stage's device block, on first use (waits for the device)
 void launch_refine_batch(svo_ctx *ctx, int n_pairs, hipStream_t st);
@@ -319,8 +321,6 @@ int ba_read_points(svo_ctx *ctx, int pair, double *X, int cap, int *n_out);
 int orb_alloc(svo_ctx *ctx);
 int orb_max_keypoints(const svo_ctx *ctx);             // what one image holds at most: the level quotas + 8 each, capped at orb_kp_cap
 void timing_mark(svo_ctx *ctx, const char *name);     // HIP event on the context's stream when timing is enabled
-const uint8_t *pnp_inlier_mask(const svo_ctx *ctx);
-int stage_chain_relative(svo_ctx *ctx, const double *T, const int32_t *ok, int n, const double *pose0_host, double *out, int mem);
 int stage_host_image(svo_ctx *ctx, const uint8_t *img, int pitch, int stage_idx, const uint8_t **dptr, int *dpitch);
 int orb_extract_batch(svo_ctx *ctx, const uint8_t *img, const uint8_t *img2, int pitch, int64_t img_stride, int slot0,
                       int n_img, hipStream_t st, bool in_place = false);
@@ -342,6 +342,7 @@ int resize_launch_tab(svo_ctx *ctx, const ResizeShape &shape, int interp, const 
                       uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st);
 int resize_launch(svo_ctx *ctx, int tab, const uint8_t *src0, const uint8_t *src1, int spitch, int64_t sstride,
                   uint8_t *dst0, uint8_t *dst1, int dpitch, int64_t dstride, int n_frames, hipStream_t st);
+// pose_chain.hip: the gates and the pose chain behind a solve (the algebra is pose_device.h's)
 // One step of a stream set: item i of a launch works for stream id[i]; init[i]: the stream's first frame (no previous one).
 constexpr int kStreamChunk = 128;                       // items per gather / scatter / finalize launch (the table is a kernel argument)
 struct StreamTable { int32_t id[kStreamChunk]; uint8_t init[kStreamChunk]; };
@@ -350,6 +351,7 @@ void launch_finalize_streams(svo_ctx *ctx, int item0, int n_items, int n_pairs, 
 void launch_streams_set_pose(svo_ctx *ctx, int id0, int n, const double *pose_host);    // null: identity
 void launch_finalize_chain(svo_ctx *ctx, int n_pairs, const int *n_prev, const int *n_cur, const int *ovf,
                            const double *pose0_host, hipStream_t st);      // ctx->seed_dev != null: seed read on the device
+int stage_chain_relative(svo_ctx *ctx, const double *T, const int32_t *ok, int n, const double *pose0_host, double *out, int mem);
 // pipeline.hip: the fused steps.  Their arguments arrive checked -- the rules of each entry-point family are written once, in
 // svo_abi.hip, and run before anything is copied or launched -- and their frames are DEVICE frames of the context's size,
 // already ordered before the context's stream, on the device svo_abi.hip has made current.

@@ -99,7 +99,7 @@ struct CompactArgs {
 };
 void launch_compact(const CompactArgs &a, int batch, hipStream_t st);
 
-// ---- pose stage records (geometry.hip writes them, refine.hip refines them in place) ----------
+// ---- pose stage records (geometry.hip writes them, refine.hip / ba.hip refine them in place, pose_chain.hip gates them) ----
 struct PnpRecord {                 // device-side record of one solvePnPRansac
     double rvec[3], tvec[3], R[9];
     int n_inliers, ransac_iters, best_iter, lm_iters, ok, n;

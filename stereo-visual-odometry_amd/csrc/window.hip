@@ -14,6 +14,8 @@
 // the new tracks below its id (a binary search in the track list), a new track's place is its rank among the new tracks plus
 // the surviving rows below its id (a binary search in the row list).  One workgroup of 1024 lanes; the ranks come from block
 // scans whose prefixes stay in device scratch.  Nothing is written to `out` before the row count is known to fit.
+#include <cstring>
+#include "pose_device.h"
 #include "refine_device.h"
 #include "window.h"
 
@@ -39,14 +41,6 @@ __device__ inline bool window_usable(const WindowUpdateArgs &a, int k)
            isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2]);
 }
 
-// element e of the camera-from-world (R row-major, t) of a world-from-camera 4 x 4: R = Rw^T, t = -(Rw^T tw), left to right
-__device__ inline double window_inverse(const double *T, int e)
-{
-    if (e < 9) return T[(e % 3) * 4 + e / 3];
-    const int i = e - 9;
-    return -((T[i] * T[3] + T[4 + i] * T[7]) + T[8 + i] * T[11]);
-}
-
 __global__ __launch_bounds__(1024) void window_update_kernel(WindowUpdateArgs a)
 {
     __shared__ int wave_tot[16];
@@ -69,8 +63,8 @@ __global__ __launch_bounds__(1024) void window_update_kernel(WindowUpdateArgs a)
     if (tid < kWindowMaxFrames * kWindowPose) {
         const int slot = tid / kWindowPose, e = tid % kWindowPose;
         double v = 0.0;
-        if (slot < cur) v = n == 0 ? window_inverse(pose_a, e) : a.in.poses[(slot + shift) * kWindowPose + e];
-        else if (slot == cur) v = window_inverse(a.pose_b, e);
+        if (slot < cur) v = n == 0 ? pose_inv_t4_elem(pose_a, e) : a.in.poses[(slot + shift) * kWindowPose + e];
+        else if (slot == cur) v = pose_inv_t4_elem(a.pose_b, e);
         pose[tid] = v;
     }
 
@@ -693,7 +687,7 @@ int window_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
     u.ids = ctx->trk_id; u.tri = ctx->X3; u.n_trk = K; u.n_trk_dev = ctx->m_out;
     u.ok = &ctx->d_results[0].ok; u.clear_in = ctx->win_clear ? 1 : 0;
     u.pose_a_by_value = 1;
-    for (int i = 0; i < 16; i++) u.pose_a_value[i] = pose0_host ? pose0_host[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    memcpy(u.pose_a_value, pose_from_host(pose0_host).m, sizeof(u.pose_a_value));
     u.pose_b = ctx->d_results[0].pose;
     u.pre_rows = (int *)(s + c.pre_rows); u.pre_new = (int *)(s + c.pre_new);
     launch_window_update(u, st);

@@ -4,6 +4,8 @@ K3-K7); the solve is a callable handed in (oracle.pnp_ransac on the GPU side's s
 tests).  The HIP kernels must equal it bit for bit in every integer, list and table."""
 import numpy as np
 
+from _pose_ref import euler, gates, inv_rt, inv_t4, mul4  # noqa: F401  (re-exported: the chain's algebra lives in _pose_ref)
+
 NONE, SHORT, PAIR_FAILED, REJECTED, APPLIED = 0, 1, 2, 3, 4
 
 
@@ -24,61 +26,11 @@ def join(tab_ids, tab_X, trk_ids, trk_xy):
     return dict(ids=trk_ids[i].copy(), X=tab_X[j].copy(), xy=trk_xy[i].copy(), trk=i.astype(np.int32), row=j.astype(np.int32))
 
 
-def mul4(A, B):
-    """4 x 4 product in the chain's association order: k ascending, separate multiply and add, from 0"""
-    A, B = np.asarray(A, np.float64).reshape(4, 4), np.asarray(B, np.float64).reshape(4, 4)
-    C = np.zeros((4, 4))
-    for i in range(4):
-        for j in range(4):
-            s = np.float64(0)
-            for k in range(4):
-                s = s + A[i, k] * B[k, j]
-            C[i, j] = s
-    return C
-
-
-def inv_t4(P):
-    """rule T4: camera from world of a world-from-camera pose: R = Rw^T, t_i = -((R_i0 tw_0 + R_i1 tw_1) + R_i2 tw_2)"""
-    P = np.asarray(P, np.float64).reshape(4, 4)
-    out = np.eye(4)
-    for i in range(3):
-        r = P[:3, i]
-        out[i, :3] = r
-        out[i, 3] = -((r[0] * P[0, 3] + r[1] * P[1, 3]) + r[2] * P[2, 3])
-    return out
-
-
-def inv_rt(R, t):
-    """inverse([R t]) in the closed form of T_rel_inv (finalize_pair): R^T, -(R^T t) summed left to right"""
-    R, t = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
-    out = np.eye(4)
-    out[:3, :3] = R.T
-    for i in range(3):
-        out[i, 3] = -(R[0, i] * t[0] + R[1, i] * t[1] + R[2, i] * t[2])
-    return out
-
-
-def euler(R):
-    """rotationMatrixToEulerAngles as the pair's gate computes it: floats holding double expressions"""
-    R = np.asarray(R, np.float64).reshape(3, 3)
-    sy = np.float32(np.sqrt(R[0, 0] * R[0, 0] + R[1, 0] * R[1, 0]))
-    if not float(sy) < 1e-6:
-        return (np.float32(np.arctan2(R[2, 1], R[2, 2])), np.float32(np.arctan2(-R[2, 0], float(sy))), np.float32(np.arctan2(R[1, 0], R[0, 0])))
-    return (np.float32(np.arctan2(-R[1, 2], R[1, 1])), np.float32(np.arctan2(-R[2, 0], float(sy))), np.float32(0))
-
-
 def implied_motion(R, t, inv_K, pose_a):
     """K4: F = ([R t; 0 0 0 1] inv_K) pose_a, the motion a -> b the keyframe pose implies"""
     M = np.eye(4)
     M[:3, :3], M[:3, 3] = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
     return mul4(mul4(M, inv_K), pose_a)
-
-
-def gates(F, max_move2):
-    """K4's gates on the implied motion: every Euler angle below 0.1, |t|^2 below max_move2 (no lower bound)"""
-    ex, ey, ez = euler(F[:3, :3])
-    n2 = F[0, 3] * F[0, 3] + F[1, 3] * F[1, 3] + F[2, 3] * F[2, 3]
-    return bool(abs(float(ey)) < 0.1 and abs(float(ex)) < 0.1 and abs(float(ez)) < 0.1 and n2 < max_move2)
 
 
 class Chain:

@@ -7,6 +7,7 @@ import math
 import numpy as np
 
 import _refine_ref as RR
+from _pose_ref import inv_t4
 
 MAX_FRAMES = 8          # SVO_WINDOW_MAX_FRAMES: the fixed stride of a row's observation columns
 
@@ -20,10 +21,8 @@ def empty(cap=0):
 
 def camera_from_world(pose):
     """(R, t) of Y = R X + t from a world-from-camera 4 x 4 chain pose: R = Rw^T, t = -(Rw^T tw), summed left to right."""
-    T = np.asarray(pose, np.float64).reshape(4, 4)
-    R = T[:3, :3].T.copy()
-    t = np.array([-((R[i, 0] * T[0, 3] + R[i, 1] * T[1, 3]) + R[i, 2] * T[2, 3]) for i in range(3)])
-    return R, t
+    M = inv_t4(pose)                                                # rule T4, the same expression as the keyframe's inv_K
+    return M[:3, :3].copy(), M[:3, 3].copy()
 
 
 def usable_tracks(t1_left, t1_right, t2_left, t2_right, tri):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""SHA-256 digests of everything the three pose optimisers write, for byte-for-byte comparisons between two builds of the
-library (a refactor of refine.hip / ba.hip / window.hip must not move one bit).  No figure here is a pass bar: run the tool at
+"""SHA-256 digests of everything the three pose optimisers and the tail of the pose stage write, for byte-for-byte comparisons
+between two builds of the library (a refactor of refine.hip / ba.hip / window.hip / pose_chain.hip must not move one bit).  No figure here is a pass bar: run the tool at
 both commits and compare the lists.
 
 Cases (the builders the GPU tests use: tests/_refine_cases.py, tests/_ba_cases.py, tests/_window_cases.py):
@@ -11,6 +11,10 @@ Cases (the builders the GPU tests use: tests/_refine_cases.py, tests/_ba_cases.p
                 (2 .. 8 frames, up to 2049 landmarks), and the optimiser on updated tables of 2, 3 and 8 frames
   fused         svo_add_frame over the 9 frames of tests/test_gpu_window.py plus one blank frame (a failed pair: the SKIPPED
                 record), in reproj mode, in ba mode, and with track carry and the window at W = 3
+  chain         the tail of the pose stage (pose_chain.hip, keyframe.hip): svo_track_batch's records over the same ten frames with
+                and without pose0; svo_streams_step's records and svo_streams_get_pose for 3 streams over 3 steps, one reset and
+                one seeded with svo_streams_set_pose in between; svo_chain_relative on tests/_pose_ref.py's chain_cases(), HOST
+                and DEVICE; the fused keyframe chain at max_gap 0 and 2 (result, matches, table, records)
 Per case: one digest over the raw bytes of every output (record, flags, points, table, step records).
 
     python tools/pose_digest.py [--out digests.json]"""
@@ -66,6 +70,7 @@ def main():
     import importlib
     import torch
     import _ba_cases as BC
+    import _pose_ref as PR
     import _refine_cases as RC
     import _refine_ref as RR
     import _window_cases as WC
@@ -190,6 +195,45 @@ def main():
             steps.append(digest(step))
             print("fused %s frame %d %s" % (mode, f, steps[-1]), flush=True)
         put("fused %s" % mode, steps)
+        ctx.close()
+
+    # ---- the tail of the pose stage
+    P1, P2 = seq.proj()
+    L, R = (torch.from_numpy(np.stack([f[k] for f in frames])).cuda() for k in (0, 1))
+    seed = PR.rigid_motions(np.random.default_rng(5), 1)[0]
+    for name, pose0 in (("identity", None), ("pose0", seed)):
+        ctx = pkg.Context(416, 128, device=0, P1=P1, P2=P2, max_batch=16)
+        put("chain track_batch %s" % name, ctx.track_batch(L, R, pose0=pose0).tobytes())
+        ctx.close()
+    ctx = pkg.Context(416, 128, device=0, P1=P1, P2=P2, max_batch=5)       # a step of m streams needs max_batch >= 2 m - 1
+    ctx.streams_create(3)
+    ids = [2, 0, 1]
+    for t in range(3):
+        if t == 2:
+            ctx.streams_reset(ids[1])
+            ctx.streams_set_pose(ids[2], seed)
+        recs = ctx.streams_step(ids, [frames[t + 2 * k][0] for k in range(3)], [frames[t + 2 * k][1] for k in range(3)])
+        put("chain streams step %d" % t, recs.tobytes(), [ctx.streams_get_pose(i) for i in ids])
+    ctx.close()
+    ctx = pkg.Context(64, 64, device=0)
+    for (n, seeded), (T, ok, pose0) in sorted(PR.chain_cases().items()):
+        put("chain relative n=%d %s host" % (n, "pose0" if seeded else "identity"), ctx.chain_relative(T.reshape(n, 16), ok, pose0))
+        got = ctx.chain_relative(dev(T.reshape(n, 16)), dev(ok), pose0)
+        ctx.sync()
+        put("chain relative n=%d %s device" % (n, "pose0" if seeded else "identity"), got.cpu().numpy())
+    ctx.close()
+    for max_gap in (0, 2):
+        ctx = pkg.Context(416, 128, device=0, P1=P1, P2=P2, max_batch=2)
+        ctx.set_track_carry(True)
+        ctx.set_keyframe(True, 60, max_gap)
+        steps = []
+        for f, (Lf, Rf) in enumerate(frames):
+            rc, rec = ctx.add_frame(Lf, Rf)
+            step = [rc, np.asarray(rec).tobytes(), ctx.get_pose()]
+            if f:
+                step += [ctx.keyframe_result(), ctx.keyframe_matches(), list(ctx.keyframe_table())]
+            steps.append(digest(step))
+        put("chain keyframe max_gap %d" % max_gap, steps)
         ctx.close()
 
     doc = {"tool": "tools/pose_digest.py", "device": torch.cuda.get_device_name(0), "cases": len(out), "digests": out}
