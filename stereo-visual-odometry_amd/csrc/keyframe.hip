@@ -192,14 +192,14 @@ static KfCut keyframe_cut(int kcap)
 
 int keyframe_alloc(svo_ctx *ctx)
 {
-    if (ctx->kf_buf) return SVO_OK;
+    if (ctx->kf.buf) return SVO_OK;
     SVO_HIP(hipSetDevice(ctx->device));
     const KfCut c = keyframe_cut(ctx->cfg.max_keypoints);
     uint8_t *p = nullptr;
     if (dev_alloc(ctx, &p, c.end) != SVO_OK) return SVO_ERR_HIP;
     SVO_HIP(hipMemsetAsync(p, 0, c.end, ctx->stream));
     SVO_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->kf_buf = p;
+    ctx->kf.buf = p;
     return SVO_OK;
 }
 
@@ -208,14 +208,14 @@ int keyframe_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
 {
     const int K = ctx->cfg.max_keypoints;
     const KfCut c = keyframe_cut(K);
-    uint8_t *s = ctx->kf_buf;
+    uint8_t *s = ctx->kf.buf;
     KfState *state = (KfState *)(s + c.state);
     int *counts = (int *)(s + c.counts);
     KeyframeJoinArgs j{};
     j.tab_ids = (const long long *)(s + c.ids); j.tab_X = (const float *)(s + c.X); j.tab_n = &state->n_rows; j.rows_cap = K;
-    j.trk_ids = ctx->trk_id; j.trk_xy = ctx->cmp[3]; j.trk_n = ctx->m_out; j.trk_cap = K;
-    j.valid = &state->valid; j.clear = ctx->kf_clear ? 1 : 0;
-    j.min_tracks = ctx->kf_min_tracks;
+    j.trk_ids = ctx->carry.trk_id; j.trk_xy = ctx->cmp[3]; j.trk_n = ctx->m_out; j.trk_cap = K;
+    j.valid = &state->valid; j.clear = ctx->kf.clear ? 1 : 0;
+    j.min_tracks = ctx->kf.min_tracks;
     j.o_X = (float *)(s + c.j_X); j.o_xy = (float2 *)(s + c.j_xy); j.o_trk = (int *)(s + c.j_trk); j.o_row = (int *)(s + c.j_row);
     j.o_id = (long long *)(s + c.j_id);
     j.out_cap = K; j.counts = counts;
@@ -225,15 +225,15 @@ int keyframe_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
     timing_mark(ctx, "kf_pnp");
     KeyframeUpdateArgs u{};
     u.state = state; u.tab_ids = (long long *)(s + c.ids); u.tab_X = (float *)(s + c.X);
-    u.clear = j.clear; u.index_b = ctx->online_frames; u.min_tracks = ctx->kf_min_tracks; u.max_gap = ctx->kf_max_gap; u.cap = K;
+    u.clear = j.clear; u.index_b = ctx->online_frames; u.min_tracks = ctx->kf.min_tracks; u.max_gap = ctx->kf.max_gap; u.cap = K;
     memcpy(u.pose_a, pose_from_host(pose0_host).m, sizeof(u.pose_a));
     u.inlier_rate = ctx->cfg.inlier_rate; u.max_move2 = ctx->cfg.max_move2;
     u.rec = ctx->d_results; u.pnp = pnp_record(ctx, 1); u.counts = counts;
-    u.trk_ids = ctx->trk_id; u.tri = ctx->X3; u.trk_n = ctx->m_out;
+    u.trk_ids = ctx->carry.trk_id; u.tri = ctx->X3; u.trk_n = ctx->m_out;
     u.res = (svo_keyframe_result *)(s + c.res);
     launch_keyframe_update(u, st);
     timing_mark(ctx, "kf_update");
-    ctx->kf_clear = false; ctx->kf_last = true;
+    ctx->kf.clear = false;
     return SVO_OK;
 }
 
@@ -241,7 +241,7 @@ int keyframe_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
 int keyframe_read_result(svo_ctx *ctx, svo_keyframe_result *res)
 {
     const KfCut c = keyframe_cut(ctx->cfg.max_keypoints);
-    SVO_TRY(from_device(ctx, res, (const svo_keyframe_result *)(ctx->kf_buf + c.res), (size_t)1, SVO_MEM_HOST));
+    SVO_TRY(from_device(ctx, res, (const svo_keyframe_result *)(ctx->kf.buf + c.res), (size_t)1, SVO_MEM_HOST));
     return io_done(ctx, SVO_MEM_HOST);
 }
 
@@ -249,7 +249,7 @@ int keyframe_read_matches(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, svo_pt2f *xy,
 {
     const int K = ctx->cfg.max_keypoints;
     const KfCut c = keyframe_cut(K);
-    const uint8_t *s = ctx->kf_buf;
+    const uint8_t *s = ctx->kf.buf;
     const int *h;
     SVO_TRY(count_fetch(ctx, 0, s + c.counts, 2));
     SVO_TRY(counts_wait(ctx, &h));
@@ -272,7 +272,7 @@ int keyframe_read_table(svo_ctx *ctx, int64_t *ids, svo_pt3f *X, int cap, int *n
 {
     const int K = ctx->cfg.max_keypoints;
     const KfCut c = keyframe_cut(K);
-    const uint8_t *s = ctx->kf_buf;
+    const uint8_t *s = ctx->kf.buf;
     const KfState *state = (const KfState *)(s + c.state);
     const int *h;
     SVO_TRY(count_fetch(ctx, 0, &state->valid, 1));
@@ -318,8 +318,8 @@ int stage_keyframe_join(svo_ctx *ctx, const int64_t *tab_ids, const svo_pt3f *ta
                  i_xy = cut.add(sizeof(float2) * nt);
     const size_t r_X = cut.add(sizeof(float) * 3 * nc), r_xy = cut.add(sizeof(float2) * nc), r_trk = cut.add(sizeof(int) * nc),
                  r_row = cut.add(sizeof(int) * nc);
-    if (dev_reserve(ctx, &ctx->kf_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
-    uint8_t *s = ctx->kf_stage.base;
+    if (dev_reserve(ctx, &ctx->kf.stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+    uint8_t *s = ctx->kf.stage.base;
     SVO_TRY(to_device(ctx, (const long long *)tab_ids, (long long *)(s + i_ids), nr, mem, &a.tab_ids));
     SVO_TRY(to_device(ctx, (const float *)tab_X, (float *)(s + i_X), 3 * nr, mem, &a.tab_X));
     SVO_TRY(to_device(ctx, (const long long *)trk_ids, (long long *)(s + i_tid), nt, mem, &a.trk_ids));

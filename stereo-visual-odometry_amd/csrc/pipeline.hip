@@ -90,8 +90,9 @@ static int ingest_frames(svo_ctx *ctx, const uint8_t *L, const uint8_t *R, int p
 
 // A stream-set step: item i of the launch set works for stream ids[i]; init[i]: that stream has no previous frame.
 struct StreamStep { const int32_t *ids; const uint8_t *init; };
-static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first = false,
-                    const StreamStep *ss = nullptr);
+// The pose stage of a launch set.  carried: track carry ran on its pairs; os: an online step and the followers it runs.
+static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool carried,
+                    bool triangulate_first = false, const StreamStep *ss = nullptr, const OnlineStep *os = nullptr);
 static const char *kTGather = "stream_gather", *kTScatter = "stream_scatter";
 
 // What a frame carries from one step to the next -- the list exists here only.  work[k]: the working array behind segment k (frame
@@ -116,10 +117,10 @@ static int stream_segments(svo_ctx *ctx, uint8_t *work[kMaxSeg], size_t bytes[kM
         work[1] = (uint8_t *)ctx->kp_xy;        bytes[1] = cap * sizeof(float2);            is_count[1] = 0;
         work[2] = (uint8_t *)ctx->kp_resp;      bytes[2] = cap * sizeof(float);             is_count[2] = 0;
         work[3] = (uint8_t *)ctx->kp_n;         bytes[3] = sizeof(int);                     is_count[3] = 1;
-        if (ctx->carry_on) {
+        if (ctx->carry.on) {
             // svo_set_track_carry: the list's ids and ages travel with it
-            work[4] = (uint8_t *)ctx->kp_id;    bytes[4] = cap * sizeof(long long);         is_count[4] = 0;
-            work[5] = (uint8_t *)ctx->kp_age;   bytes[5] = cap * sizeof(int);               is_count[5] = 0;
+            work[4] = (uint8_t *)ctx->carry.kp_id;    bytes[4] = cap * sizeof(long long);         is_count[4] = 0;
+            work[5] = (uint8_t *)ctx->carry.kp_age;   bytes[5] = cap * sizeof(int);               is_count[5] = 0;
             return 6;
         }
     }
@@ -132,7 +133,7 @@ static const char *kTCarry = "carry";
 int carry_alloc(svo_ctx *ctx)
 {
     const size_t cap = (size_t)ctx->cfg.max_keypoints, nf = (size_t)ctx->n_img, np = (size_t)ctx->cfg.max_batch;
-    if (!ctx->carry_buf) {
+    if (!ctx->carry.buf) {
         BlockCut cut;
         const size_t o_next = cut.add(sizeof(long long)), o_id = cut.add(sizeof(long long) * cap * nf), o_age = cut.add(sizeof(int) * cap * nf),
                      o_tid = cut.add(sizeof(long long) * cap * np), o_tage = cut.add(sizeof(int) * cap * np),
@@ -141,12 +142,12 @@ int carry_alloc(svo_ctx *ctx)
         uint8_t *s = nullptr;
         if (dev_alloc(ctx, &s, cut.total()) != SVO_OK) return SVO_ERR_HIP;
         SVO_HIP(hipMemsetAsync(s, 0, cut.total(), ctx->stream));
-        ctx->carry_next = (long long *)(s + o_next);
-        ctx->kp_id = (long long *)(s + o_id); ctx->kp_age = (int *)(s + o_age);
-        ctx->trk_id = (long long *)(s + o_tid); ctx->trk_age = (int *)(s + o_tage);
-        ctx->carry_sorted = (int *)(s + o_sorted); ctx->carry_flag = s + o_flag; ctx->carry_dflag = s + o_dflag;
-        ctx->carry_dxy = (float2 *)(s + o_dxy); ctx->carry_dresp = (float *)(s + o_dresp);
-        ctx->carry_buf = s;
+        ctx->carry.next = (long long *)(s + o_next);
+        ctx->carry.kp_id = (long long *)(s + o_id); ctx->carry.kp_age = (int *)(s + o_age);
+        ctx->carry.trk_id = (long long *)(s + o_tid); ctx->carry.trk_age = (int *)(s + o_tage);
+        ctx->carry.sorted = (int *)(s + o_sorted); ctx->carry.flag = s + o_flag; ctx->carry.dflag = s + o_dflag;
+        ctx->carry.dxy = (float2 *)(s + o_dxy); ctx->carry.dresp = (float *)(s + o_dresp);
+        ctx->carry.buf = s;
     }
     StreamSet &ss = ctx->streams;
     if (ss.n > 0) {
@@ -170,26 +171,26 @@ static void launch_carry_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int 
     const size_t cap = (size_t)ctx->cfg.max_keypoints;
     CarryMergeArgs a{};
     a.w = ctx->cfg.width; a.h = ctx->cfg.height;
-    carry_grid(a.w, a.h, ctx->carry_min_distance, &a.cell, &a.cols, &a.rows);
-    a.min_d2 = ctx->carry_min_distance * ctx->carry_min_distance;
-    a.max_age = ctx->carry_max_age;
+    carry_grid(a.w, a.h, ctx->carry.min_distance, &a.cell, &a.cols, &a.rows);
+    a.min_d2 = ctx->carry.min_distance * ctx->carry.min_distance;
+    a.max_age = ctx->carry.max_age;
     a.cap = a.out_cap = (int)cap;
     a.stride = (int64_t)fstep * (int64_t)cap; a.n_stride = fstep;
     a.q = ctx->pts_out[2]; a.keep = ctx->keep;
-    a.p_resp = ctx->kp_resp + (size_t)fp0 * cap; a.p_id = ctx->kp_id + (size_t)fp0 * cap; a.p_age = ctx->kp_age + (size_t)fp0 * cap;
+    a.p_resp = ctx->kp_resp + (size_t)fp0 * cap; a.p_id = ctx->carry.kp_id + (size_t)fp0 * cap; a.p_age = ctx->carry.kp_age + (size_t)fp0 * cap;
     a.p_n = no_prev ? nullptr : ctx->kp_n + fp0; a.n_trk = 0;
     a.d_xy = ctx->kp_xy + (size_t)fc0 * cap; a.d_resp = ctx->kp_resp + (size_t)fc0 * cap; a.d_n = ctx->kp_n + fc0;
     a.o_xy = ctx->kp_xy + (size_t)fc0 * cap; a.o_resp = ctx->kp_resp + (size_t)fc0 * cap;
-    a.o_id = ctx->kp_id + (size_t)fc0 * cap; a.o_age = ctx->kp_age + (size_t)fc0 * cap;
+    a.o_id = ctx->carry.kp_id + (size_t)fc0 * cap; a.o_age = ctx->carry.kp_age + (size_t)fc0 * cap;
     a.o_n = ctx->kp_n + fc0;
-    a.trk_id = ctx->trk_id; a.trk_age = ctx->trk_age;
-    a.sorted = ctx->carry_sorted; a.flag = ctx->carry_flag; a.dflag = ctx->carry_dflag; a.s_dxy = ctx->carry_dxy; a.s_dresp = ctx->carry_dresp;
+    a.trk_id = ctx->carry.trk_id; a.trk_age = ctx->carry.trk_age;
+    a.sorted = ctx->carry.sorted; a.flag = ctx->carry.flag; a.dflag = ctx->carry.dflag; a.s_dxy = ctx->carry.dxy; a.s_dresp = ctx->carry.dresp;
     if (!ss) {
         // the online ring: one pair, one counter
-        a.next_id = ctx->carry_next;
-        a.fresh[0] = !no_prev && !ctx->carry_ids[fp0 & 1];
-        a.restart[0] = ctx->carry_restart;
-        ctx->carry_restart = false;
+        a.next_id = ctx->carry.next;
+        a.fresh[0] = !no_prev && !ctx->carry.ids[fp0 & 1];
+        a.restart[0] = ctx->carry.restart;
+        ctx->carry.restart = false;
         launch_carry_merge(a, 1, ctx->stream);
         return;
     }
@@ -310,7 +311,7 @@ static void for_stream_chunks(const int32_t *ids, const uint8_t *init, int m, F 
 // solver, gates, chain, optional copy of the records to `results_dev`) on `back_stream`, which is
 // the context's stream, or -- overlap mode -- the side stream, ordered after the front by an event.
 static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, const double *pose0_host,
-                     svo_step_result *results_dev, const StreamStep *ss = nullptr)
+                     svo_step_result *results_dev, const StreamStep *ss = nullptr, const OnlineStep *os = nullptr)
 {
     const PyrGeom &g = ctx->geom;
     const int cap = ctx->cfg.max_keypoints;
@@ -331,7 +332,7 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
         const SnapSpec snap{(const int *)ctx->orb_n, (const int *)ctx->orb_overflow, fp0, fc0, fstep, 2};
         launch_triangulate_batch(ctx, n_pairs, cap, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, &snap);
         mark(ctx, kTTri);
-        return run_back(ctx, n_pairs, pose0_host, results_dev, false, ss);
+        return run_back(ctx, n_pairs, pose0_host, results_dev, /*carried*/ false, false, ss, os);
     }
     auto S = [&](int slot) { return ctx->bslots + (size_t)slot * g.slot_bytes; };
     LkArgs a{};
@@ -377,12 +378,11 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
     if (tri_side && ctx->overlap && results_dev != nullptr && !ss) {
         launch_snap_counts(ctx, n_pairs, snap, ctx->stream);
         mark(ctx, kTTri);
-        return run_back(ctx, n_pairs, pose0_host, results_dev, /*triangulate_first*/ true);
+        return run_back(ctx, n_pairs, pose0_host, results_dev, /*carried*/ false, /*triangulate_first*/ true);
     }
     launch_triangulate_batch(ctx, n_pairs, cap, ctx->cmp[0], ctx->cmp[1], ctx->m_out, 0, &snap);
     mark(ctx, kTTri);
-    ctx->carry_last_pairs = ctx->carry_on ? n_pairs : 0;
-    if (ctx->carry_on) {
+    if (ctx->carry.on) {
         // svo_set_track_carry: the new frames' lists = what was just tracked into them + their detections; the counts the
         // pose stage reports are already frozen.  A stream set stores the new frames only now.
         launch_carry_pairs(ctx, n_pairs, fp0, fc0, fstep, ss, false);
@@ -392,13 +392,13 @@ static int run_pairs(svo_ctx *ctx, int n_pairs, int fp0, int fc0, int fstep, con
             mark(ctx, kTScatter);
         }
     }
-    return run_back(ctx, n_pairs, pose0_host, results_dev, false, ss);
+    return run_back(ctx, n_pairs, pose0_host, results_dev, ctx->carry.on, false, ss, os);
 }
 
 // Pose stage: solvePnPRansac(X, t2_left) (:299 / :200), gates, frame_pose_ chain, optional copy of the
 // records; on the side stream in overlap mode.
-static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool triangulate_first,
-                    const StreamStep *ss)
+static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_step_result *results_dev, bool carried,
+                    bool triangulate_first, const StreamStep *ss, const OnlineStep *os)
 {
     hipStream_t bs = ctx->stream;
     const bool side = ctx->overlap && results_dev != nullptr && !ss;      // a stream-set step is ordered on the context's stream
@@ -412,9 +412,7 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
     launch_pnp_batch(ctx, n_pairs, ctx->cmp[3], ctx->m_out, 0, bs);
     if (!side) mark(ctx, kTPnp);
     // svo_set_pose_refine: robust two-view refinement of every pair's PnP record in place, before the gates read it
-    ctx->refine_last_pairs = ctx->refine_mode != SVO_REFINE_OFF ? n_pairs : 0;
-    ctx->refine_last_mode = ctx->refine_mode;
-    if (ctx->refine_last_pairs) {
+    if (ctx->refine_mode != SVO_REFINE_OFF) {
         if (ctx->refine_mode == SVO_REFINE_BA) launch_ba_batch(ctx, n_pairs, bs);
         else launch_refine_batch(ctx, n_pairs, bs);
         if (!side) mark(ctx, kTRefine);
@@ -429,9 +427,13 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
         launch_finalize_chain(ctx, n_pairs, ctx->kp_n_snap, ctx->kp_n_snap + n_pairs, ovf, pose0_host, bs);
     }
     // svo_set_window_ba: the online chain's landmark table moves on by this pair and is adjusted; an applied result rewrites the record's pose
-    if (ctx->win_step) SVO_TRY(window_fused_step(ctx, pose0_host, bs));
+    if (os && os->window) SVO_TRY(window_fused_step(ctx, pose0_host, bs));
     // svo_set_keyframe: the pair's tracks joined with the keyframe's table, one more solve, and where it is accepted its pose in the record
-    if (ctx->kf_step) SVO_TRY(keyframe_fused_step(ctx, pose0_host, bs));
+    if (os && os->keyframe) SVO_TRY(keyframe_fused_step(ctx, pose0_host, bs));
+    // everything is queued: what this launch ran (the followers belong to online steps; other launches leave theirs alone)
+    LastLaunch &last = ctx->last;
+    last.pairs = n_pairs; last.carry = carried; last.refine_mode = ctx->refine_mode;
+    if (os) { last.window_frames = os->window ? ctx->win.frames : 0; last.keyframe = os->keyframe; }
     const int rc = deliver_records(ctx, ctx->d_results, n_pairs, results_dev, SVO_MEM_DEVICE, bs);
     if (rc) return rc;
     if (side) {
@@ -441,6 +443,25 @@ static int run_back(svo_ctx *ctx, int n_pairs, const double *pose0_host, svo_ste
         mark(ctx, kTFin);
     }
     return SVO_OK;
+}
+
+// When the online chain breaks -- the ONE statement of it.  Every entry point that starts, re-seats or reconfigures the chain
+// calls this; nothing else sets a "start fresh" flag, and only the fused step that honours one clears it (launch_carry_pairs,
+// window_fused_step, keyframe_fused_step).
+//
+//   event                                                   track ids     window table   keyframe
+//   kChainNew          svo_reset, a chain's first frame      start at 0    cleared        dropped
+//   kChainPoseSet      svo_set_pose                          run on        cleared        dropped    their poses belong to the chain that was
+//   kChainCarrySet     svo_set_track_carry, switched on      run on        cleared        dropped    (a list without ids is fresh: carry.ids[])
+//   kChainWindowSet    svo_set_window_ba, on or off          run on        cleared        kept
+//   kChainKeyframeSet  svo_set_keyframe, on or off           run on        kept           dropped
+//
+// A failed step is no event of the host's: the kernels read the record's `ok` (the window clears its table, the keyframe stays).
+void chain_event(svo_ctx *ctx, ChainEvent ev)
+{
+    if (ev == kChainNew) ctx->carry.restart = true;
+    if (ev != kChainKeyframeSet) ctx->win.clear = true;
+    if (ev != kChainWindowSet) ctx->kf.clear = true;
 }
 
 int deliver_records(svo_ctx *ctx, const svo_step_result *d_src, int n, svo_step_result *out, int mem, hipStream_t st)
@@ -515,14 +536,14 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
     int rc = ingest_frames(ctx, left, right, pitch, 0, cur, 1);
     if (rc) return rc;
     memset(res, 0, sizeof(*res));
-    ctx->carry_ids[cur] = ctx->carry_on;
+    ctx->carry.ids[cur] = ctx->carry.on;
     if (ctx->online_frames == 0) {
-        ctx->win_clear = true; ctx->win_last = false;      // svo_set_window_ba, T1: a chain's first frame
-        ctx->kf_clear = true; ctx->kf_last = false;        // svo_set_keyframe, K1
+        chain_event(ctx, kChainNew);
+        ctx->last.window_frames = 0; ctx->last.keyframe = false;      // no pair, no follower ran
         // StereoInit_f2f (:78-92): detect only
         int n_cur;
         SVO_TRY(count_read(ctx, ctx->cfg.track_mode == SVO_MODE_ORB ? ctx->orb_n + 2 * cur : ctx->kp_n + cur, &n_cur));
-        if (ctx->carry_on) {                     // svo_set_track_carry: the chain's first list gets its ids (the count above stays the detector's)
+        if (ctx->carry.on) {                     // svo_set_track_carry: the chain's first list gets its ids (the count above stays the detector's)
             launch_carry_pairs(ctx, 1, prev, cur, 0, nullptr, /*no_prev*/ true);
             mark(ctx, kTCarry);
             SVO_HIP(hipGetLastError());
@@ -533,12 +554,8 @@ int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, 
         ctx->online_frames = 1; ctx->online_cur = cur; ctx->online_tracked = 0;
         return SVO_OK;
     }
-    ctx->win_step = ctx->win_frames > 0 && ctx->carry_on;
-    ctx->win_last = false; ctx->win_last_frames = ctx->win_frames;
-    ctx->kf_step = ctx->kf_on && ctx->carry_on;
-    ctx->kf_last = false;
-    rc = run_pairs(ctx, 1, prev, cur, 0, ctx->pose, nullptr);
-    ctx->win_step = false; ctx->kf_step = false;
+    const OnlineStep step{ctx->win.frames > 0 && ctx->carry.on, ctx->kf.on && ctx->carry.on};
+    rc = run_pairs(ctx, 1, prev, cur, 0, ctx->pose, nullptr, nullptr, &step);
     if (rc) return rc;
     SVO_HIP(hipGetLastError());
     rc = deliver_records(ctx, ctx->d_results, 1, res, SVO_MEM_HOST, ctx->stream);
@@ -572,7 +589,7 @@ int pipeline_streams_create(svo_ctx *ctx, int n_streams)
     ss.restart.assign((size_t)n_streams, 1);
     ss.call = 0;
     ss.n = n_streams;                                  // the set exists from here on
-    if (ctx->carry_buf) SVO_TRY(carry_alloc(ctx));     // svo_set_track_carry came first: the store's ids, ages and counters
+    if (ctx->carry.buf) SVO_TRY(carry_alloc(ctx));     // svo_set_track_carry came first: the store's ids, ages and counters
     launch_streams_set_pose(ctx, 0, n_streams, nullptr);
     SVO_HIP(hipGetLastError());
     return SVO_OK;
@@ -650,7 +667,7 @@ int pipeline_streams_step(svo_ctx *ctx, const int32_t *ids, int m, const uint8_t
     mark(ctx, kTGather);
     int rc = ingest_frames(ctx, L, R, pitch, m == 1 ? 0 : frame_stride, m, m);
     if (rc) return rc;
-    if (!ctx->carry_on) {                               // (with track carry the lists are still to be merged: run_pairs stores the frames)
+    if (!ctx->carry.on) {                               // (with track carry the lists are still to be merged: run_pairs stores the frames)
         for_stream_chunks(ids, nullptr, m, [&](const StreamTable &tab, int i0, int n) { launch_stream_copy(ctx, tab, n, m + i0, /*to_store*/ true); });
         mark(ctx, kTScatter);
         for (int i = 0; i < m; i++) ss.has_ids[(size_t)ids[i]] = 0;

@@ -355,6 +355,25 @@ extern "C" int svo_wait_results(svo_ctx *ctx)
     return SVO_OK;
 }
 
+// The read-backs' common start: what is asked for exists (`ran`, else the ARG error `why_not`), the context's device is current
+// and a pose stage still on the side stream is ordered before the context's stream.
+static int read_back_ready(svo_ctx *ctx, bool ran, const char *why_not)
+{
+    SVO_ARG(ran, why_not);
+    SVO_HIP(hipSetDevice(ctx->device));
+    return svo_wait_results(ctx) == SVO_OK ? SVO_OK : SVO_ERR_HIP;
+}
+
+// What a follower stage of the online chain (`name`) needs before it is switched on: an LK-mode context, track carry on, and
+// the other stage that rewrites the step's pose off.
+static int follower_may_start(svo_ctx *ctx, const std::string &name, bool other_on, const std::string &other, const char *other_off)
+{
+    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, name + " is an LK-mode option");
+    if (!ctx->carry.on) { ctx->err = name + " needs track carry (svo_set_track_carry) on"; return SVO_ERR_STATE; }
+    if (other_on) { ctx->err = other + " is on and rewrites the step's pose too (" + other_off + " first)"; return SVO_ERR_STATE; }
+    return SVO_OK;
+}
+
 // ABI v7: ordering against work on OTHER streams on the device, without a host synchronisation.
 extern "C" int svo_wait_stream(svo_ctx *ctx, void *hip_stream)
 {
@@ -737,9 +756,7 @@ extern "C" int svo_reset(svo_ctx *ctx)
 {
     if (!ctx) return SVO_ERR_ARG;
     ctx->online_frames = 0; ctx->online_cur = 0;
-    ctx->carry_restart = true;                   // svo_set_track_carry: the next chain's ids start at 0
-    ctx->win_clear = true;                       // svo_set_window_ba, T1
-    ctx->kf_clear = true;                        // svo_set_keyframe, K1
+    chain_event(ctx, kChainNew);
     pose_identity16(ctx->pose);
     return SVO_OK;
 }
@@ -755,8 +772,7 @@ extern "C" int svo_set_pose(svo_ctx *ctx, const double pose[16])
 {
     if (!ctx || !pose) return SVO_ERR_ARG;
     memcpy(ctx->pose, pose, sizeof(double) * 16);
-    ctx->win_clear = true;                       // svo_set_window_ba, T1: the window's poses belong to the chain that was
-    ctx->kf_clear = true;                        // svo_set_keyframe, K1: so does the keyframe's
+    chain_event(ctx, kChainPoseSet);
     return SVO_OK;
 }
 
@@ -889,7 +905,7 @@ static int track_batch(svo_ctx *ctx, int w, int h, bool resize, const uint8_t *l
     SVO_ARG(n_frames >= 2 && n_frames - 1 <= ctx->cfg.max_batch, "n_frames - 1 must be in [1, max_batch]");
     SVO_ARG(pitch >= w && frame_stride >= (int64_t)pitch * h, "bad pitch / frame_stride");
     SVO_ARG(results_mem == SVO_MEM_HOST || results_mem == SVO_MEM_DEVICE, "bad results_mem");
-    if (ctx->carry_on) {
+    if (ctx->carry.on) {
         ctx->err = "track carry is on (svo_set_track_carry): a batch treats its pairs as independent; use svo_add_frame / svo_streams_step";
         return SVO_ERR_STATE;
     }
@@ -1129,8 +1145,8 @@ extern "C" int svo_streams_count(const svo_ctx *ctx, int *n_streams)
 static int streams_step(svo_ctx *ctx, int w, int h, bool resize, const int32_t *stream_ids, int m, const uint8_t *lefts,
                         const uint8_t *rights, int pitch, int64_t frame_stride, int mem, svo_step_result *results, int results_mem)
 {
-    if (ctx->win_frames > 0) { ctx->err = "the sliding window (svo_set_window_ba) works on the online chain only: stream sets have no table yet"; return SVO_ERR_STATE; }
-    if (ctx->kf_on) { ctx->err = "keyframe mode (svo_set_keyframe) works on the online chain only: stream sets have no keyframe yet"; return SVO_ERR_STATE; }
+    if (ctx->win.frames > 0) { ctx->err = "the sliding window (svo_set_window_ba) works on the online chain only: stream sets have no table yet"; return SVO_ERR_STATE; }
+    if (ctx->kf.on) { ctx->err = "keyframe mode (svo_set_keyframe) works on the online chain only: stream sets have no keyframe yet"; return SVO_ERR_STATE; }
     SVO_ARG(ctx->streams.n > 0, "no stream set (svo_streams_create)");
     SVO_ARG(stream_ids && lefts && rights && (results || results_mem == SVO_MEM_DEVICE), "null pointer");
     SVO_ARG(m >= 1 && m <= (ctx->cfg.max_batch + 1) / 2, "m must be in [1, (max_batch + 1) / 2]");
@@ -1310,9 +1326,7 @@ extern "C" int svo_get_batch_tracks(svo_ctx *ctx, int pair, svo_pt2f *t1_left, s
 {
     if (!ctx) return SVO_ERR_ARG;
     SVO_ARG(n_out && cap >= 0, "null output");
-    SVO_ARG(pair >= 0 && pair < ctx->last_batch_pairs, "pair is not part of the last batch launch");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    SVO_TRY(read_back_ready(ctx, pair >= 0 && pair < ctx->last_batch_pairs, "pair is not part of the last batch launch"));
     int n;
     SVO_TRY(count_read(ctx, ctx->m_out + pair, &n));
     SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "corrupt track count");
@@ -1610,9 +1624,7 @@ extern "C" int svo_gftt_detect(svo_ctx *ctx, const uint8_t *img, int width, int 
 // ---- robust two-view pose refinement after solvePnPRansac (refine.hip: pose_refine_kernel) ----------------------------
 static int set_pose_refine(svo_ctx *ctx, int mode, int rounds, int iters, double sigma_px, int min_inliers)
 {
-    SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
-    SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
-    SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
+    SVO_TRY(check_optimiser_params(ctx, rounds, iters, sigma_px));
     SVO_ARG(min_inliers >= 1, "min_inliers < 1");
     if (mode != SVO_REFINE_OFF) { const int rc = mode == SVO_REFINE_BA ? ba_alloc(ctx) : refine_alloc(ctx); if (rc) return rc; }
     ctx->refine_mode = mode; ctx->refine_rounds = rounds; ctx->refine_iters = iters;
@@ -1657,11 +1669,9 @@ extern "C" int svo_refine_pose(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f
 extern "C" int svo_get_refine_result(svo_ctx *ctx, int pair, svo_refine_result *res, uint8_t *active, int cap, int *n_out)
 {
     if (!ctx) return SVO_ERR_ARG;
-    SVO_ARG(ctx->refine_last_pairs > 0 && ctx->refine_buf, "the refinement stage was off for the last launch (svo_set_pose_refine)");
-    SVO_ARG(pair >= 0 && pair < ctx->refine_last_pairs, "pair is not part of the last launch");
+    SVO_TRY(read_back_ready(ctx, ctx->last.refine_mode != SVO_REFINE_OFF && ctx->refine_buf, "the refinement stage was off for the last launch (svo_set_pose_refine)"));
+    SVO_ARG(pair >= 0 && pair < ctx->last.pairs, "pair is not part of the last launch");
     SVO_ARG(active == nullptr || cap >= 0, "negative capacity");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
     return refine_read_result(ctx, pair, res, active, cap, n_out);
 }
 
@@ -1678,12 +1688,9 @@ extern "C" int svo_refine_ba(svo_ctx *ctx, const svo_pt3f *obj, const svo_pt2f *
 extern "C" int svo_get_refine_points(svo_ctx *ctx, int pair, double *X, int cap, int *n_out)
 {
     if (!ctx) return SVO_ERR_ARG;
-    SVO_ARG(ctx->refine_last_pairs > 0 && ctx->refine_last_mode == SVO_REFINE_BA && ctx->ba_buf,
-            "the last launch did not run in SVO_REFINE_BA mode (svo_set_pose_refine_ba)");
-    SVO_ARG(pair >= 0 && pair < ctx->refine_last_pairs, "pair is not part of the last launch");
+    SVO_TRY(read_back_ready(ctx, ctx->last.refine_mode == SVO_REFINE_BA && ctx->ba_buf, "the last launch did not run in SVO_REFINE_BA mode (svo_set_pose_refine_ba)"));
+    SVO_ARG(pair >= 0 && pair < ctx->last.pairs, "pair is not part of the last launch");
     SVO_ARG(X == nullptr || cap >= 0, "negative capacity");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
     return ba_read_points(ctx, pair, X, cap, n_out);
 }
 
@@ -1696,25 +1703,24 @@ static bool carry_params_ok(double min_distance, int max_age)
 extern "C" int svo_set_track_carry(svo_ctx *ctx, int on, double min_distance, int max_age)
 {
     if (!ctx) return SVO_ERR_ARG;
-    if (!on && ctx->win_frames > 0) { ctx->err = "the sliding window is on and needs track carry (svo_set_window_ba(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
-    if (!on && ctx->kf_on) { ctx->err = "keyframe mode is on and needs track carry (svo_set_keyframe(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
-    if (!on) { ctx->carry_on = false; return SVO_OK; }               // off: the other arguments are ignored
+    if (!on && ctx->win.frames > 0) { ctx->err = "the sliding window is on and needs track carry (svo_set_window_ba(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
+    if (!on && ctx->kf.on) { ctx->err = "keyframe mode is on and needs track carry (svo_set_keyframe(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
+    if (!on) { ctx->carry.on = false; return SVO_OK; }               // off: the other arguments are ignored
     SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "track carry is an LK-mode option (ORB mode matches descriptors frame to frame)");
     SVO_ARG(carry_params_ok(min_distance, max_age), "min_distance must be finite and in [1, 256], max_age >= 0");
     SVO_HIP(hipSetDevice(ctx->device));
     SVO_TRY(carry_alloc(ctx));                                       // first enabling call: the working frames' and an existing stream set's share
-    ctx->carry_on = true; ctx->carry_min_distance = min_distance; ctx->carry_max_age = max_age;
-    ctx->win_clear = true;                                           // svo_set_window_ba, T1
-    ctx->kf_clear = true;                                            // svo_set_keyframe, K1
+    ctx->carry.on = true; ctx->carry.min_distance = min_distance; ctx->carry.max_age = max_age;
+    chain_event(ctx, kChainCarrySet);
     return SVO_OK;
 }
 
 extern "C" int svo_get_track_carry(const svo_ctx *ctx, int *on, double *min_distance, int *max_age)
 {
     if (!ctx) return SVO_ERR_ARG;
-    if (on) *on = ctx->carry_on ? 1 : 0;
-    if (min_distance) *min_distance = ctx->carry_on ? ctx->carry_min_distance : 0.0;
-    if (max_age) *max_age = ctx->carry_on ? ctx->carry_max_age : 0;
+    if (on) *on = ctx->carry.on ? 1 : 0;
+    if (min_distance) *min_distance = ctx->carry.on ? ctx->carry.min_distance : 0.0;
+    if (max_age) *max_age = ctx->carry.on ? ctx->carry.max_age : 0;
     return SVO_OK;
 }
 
@@ -1744,8 +1750,8 @@ extern "C" int svo_carry_merge(svo_ctx *ctx, int width, int height, double min_d
                  i_dxy = cut.add(host ? sizeof(float2) * nd : 0), i_dresp = cut.add(host ? sizeof(float) * nd : 0);
     const size_t r_xy = cut.add(host ? sizeof(float2) * nc : 0), r_resp = cut.add(host ? sizeof(float) * nc : 0),
                  r_id = cut.add(host ? sizeof(long long) * nc : 0), r_age = cut.add(host ? sizeof(int) * nc : 0), r_src = cut.add(host ? sizeof(int) * nc : 0);
-    if (dev_reserve(ctx, &ctx->carry_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
-    uint8_t *s = ctx->carry_stage.base;
+    if (dev_reserve(ctx, &ctx->carry.stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+    uint8_t *s = ctx->carry.stage.base;
     CarryMergeArgs a{};
     a.w = width; a.h = height;
     carry_grid(width, height, min_distance, &a.cell, &a.cols, &a.rows);
@@ -1792,30 +1798,26 @@ extern "C" int svo_window_update(svo_ctx *ctx, int frames, const svo_window_tabl
 extern "C" int svo_set_window_ba(svo_ctx *ctx, int frames, int rounds, int iters, double sigma_px, int min_obs)
 {
     if (!ctx) return SVO_ERR_ARG;
-    if (frames == 0) { ctx->win_frames = 0; ctx->win_clear = true; return SVO_OK; }      // off: the other arguments are ignored
-    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "the sliding window is an LK-mode option");
+    if (frames == 0) { ctx->win.frames = 0; chain_event(ctx, kChainWindowSet); return SVO_OK; }      // off: the other arguments are ignored
     SVO_ARG(frames >= 2 && frames <= SVO_WINDOW_MAX_FRAMES, "frames must be 0 or 2..SVO_WINDOW_MAX_FRAMES");
-    SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
-    SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
-    SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
+    SVO_TRY(check_optimiser_params(ctx, rounds, iters, sigma_px));
     SVO_ARG(min_obs >= 1, "min_obs < 1");
-    if (!ctx->carry_on) { ctx->err = "the sliding window needs track carry (svo_set_track_carry) on"; return SVO_ERR_STATE; }
-    if (ctx->kf_on) { ctx->err = "keyframe mode is on and rewrites the step's pose too (svo_set_keyframe(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
+    SVO_TRY(follower_may_start(ctx, "the sliding window", ctx->kf.on, "keyframe mode", "svo_set_keyframe(ctx, 0, ...)"));
     SVO_TRY(window_alloc(ctx, frames));
-    ctx->win_frames = frames; ctx->win_rounds = rounds; ctx->win_iters = iters; ctx->win_sigma = sigma_px; ctx->win_min_obs = min_obs;
-    ctx->win_clear = true;
+    ctx->win.frames = frames; ctx->win.rounds = rounds; ctx->win.iters = iters; ctx->win.sigma = sigma_px; ctx->win.min_obs = min_obs;
+    chain_event(ctx, kChainWindowSet);
     return SVO_OK;
 }
 
 extern "C" int svo_get_window_ba(const svo_ctx *ctx, int *frames, int *rounds, int *iters, double *sigma_px, int *min_obs)
 {
     if (!ctx) return SVO_ERR_ARG;
-    const bool on = ctx->win_frames > 0;
-    if (frames) *frames = ctx->win_frames;
-    if (rounds) *rounds = on ? ctx->win_rounds : 0;
-    if (iters) *iters = on ? ctx->win_iters : 0;
-    if (sigma_px) *sigma_px = on ? ctx->win_sigma : 0.0;
-    if (min_obs) *min_obs = on ? ctx->win_min_obs : 0;
+    const bool on = ctx->win.frames > 0;
+    if (frames) *frames = ctx->win.frames;
+    if (rounds) *rounds = on ? ctx->win.rounds : 0;
+    if (iters) *iters = on ? ctx->win.iters : 0;
+    if (sigma_px) *sigma_px = on ? ctx->win.sigma : 0.0;
+    if (min_obs) *min_obs = on ? ctx->win.min_obs : 0;
     return SVO_OK;
 }
 
@@ -1823,9 +1825,7 @@ extern "C" int svo_get_window(svo_ctx *ctx, const svo_window_table *out, int cap
 {
     if (!ctx) return SVO_ERR_ARG;
     SVO_ARG(out && out->counts && cap >= 0, "null table / counts");
-    SVO_ARG(ctx->win_last && ctx->win_block.base, "the sliding window was off for the last svo_add_frame step (svo_set_window_ba)");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    SVO_TRY(read_back_ready(ctx, ctx->last.window_frames > 0 && ctx->win.block.base, "the sliding window was off for the last svo_add_frame step (svo_set_window_ba)"));
     return window_read(ctx, out, cap);
 }
 
@@ -1833,9 +1833,7 @@ extern "C" int svo_get_window_result(svo_ctx *ctx, svo_window_result *res)
 {
     if (!ctx) return SVO_ERR_ARG;
     SVO_ARG(res, "null result");
-    SVO_ARG(ctx->win_last && ctx->win_block.base, "the sliding window was off for the last svo_add_frame step (svo_set_window_ba)");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    SVO_TRY(read_back_ready(ctx, ctx->last.window_frames > 0 && ctx->win.block.base, "the sliding window was off for the last svo_add_frame step (svo_set_window_ba)"));
     return window_read_result(ctx, res);
 }
 
@@ -1850,35 +1848,30 @@ extern "C" int svo_window_ba(svo_ctx *ctx, const svo_window_table *table, int ca
 extern "C" int svo_set_keyframe(svo_ctx *ctx, int on, int min_tracks, int max_gap)
 {
     if (!ctx) return SVO_ERR_ARG;
-    if (!on) { ctx->kf_on = false; ctx->kf_clear = true; return SVO_OK; }                 // off: the other arguments are ignored
-    SVO_ARG(ctx->cfg.track_mode == SVO_MODE_LK, "keyframe mode is an LK-mode option");
+    if (!on) { ctx->kf.on = false; chain_event(ctx, kChainKeyframeSet); return SVO_OK; }      // off: the other arguments are ignored
     SVO_ARG(min_tracks >= 4 && min_tracks <= ctx->cfg.max_keypoints, "min_tracks outside 4..max_keypoints");
     SVO_ARG(max_gap >= 0 && max_gap != 1, "max_gap must be 0 (no limit) or >= 2: the smallest gap of a solve is 2");
     SVO_ARG(ctx->cfg.max_batch >= 2, "keyframe mode solves on item 1 of the pose workspace: max_batch must be >= 2");
-    if (!ctx->carry_on) { ctx->err = "keyframe mode needs track carry (svo_set_track_carry) on"; return SVO_ERR_STATE; }
-    if (ctx->win_frames > 0) { ctx->err = "the sliding window is on and rewrites the step's pose too (svo_set_window_ba(ctx, 0, ...) first)"; return SVO_ERR_STATE; }
+    SVO_TRY(follower_may_start(ctx, "keyframe mode", ctx->win.frames > 0, "the sliding window", "svo_set_window_ba(ctx, 0, ...)"));
     SVO_TRY(keyframe_alloc(ctx));
-    ctx->kf_on = true; ctx->kf_min_tracks = min_tracks; ctx->kf_max_gap = max_gap;
-    ctx->kf_clear = true;
+    ctx->kf.on = true; ctx->kf.min_tracks = min_tracks; ctx->kf.max_gap = max_gap;
+    chain_event(ctx, kChainKeyframeSet);
     return SVO_OK;
 }
 
 extern "C" int svo_get_keyframe(const svo_ctx *ctx, int *on, int *min_tracks, int *max_gap)
 {
     if (!ctx) return SVO_ERR_ARG;
-    if (on) *on = ctx->kf_on ? 1 : 0;
-    if (min_tracks) *min_tracks = ctx->kf_on ? ctx->kf_min_tracks : 0;
-    if (max_gap) *max_gap = ctx->kf_on ? ctx->kf_max_gap : 0;
+    if (on) *on = ctx->kf.on ? 1 : 0;
+    if (min_tracks) *min_tracks = ctx->kf.on ? ctx->kf.min_tracks : 0;
+    if (max_gap) *max_gap = ctx->kf.on ? ctx->kf.max_gap : 0;
     return SVO_OK;
 }
 
-// the read-backs' common start: the mode ran in the last online step, and that step is complete
 static int keyframe_last_step(svo_ctx *ctx)
 {
-    SVO_ARG(ctx->online_frames >= 2 && ctx->kf_last && ctx->kf_buf, "keyframe mode was off for the last svo_add_frame step, or no pair has been tracked (svo_set_keyframe)");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
-    return SVO_OK;
+    return read_back_ready(ctx, ctx->online_frames >= 2 && ctx->last.keyframe && ctx->kf.buf,
+                           "keyframe mode was off for the last svo_add_frame step, or no pair has been tracked (svo_set_keyframe)");
 }
 
 extern "C" int svo_get_keyframe_result(svo_ctx *ctx, svo_keyframe_result *res)
@@ -1932,28 +1925,24 @@ extern "C" int svo_get_frame_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages
     SVO_ARG(n_out && cap >= 0, "null output");
     SVO_ARG(ctx->online_frames > 0, "no frame has been added");
     const int cur = ctx->online_cur;
-    SVO_ARG(ctx->carry_ids[cur] && ctx->carry_buf, "track carry was off when the last frame was added (svo_set_track_carry)");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    SVO_TRY(read_back_ready(ctx, ctx->carry.ids[cur] && ctx->carry.buf, "track carry was off when the last frame was added (svo_set_track_carry)"));
     int n = 0;
     SVO_TRY(count_read(ctx, ctx->kp_n + cur, &n));
     const size_t kcap = (size_t)ctx->cfg.max_keypoints;
     n = n < (int)kcap ? n : (int)kcap;
-    return read_ids(ctx, ctx->kp_id, ctx->kp_age, (size_t)cur * kcap, n, ids, ages, cap, n_out);
+    return read_ids(ctx, ctx->carry.kp_id, ctx->carry.kp_age, (size_t)cur * kcap, n, ids, ages, cap, n_out);
 }
 
 // ids / ages-at-t1 of the tracks of pair `pair` of the last fused launch, in the order of svo_get_batch_tracks' lists
 static int pair_track_ids(svo_ctx *ctx, int pair, int64_t *ids, int32_t *ages, int cap, int *n_out)
 {
     SVO_ARG(n_out && cap >= 0, "null output");
-    SVO_ARG(ctx->carry_last_pairs > 0 && ctx->carry_buf, "track carry was off for the last step (svo_set_track_carry)");
-    SVO_ARG(pair >= 0 && pair < ctx->carry_last_pairs, "item is not part of the last step");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    SVO_TRY(read_back_ready(ctx, ctx->last.carry && ctx->carry.buf, "track carry was off for the last step (svo_set_track_carry)"));
+    SVO_ARG(pair >= 0 && pair < ctx->last.pairs, "item is not part of the last step");
     int n;
     SVO_TRY(count_read(ctx, ctx->m_out + pair, &n));
     SVO_ARG(n >= 0 && n <= ctx->cfg.max_keypoints, "corrupt track count");
-    return read_ids(ctx, ctx->trk_id, ctx->trk_age, (size_t)pair * ctx->cfg.max_keypoints, n, ids, ages, cap, n_out);
+    return read_ids(ctx, ctx->carry.trk_id, ctx->carry.trk_age, (size_t)pair * ctx->cfg.max_keypoints, n, ids, ages, cap, n_out);
 }
 
 extern "C" int svo_get_last_track_ids(svo_ctx *ctx, int64_t *ids, int32_t *ages, int cap, int *n_out)
@@ -1977,10 +1966,8 @@ extern "C" int svo_streams_get_frame_tracks(svo_ctx *ctx, int stream_id, svo_key
     SVO_ARG(ss.n > 0, "no stream set (svo_streams_create)");
     SVO_ARG(stream_id >= 0 && stream_id < ss.n, "stream id out of range");
     SVO_ARG(n_out && cap >= 0, "null output");
-    SVO_ARG(ss.n_frames[(size_t)stream_id] > 0 && ss.has_ids[(size_t)stream_id] && ss.seg[4] && ss.seg[5],
-            "the stream has no stored list with ids (no frame yet, or track carry was off for its last step)");
-    SVO_HIP(hipSetDevice(ctx->device));
-    if (svo_wait_results(ctx) != SVO_OK) return SVO_ERR_HIP;
+    SVO_TRY(read_back_ready(ctx, ss.n_frames[(size_t)stream_id] > 0 && ss.has_ids[(size_t)stream_id] && ss.seg[4] && ss.seg[5],
+                            "the stream has no stored list with ids (no frame yet, or track carry was off for its last step)"));
     const size_t kcap = (size_t)ctx->cfg.max_keypoints, sid = (size_t)stream_id;
     int n = 0;
     SVO_TRY(count_read(ctx, (const int *)ss.seg[3] + sid, &n));

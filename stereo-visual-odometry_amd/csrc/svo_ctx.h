@@ -1,20 +1,16 @@
 // svo_ctx.h -- the context object behind the C-ABI (internal).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <functional>
 #include <string>
 #include <utility>
 #include <vector>
 #include "../../include/svo_abi.h"
 #include "block_cut.h"
+#include "chain_stages.h"
 #include "pinned_layout.h"
 #include "svo_kernels.h"
-
-// A block of device memory that appears when a feature is first used and grows with the largest request: dev_reserve.
-struct DevScratch {
-    uint8_t *base = nullptr;
-    size_t bytes = 0;
-};
 
 // What a context owns on the device, all of it released by free_all() (svo_abi.hip) and by nothing else.  Device memory has
 // three lifetimes, and one function each:
@@ -210,42 +206,12 @@ struct svo_ctx {
     int refine_mode = SVO_REFINE_OFF, refine_rounds = 4, refine_iters = 10, refine_min_inliers = 6;
     double refine_sigma = 1.0;
     uint8_t *refine_buf = nullptr;                       // ONE block: records, per-point flags, stage-call scratch (refine.hip)
-    int refine_last_pairs = 0;                           // pairs the stage refined in the most recent fused launch (0: it was off)
-    int refine_last_mode = SVO_REFINE_OFF;               // ... and the mode that launch ran in
     uint8_t *ba_buf = nullptr;                           // SVO_REFINE_BA: the pairs' points, two buffers, + stage-call scratch (ba.hip)
-    // ---- track carry (svo_set_track_carry / svo_carry_merge, carry.hip; off and nothing allocated until it is first enabled)
-    bool carry_on = false;
-    double carry_min_distance = 3.0;
-    int carry_max_age = 0;
-    uint8_t *carry_buf = nullptr;                        // ONE block, cut into what follows
-    long long *kp_id = nullptr; int *kp_age = nullptr;   // beside kp_xy / kp_resp: n_img frame slots x max_keypoints
-    long long *trk_id = nullptr; int *trk_age = nullptr; // id / age-at-t1 of a pair's tracks, in the order of cmp[]: max_batch x max_keypoints
-    int *carry_sorted = nullptr; uint8_t *carry_flag = nullptr, *carry_dflag = nullptr;       // kernel scratch, max_batch x max_keypoints
-    float2 *carry_dxy = nullptr; float *carry_dresp = nullptr;
-    long long *carry_next = nullptr;                     // the online chain's id counter, on the device
-    bool carry_ids[2] = {false, false};                  // the list in online ring slot 0 / 1 has ids
-    bool carry_restart = true;                           // the online chain's ids start at 0 with its next carry launch
-    int carry_last_pairs = 0;                            // pairs of the most recent fused launch that ran with carry (0: it was off)
-    DevScratch carry_stage;                              // svo_carry_merge: the caller's lists, the outputs and the scratch
-    // ---- sliding window (svo_window_update, window.hip): nothing allocated until the stage call is first used
-    DevScratch window_stage;                             // the caller's tables and tracks (HOST calls) and the kernel's prefix scratch
-    DevScratch window_ba_stage;                          // svo_window_ba's own: a growing stage call never frees what the other one's launch still reads
-    // svo_set_window_ba: the online chain's table (two buffers, swapped per step) and the optimiser's scratch, ONE growable block
-    int win_frames = 0;                                  // W; 0: off
-    int win_rounds = 4, win_iters = 5, win_min_obs = 10; double win_sigma = 1.0;
-    DevScratch win_block;
-    int win_cur = 0;                                     // which of the two tables is the chain's
-    bool win_clear = true;                               // T1: the next step starts from a cleared table
-    bool win_step = false;                               // set by pipeline_add_frame around its run_pairs: run_back runs the two kernels
-    bool win_last = false; int win_last_frames = 0;      // the last online step ran them (with this W): what the read-backs return
-    // ---- keyframe-relative pose (svo_set_keyframe / svo_keyframe_join, keyframe.hip; off and nothing allocated until it is first enabled)
-    bool kf_on = false;
-    int kf_min_tracks = 60, kf_max_gap = 0;
-    uint8_t *kf_buf = nullptr;                           // ONE block: the chain's state, its table, the joined lists, the result
-    bool kf_clear = true;                                // K1: the next step starts without a keyframe
-    bool kf_step = false;                                // set by pipeline_add_frame around its run_pairs: run_back runs the keyframe stage
-    bool kf_last = false;                                // the last online step ran it: what the read-backs return
-    DevScratch kf_stage;                                 // svo_keyframe_join: the caller's lists and the outputs (HOST calls)
+    // ---- the online chain's stages (their lifecycle: chain_event, pipeline.hip)
+    CarryStage carry;
+    WindowStage win;
+    KeyframeStage kf;
+    LastLaunch last;
     // ---- timing
     // stage marks are HIP events recorded on the context's stream; they are resolved (elapsed
     // times averaged per stage over all steps since the last query) in svo_get_timing
@@ -277,6 +243,14 @@ struct svo_ctx {
     } while (0)
 
 namespace svo {
+// the schedule limits of every robust optimiser (refine.hip, ba.hip, window.hip), setters and stage calls alike
+inline int check_optimiser_params(svo_ctx *ctx, int rounds, int iters, double sigma_px)
+{
+    SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
+    SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
+    SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
+    return SVO_OK;
+}
 // svo_abi.hip: the context's device memory, events and streams (DevArena)
 int dev_alloc_raw(svo_ctx *ctx, void **out, size_t bytes);
 template <class T> inline int dev_alloc(svo_ctx *ctx, T **out, size_t bytes) { return dev_alloc_raw(ctx, (void **)out, bytes); }
@@ -356,6 +330,9 @@ int stage_chain_relative(svo_ctx *ctx, const double *T, const int32_t *ok, int n
 // svo_abi.hip, and run before anything is copied or launched -- and their frames are DEVICE frames of the context's size,
 // already ordered before the context's stream, on the device svo_abi.hip has made current.
 int pipeline_add_frame(svo_ctx *ctx, const uint8_t *left, const uint8_t *right, int pitch, svo_step_result *res);
+// what can break the online chain, and the one statement of which stage starts fresh after it (the rule table is its comment)
+enum ChainEvent { kChainNew, kChainPoseSet, kChainCarrySet, kChainWindowSet, kChainKeyframeSet };
+void chain_event(svo_ctx *ctx, ChainEvent ev);
 int pipeline_track_batch(svo_ctx *ctx, const uint8_t *left_frames, const uint8_t *right_frames, int pitch, int64_t frame_stride,
                          int n_frames, const double *pose0, svo_step_result *results, int results_mem, int carry_first);
 // window.hip: window_update_kernel on a caller's tables

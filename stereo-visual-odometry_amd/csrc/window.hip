@@ -669,23 +669,23 @@ static WindowCut window_cut(int frames, int kcap)
 int window_alloc(svo_ctx *ctx, int frames)
 {
     SVO_HIP(hipSetDevice(ctx->device));
-    if (dev_reserve(ctx, &ctx->win_block, window_cut(frames, ctx->cfg.max_keypoints).end) != SVO_OK) return SVO_ERR_HIP;
+    if (dev_reserve(ctx, &ctx->win.block, window_cut(frames, ctx->cfg.max_keypoints).end) != SVO_OK) return SVO_ERR_HIP;
     return SVO_OK;
 }
 
 // after launch_finalize_chain of an online step, on its stream: the update on the pair's tracks, then the optimiser on the new table
 int window_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
 {
-    const int W = ctx->win_frames, K = ctx->cfg.max_keypoints;
+    const int W = ctx->win.frames, K = ctx->cfg.max_keypoints;
     const WindowCut c = window_cut(W, K);
-    uint8_t *s = ctx->win_block.base;
-    const int in = ctx->win_cur, out = in ^ 1;
+    uint8_t *s = ctx->win.block.base;
+    const int in = ctx->win.cur, out = in ^ 1;
     WindowUpdateArgs u{};
     u.frames = W; u.cap = (W - 1) * K;
     u.in = window_table_at(s, c.tab[in]); u.out = window_table_at(s, c.tab[out]);
     u.t1_left = ctx->cmp[0]; u.t1_right = ctx->cmp[1]; u.t2_right = ctx->cmp[2]; u.t2_left = ctx->cmp[3];
-    u.ids = ctx->trk_id; u.tri = ctx->X3; u.n_trk = K; u.n_trk_dev = ctx->m_out;
-    u.ok = &ctx->d_results[0].ok; u.clear_in = ctx->win_clear ? 1 : 0;
+    u.ids = ctx->carry.trk_id; u.tri = ctx->X3; u.n_trk = K; u.n_trk_dev = ctx->m_out;
+    u.ok = &ctx->d_results[0].ok; u.clear_in = ctx->win.clear ? 1 : 0;
     u.pose_a_by_value = 1;
     memcpy(u.pose_a_value, pose_from_host(pose0_host).m, sizeof(u.pose_a_value));
     u.pose_b = ctx->d_results[0].pose;
@@ -695,21 +695,21 @@ int window_fused_step(svo_ctx *ctx, const double *pose0_host, hipStream_t st)
     WindowBaArgs b{};
     b.tab = u.out; b.cap = u.cap;
     b.cam = stereo_cam(ctx->cfg.P1, ctx->cfg.P2);
-    b.rounds = ctx->win_rounds; b.iters = ctx->win_iters; b.min_obs = ctx->win_min_obs; b.sigma = ctx->win_sigma;
+    b.rounds = ctx->win.rounds; b.iters = ctx->win.iters; b.min_obs = ctx->win.min_obs; b.sigma = ctx->win.sigma;
     b.Xa = (double *)(s + c.Xa); b.Xb = (double *)(s + c.Xb); b.sys = (double *)(s + c.sys); b.act = (uint32_t *)(s + c.act);
     b.res = (svo_window_result *)(s + c.res);
     b.record_pose = ctx->d_results[0].pose;
     launch_window_ba(b, st);
     timing_mark(ctx, "win_ba");
-    ctx->win_cur = out; ctx->win_clear = false; ctx->win_last = true;
+    ctx->win.cur = out; ctx->win.clear = false;
     return SVO_OK;
 }
 
 // read-backs of the online chain's table and of the last step's outcome (HOST)
 int window_read(svo_ctx *ctx, const svo_window_table *out, int cap)
 {
-    const WindowCut c = window_cut(ctx->win_last_frames, ctx->cfg.max_keypoints);
-    const WindowTable t = window_table_at(ctx->win_block.base, c.tab[ctx->win_cur]);
+    const WindowCut c = window_cut(ctx->last.window_frames, ctx->cfg.max_keypoints);
+    const WindowTable t = window_table_at(ctx->win.block.base, c.tab[ctx->win.cur]);
     SVO_TRY(window_table_out(ctx, *out, t, 0, kTabCounts, SVO_MEM_HOST));
     SVO_TRY(io_done(ctx, SVO_MEM_HOST));
     const int m = out->counts[1];
@@ -721,8 +721,8 @@ int window_read(svo_ctx *ctx, const svo_window_table *out, int cap)
 
 int window_read_result(svo_ctx *ctx, svo_window_result *res)
 {
-    const WindowCut c = window_cut(ctx->win_last_frames, ctx->cfg.max_keypoints);
-    SVO_TRY(from_device(ctx, res, (const svo_window_result *)(ctx->win_block.base + c.res), (size_t)1, SVO_MEM_HOST));
+    const WindowCut c = window_cut(ctx->last.window_frames, ctx->cfg.max_keypoints);
+    SVO_TRY(from_device(ctx, res, (const svo_window_result *)(ctx->win.block.base + c.res), (size_t)1, SVO_MEM_HOST));
     return io_done(ctx, SVO_MEM_HOST);
 }
 
@@ -757,8 +757,8 @@ int stage_window_update(svo_ctx *ctx, int frames, const svo_window_table *in, co
                  i_t2r = cut.add(sizeof(float2) * ht), i_ids = cut.add(sizeof(long long) * ht), i_tri = cut.add(sizeof(float) * 3 * ht),
                  i_pa = cut.add(host ? sizeof(double) * 16 : 0), i_pb = cut.add(host ? sizeof(double) * 16 : 0);
     SVO_HIP(hipSetDevice(ctx->device));
-    if (dev_reserve(ctx, &ctx->window_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
-    uint8_t *s = ctx->window_stage.base;
+    if (dev_reserve(ctx, &ctx->win.update_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+    uint8_t *s = ctx->win.update_stage.base;
     WindowUpdateArgs a{};
     a.frames = frames; a.cap = cap; a.n_trk = n_trk;
     a.pre_rows = (int *)(s + s_rows); a.pre_new = (int *)(s + s_new);
@@ -791,9 +791,7 @@ int stage_window_ba(svo_ctx *ctx, const svo_window_table *tab, int cap, const do
     SVO_ARG(cap >= 1 && cap <= (1 << 21), "cap outside 1..2^21");
     SVO_ARG(tab && tab->counts && tab->poses && tab->ids && tab->X && tab->seen && tab->active && tab->obs_left && tab->obs_right, "null table");
     SVO_ARG(P1 && P2 && res, "null P1 / P2 / result");
-    SVO_ARG(rounds >= 1 && rounds <= 16, "rounds outside 1..16");
-    SVO_ARG(iters >= 1 && iters <= 100, "iters outside 1..100");
-    SVO_ARG(std::isfinite(sigma_px) && sigma_px > 0.0, "sigma_px must be finite and > 0");
+    SVO_TRY(check_optimiser_params(ctx, rounds, iters, sigma_px));
     SVO_ARG(min_obs >= 1, "min_obs < 1");
     SVO_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE, "mem must be SVO_MEM_HOST or SVO_MEM_DEVICE");
     const bool host = mem == SVO_MEM_HOST;
@@ -811,8 +809,8 @@ int stage_window_ba(svo_ctx *ctx, const svo_window_table *tab, int cap, const do
     size_t at[8];
     window_table_cut(cut, hm, host ? read : 0u, at);
     SVO_HIP(hipSetDevice(ctx->device));
-    if (dev_reserve(ctx, &ctx->window_ba_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
-    uint8_t *s = ctx->window_ba_stage.base;
+    if (dev_reserve(ctx, &ctx->win.ba_stage, cut.total()) != SVO_OK) return SVO_ERR_HIP;
+    uint8_t *s = ctx->win.ba_stage.base;
     WindowBaArgs a{};
     a.cap = cap;
     a.cam = stereo_cam(P1, P2);

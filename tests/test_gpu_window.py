@@ -334,6 +334,60 @@ def test_fused_off_on_off_and_a_failed_step(pkg, seq9):
         ref.close()
 
 
+def _step_from_cleared_table(ctx, oracle, P1, P2, frame):
+    """One step; the table read after it must be the twin's update of an EMPTY table by the step's tracks.  Returns the pose
+    the step started from and the tracks' ids."""
+    pose_a = ctx.get_pose().copy()
+    rc, rec = ctx.add_frame(*frame)
+    assert rc == 0 and rec["ok"] == 1
+    t1l, t1r, t2r, t2l = ctx.last_tracks()[:4]
+    ids, _ = ctx.last_track_ids()
+    tri = oracle.triangulate(P1, P2, t1l, t1r)
+    want = WR.update(WR.empty(), 3, t1l, t1r, t2l, t2r, ids, tri, pose_a, pose_a @ rec["T_rel_inv"].reshape(4, 4))
+    got = ctx.window()
+    assert want["n"] == 2 and want["m"] > 100                                        # (a table that was kept would hold 3 frames)
+    assert (got["n"], got["m"]) == (want["n"], want["m"])
+    for k in ("ids", "seen", "obs_left", "obs_right"):
+        assert got[k].tobytes() == want[k][:want["m"]].tobytes(), k
+    return pose_a, ids
+
+
+def test_every_restart_clears_the_table(pkg, oracle, seq9):
+    """T1, the twin of the keyframe's K1 test: svo_set_pose, svo_set_track_carry, svo_set_window_ba and svo_reset each make the
+    next step start from a cleared table; across the first two the track ids run on from the chain's counter."""
+    seq, frames = seq9
+    P1, P2 = (np.asarray(p, np.float64).reshape(3, 4) for p in seq.proj())
+    ctx = _ctx(pkg, seq, 3)
+    try:
+        hi = -1                                                                      # the largest id the chain has given out
+        for fr in frames[:4]:
+            ctx.add_frame(*fr)
+            hi = max(hi, int(ctx.frame_track_ids()[0].max()))
+        assert ctx.window()["n"] == 3
+        T = np.eye(4)
+        T[:3, 3] = [1.0, 2.0, 3.0]
+        breaks = ((4, lambda: ctx.set_pose(T)), (5, lambda: ctx.set_track_carry(True, 3.0, 0)), (6, lambda: ctx.set_window_ba(3, 4, 2, 1.0, 10)))
+        for f, restart in breaks:
+            listed = ctx.frame_track_ids()[0]                                         # every id of the list the next pair tracks from
+            restart()
+            pose_a, ids = _step_from_cleared_table(ctx, oracle, P1, P2, frames[f])
+            if f == 4:
+                assert pose_a.tobytes() == T.tobytes()
+            if f in (4, 5):
+                assert (np.diff(ids) > 0).all() and np.isin(ids, listed).all()       # the tracks kept their ids, in ascending order
+                new = np.setdiff1d(ctx.frame_track_ids()[0], listed)
+                assert len(new) > 0 and new.min() > hi                               # and the counter went on: no id is given twice
+            hi = max(hi, int(ctx.frame_track_ids()[0].max()))
+        ctx.reset()
+        ctx.add_frame(*frames[0])
+        with pytest.raises(pkg.SvoError):
+            ctx.window()
+        pose_a, _ = _step_from_cleared_table(ctx, oracle, P1, P2, frames[1])
+        assert pose_a.tobytes() == np.eye(4).tobytes()
+    finally:
+        ctx.close()
+
+
 def test_fused_switch_rules(pkg, seq9):
     seq, frames = seq9
     c = pkg.Context(416, 128, device=0, P1=seq.proj()[0], P2=seq.proj()[1])
