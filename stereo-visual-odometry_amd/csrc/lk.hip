@@ -15,11 +15,11 @@
 //   * tiles live in LDS as ROW-PAIR COLUMN WORDS (pixel[r][c] | pixel[r+1][c] << 16), formed once while
 //     staging (4 v_perm per source dword pair): exactly the operand of the bilinear v_dot2_i32_i16, so
 //     neither the patch build nor an iteration spends an instruction on byte alignment or unpacking;
-//   * per level, per slot: the 24x28 I tile (requested one level ahead); the lane reads its 3 row pairs x
+//   * per level, per slot: the 24x27 I tile (requested one level ahead); the lane reads its 3 row pairs x
 //     10 columns, forms the Scharr derivatives of the 2x8 positions it interpolates from ON THE FLY with
 //     packed 16-bit math (the reference path materialises a full int16x2 derivative image per level
 //     per call), interpolates I, Ix, Iy with v_dot2_i32_i16 and keeps the patch as 12 packed VGPRs;
-//   * per iteration, per active slot: eight conflict-free dword reads from a column-major 27x28 J tile
+//   * per iteration, per active slot: eight conflict-free dword reads from a column-major 27x27 J tile
 //     (re-staged only when the window drifts out of it; requested beside the patch arithmetic), a
 //     four-tap bilinear sample is two v_dot2_i32_i16 (signed 16-bit weight pairs; the words hold
 //     pixel << 7, so the sample is the high half of its sum), then v_dot2 mismatch sums;
@@ -35,10 +35,11 @@
 //     slots at work is 207 vector instructions: 87 of control, reduction and solve + 30 per slot (3 v_readlane, 1 address
 //     add, 14 + 8 v_dot2, 3 v_perm, 1 shift) -- 221 = 101 + 4 x 30 with bool flags and zero fills; the loop body has
 //     no branch besides the per-slot skips, the re-stage test and the near-epsilon f64 test.
-// The column-word J tiles cost 4x the LDS of byte tiles (13 KB per wave): three waves per SIMD, 168 VGPRs.
+// The column-word J tiles cost 4x the LDS of byte tiles: 12 528 B per wave, ten of the 1280-byte granules LDS is handed
+// out in, so twelve waves fit into a CU's 160 KB: three waves per SIMD, 168 VGPRs.
 // A wave's life varies 2x with the iteration counts of its points, so a throughput launch's workgroup is
 // ONE wave: it gives its LDS back the moment it ends and the dispatcher starts the next one (four-wave
-// workgroups hold 52 KB until their slowest wave has ended).
+// workgroups hold 50 KB until their slowest wave has ended).
 //
 // Exactness: all pixel arithmetic is upstream's fixed point (14-bit weights, 5 fractional bits);
 // the five sums A11,A12,A22,b1,b2 are accumulated as exact integers (per-lane int32 partials,
@@ -59,25 +60,33 @@
 
 namespace svo {
 
-// I tile: 24 rows x 28 bytes of the level, staged as ROW-PAIR COLUMN WORDS: Q[p][c] = byte c of tile
-// row p | byte c of row p + 1 << 16 (23 pairs x 28 columns, one dword each).  The patch build wants
+// I tile: 24 rows x 27 bytes of the level, staged as ROW-PAIR COLUMN WORDS: Q[p][c] = byte c of tile
+// row p | byte c of row p + 1 << 16 (23 pairs x 27 columns, one dword each).  The patch build wants
 // exactly these words for the row pairs (r, r+1), (r+1, r+2), (r+2, r+3) of every lane's 10 columns;
 // formed while staging (4 v_perm per staged dword pair, 12 per lane) they replace the 30 v_perm +
 // 12 v_alignbyte every lane spent on its own copy, and the lane's reads become plain dword reads.
-// The tile starts at the 4-byte aligned column at or left of ipx - 1 (offI columns of slack).
-// J tile: the same row-pair column words, 27 pairs x 28 columns around the window (3 spare on every side:
-// a window drifts that far at one level only rarely, and then the tile is staged again).
+// The tile starts at the 4-byte aligned column at or left of ipx - 1 (offI <= 3 columns of slack): the last column a
+// lane reads is 3 + 7 * 2 + 9 = 26.  The seven source dwords of a row pair carry 28 columns; the last one is not stored
+// (in a 27-column tile it would be the next slot's column 0 and, behind slot 3, the word after the wave's LDS region).
+// J tile: the same row-pair column words, 27 pairs x 27 columns around the window: 3 spare rows above and below, 3 spare
+// columns on the left and 2 on the right (a window drifts that far at one level only rarely, and then the tile is
+// staged again around it; a re-stage changes no result).  The 28th column would make a wave's tiles 12 992 B, eleven
+// granules: eleven waves per CU instead of twelve.
 // Both are stored COLUMN-MAJOR with 29 words per column: lane (row, seg) reads column cx + 7 seg + k, pair cy + row
 // (I: its row pairs row, row+1, row+2 of column offI + 7 seg + j), so the banks of a 32-lane half are
 // 7 * 29 * seg + row = 11 seg + row (mod 32) -- conflict-free; the row-major order is 2-way conflicted for every
 // stride below 53 (half of all LDS-array cycles of the patch build; SQ_LDS_BANK_CONFLICT was 30 % of
 // SQ_LDS_IDX_ACTIVE).  Slot s's J tile takes over slot s's I tile.
 struct ExactTile {
-    static constexpr int kColDw = 29, kTileDw = 28 * kColDw;       // 812 dwords per slot
+    static constexpr int kColDw = 29, kCols = 27, kTileDw = kCols * kColDw;      // 783 dwords per slot
+    static constexpr int kStoreCols = kCols;                       // nothing spills: slot 3's tile ends the wave's region
     static constexpr int kQPairs = 23, kJPairs = 27, kJMargin = 3;
     static constexpr bool kAlignedI = true;
 };
-constexpr int kLdsDwPerWave = kSlots * ExactTile::kTileDw;         // 3248 dwords
+constexpr int kLdsDwPerWave = kSlots * ExactTile::kTileDw;         // 3132 dwords
+// the I tile's last column read: offI <= 3, + 7 * 2 (segment) + 9; the J tile's: j_span_x + kWindowCols - 1
+static_assert(3 + 14 + 9 < ExactTile::kCols && j_span_x<ExactTile>() == 5 && ExactTile::kJMargin <= j_span_x<ExactTile>(), "tile columns");
+static_assert(kLdsDwPerWave * 4 <= 10 * 1280, "ten LDS granules per wave: twelve single-wave workgroups per CU");
 
 // Diagnostic build (-DSVO_LK_STAMP=k, tools/gpu/lk_stamps.sh): every wave adds the s_memtime cycles it spends in
 // section k of lk_call4 (between stamp points k and k + 1; k = 8: the whole call) to a counter read back with
@@ -324,17 +333,16 @@ __device__ __forceinline__ void lk_call4(const PyrGeom &g, const uint8_t *slotI,
 // Waves per workgroup (4, 2 or 1; -DSVO_LK_WAVES_PER_WG=k for A/B builds).  The waves of a workgroup share
 // nothing but the LDS allocation, and a workgroup gives its LDS back only when its SLOWEST wave has ended:
 // with four waves the slots of the finished ones stay empty until then, because no other workgroup fits
-// beside 3 x 52 KB.  With single-wave workgroups the hardware dispatcher is the
+// beside 3 x 50 KB.  With single-wave workgroups the hardware dispatcher is the
 // work queue: a wave that ends frees its LDS at once and the next one starts.
 #ifndef SVO_LK_WAVES_PER_WG
 #define SVO_LK_WAVES_PER_WG 1
 #endif
 constexpr int kLkWavesPerWg = SVO_LK_WAVES_PER_WG;
 static_assert(kLkWavesPerWg == 4 || kLkWavesPerWg == 2 || kLkWavesPerWg == 1, "lk_kernel: 4, 2 or 1 waves per workgroup");
-// The latency shape (launches of fewer than 4 items) stays at four: LDS is handed out in 1280-byte granules
-// (tools/gpu/lds_granule_probe.hip), so a lone wave's 12 992 B take 14 080 and only ELEVEN fit into a CU's
-// 160 KB where three four-wave workgroups hold twelve.  A throughput launch gains more from the early hand-back
-// than it loses with the twelfth wave; a launch whose waves all start at once only loses (stream k = 2: -3 %).
+// The latency shape (launches of fewer than 4 items) stays at four: measured when a lone wave's tiles took eleven LDS
+// granules (28-column tiles: eleven waves per CU where three four-wave workgroups held twelve; stream k = 2: -3 % as
+// single waves).  Its waves all start at once, so it has nothing to gain from the early hand-back.
 constexpr int kLkSpreadWavesPerWg = 4;
 
 // Grid and item mapping: lk_track_item (lk_common.h); a wave's LDS region is its four slot tiles.

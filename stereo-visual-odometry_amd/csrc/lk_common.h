@@ -24,9 +24,16 @@ constexpr float kHalfWin = 10.f;                          // (winSize - 1) * 0.5
 constexpr float kFltScale = 1.f / (1 << 20);              // FLT_SCALE of the five sums
 constexpr int kNoJTile = -(1 << 20);                      // tx0 of a slot without a staged J tile
 
-// A tile geometry (the template parameter T below) names: kColDw (words per tile column), kTileDw (words per slot
-// tile), kQPairs / kJPairs (row pairs of the I / J tile), kJMargin (spare J rows and columns around the window) and
-// kAlignedI (the I tile starts at a 4-byte aligned image column).
+// A tile geometry (the template parameter T below) names: kColDw (words per tile column), kCols (columns of a slot
+// tile), kTileDw = kCols * kColDw (words per slot tile), kStoreCols (how many of the 28 staged columns a staging pass at
+// a level's start stores: kCols, or more where the geometry lets the last source dword spill behind the tile),
+// kQPairs / kJPairs (row pairs of the I / J tile), kJMargin (spare J rows, and columns on the left, around the window)
+// and kAlignedI (the I tile starts at a 4-byte aligned image column).
+constexpr int kStagedCols = 28;                           // 7 source dwords per row pair
+// columns a window spans: lane segment 2 reads its eight column words from cx + 14
+constexpr int kWindowCols = 2 * 7 + 8;
+// largest cx = inx - tx0 at which the window's columns are all inside the tile: the x half of the re-stage test
+template <class T> constexpr int j_span_x() { return T::kCols - kWindowCols; }
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -210,11 +217,16 @@ __device__ __forceinline__ void tile_store_i(uint32_t *tile, const uint32_t (&r)
             const uint32_t top = r[t][0], bot = r[t][1];
             uint32_t *d = tile + q.dst[t];
 #pragma unroll
-            for (int c = 0; c < 4; c++) d[c * T::kColDw] = perm_b32(bot, top, 0x0c040c00u + 0x00010001u * c);
+            for (int c = 0; c < 4; c++) {
+                // a column past the tile would land in the next slot's first column, or behind the wave's LDS region
+                if (24 + c >= T::kStoreCols && q.dc4[t] == 24) continue;
+                d[c * T::kColDw] = perm_b32(bot, top, 0x0c040c00u + 0x00010001u * c);
+            }
         }
     }
 }
-// ... into a J tile.  MASKED (tiles narrower than the 28 staged columns): columns 26, 27 are left out.
+// ... into a J tile.  The columns from kStoreCols on are left out; MASKED (a re-stage of one slot beside live
+// neighbours): the columns from kCols on.
 template <class T, bool MASKED>
 __device__ __forceinline__ void tile_store_j(uint32_t *tile, const uint32_t (&r)[3][2], const StageLane &q, int lane)
 {
@@ -228,7 +240,7 @@ __device__ __forceinline__ void tile_store_j(uint32_t *tile, const uint32_t (&r)
             const u16x2 one = {1, 1};
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                if (MASKED && c >= 2 && q.dc4[t] == 24) continue;
+                if (24 + c >= (MASKED ? T::kCols : T::kStoreCols) && q.dc4[t] == 24) continue;
                 d[c * T::kColDw] = as_u32(as_u16x2(perm_b32(bot, top, 0x040c000cu + 0x01000100u * c)) >> one);
             }
         }
@@ -383,7 +395,8 @@ __device__ __forceinline__ lanemask level_solve_setup(float A11, float A12, floa
 }
 
 // An iteration's start: the J window position and weights, the status rule for a window that left the level, and the
-// re-stage test: the tile holds kJMargin spare rows and columns on every side of the window it was staged for; a
+// re-stage test: the tile holds kJMargin spare rows above and below and kJMargin spare columns left of the window it
+// was staged for, and j_span_x - kJMargin columns right of it (one fewer than on the left in a 27-column tile); a
 // window that drifted further gets a new tile around itself.
 // A slot that does not iterate computes all of this from a stale window position (iter_update); nothing of it is used:
 // status and restage carry "it_on &", the tile origin moves under restage only, and the weights and joff of a slot are
@@ -405,7 +418,7 @@ __device__ __forceinline__ LkIter iter_begin(float qx, float qy, int w, int h, i
     it_on &= ~oob;
     const PackedWeights wj = bilinear_weights(qx - (float)inx, qy - (float)iny);
     it.Wa = wj.Wa; it.Wb = wj.Wb;
-    it.restage = it_on & (mask_ugt((unsigned)(inx - tx0), (unsigned)(2 * T::kJMargin)) |
+    it.restage = it_on & (mask_ugt((unsigned)(inx - tx0), (unsigned)j_span_x<T>()) |
                           mask_ugt((unsigned)(iny - ty0), (unsigned)(2 * T::kJMargin)));
     // a re-staged tile starts kJMargin before the window: cx = cy = kJMargin then fall out of the new origin
     tx0 = select(inx - T::kJMargin, tx0, it.restage); ty0 = select(iny - T::kJMargin, ty0, it.restage);

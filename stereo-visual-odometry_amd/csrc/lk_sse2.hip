@@ -59,7 +59,8 @@ constexpr int kQPairs2 = 23, kJPairs2 = kWin + 2 * kJMargin2;                   
 constexpr int kTileDw2 = 26 * kCS2, kTileSpill = 2 * kCS2;                         // 676, 52
 constexpr int kTilesDw = kSlots * kTileDw2;                                        // 2704
 struct ChainTile {
-    static constexpr int kColDw = kCS2, kTileDw = kTileDw2;
+    static constexpr int kColDw = kCS2, kCols = 26, kTileDw = kTileDw2;
+    static constexpr int kStoreCols = kStagedCols;     // a level's staging spills two columns behind the tile (above)
     static constexpr int kQPairs = kQPairs2, kJPairs = kJPairs2, kJMargin = kJMargin2;
     static constexpr bool kAlignedI = false;       // fetched from image column ipx - 1, like the J tiles: the patch needs exactly 24 columns from there
 };

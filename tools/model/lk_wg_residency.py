@@ -10,9 +10,11 @@ of lk_wave_model.py), groups W consecutive waves into a workgroup as the kernel 
   * the mean and the tail of the wave cost,
   * the mean workgroup lifetime (slowest of its W waves) against the mean wave,
   * the in-order list-scheduling makespan of 32 items (what one XCD gets of a 256-pair launch) on the XCD's
-    96 * 4 / W workgroup slots (32 CUs x 12 waves; for W = 1 also with the 11 per CU that the LDS granule leaves)
-    against the ideal (all 12 wave slots busy to the end), and the mean number of waves per SIMD that are still running
-    while their workgroup is resident.
+    96 * 4 / W workgroup slots (32 CUs x 12 waves; for W = 1 also with the 11 per CU that the LDS granule left the
+    28-column tiles) against the ideal (all 12 wave slots busy to the end), and the mean number of waves per SIMD that
+    are still running while their workgroup is resident,
+
+and, first, the LDS granule arithmetic of a workgroup's tiles at 28 and at 27 columns a slot tile.
 
 usage: lk_wg_residency.py [pairs=2]"""
 import heapq
@@ -29,6 +31,16 @@ LPF, LPS, ITF, ITS = 350, 208, 92, 32         # lk_wave_model.py "exact": per le
 WAVE_SLOTS_PER_XCD = 32 * 12                  # 32 CUs x 4 SIMDs x 3 waves
 ITEMS_PER_XCD = 32                            # 256 pairs dealt one per XCD in groups of 8
 WAVES_PER_ITEM = 768                          # launch_lk: 3072 points per pass
+LDS_PER_CU, LDS_GRANULE = 160 * 1024, 1280    # tools/gpu/lds_granule_probe.hip: 12 800 B -> 12 workgroups per CU, 12 801 B -> 11
+COL_DW, SLOTS = 29, 4                         # csrc/lk.hip ExactTile: words per tile column (bank-conflict freedom), slot tiles per wave
+
+
+def lds_fit(cols, W):
+    """(bytes declared, bytes taken, workgroups per CU, waves per CU) of a W-wave workgroup with `cols`-column slot tiles"""
+    declared = W * SLOTS * cols * COL_DW * 4
+    taken = -(-declared // LDS_GRANULE) * LDS_GRANULE
+    wgs = LDS_PER_CU // taken
+    return declared, taken, wgs, min(12, wgs * W)
 
 
 def wave_costs(its, livec):
@@ -80,10 +92,16 @@ def main():
     allw = np.concatenate(items)
     print(f"waves {allw.size} ({npairs} pairs): cost mean {allw.mean() / 1e3:.1f} k instructions, p99 {np.percentile(allw, 99) / 1e3:.1f} k, "
           f"max {allw.max() / 1e3:.1f} k")
+    for cols in (28, 27):
+        for W in (4, 2, 1):
+            declared, taken, wgs, waves = lds_fit(cols, W)
+            print(f"{cols}-column tiles, W = {W}: {declared} B declared = {taken // LDS_GRANULE} granules = {taken} B; {wgs} workgroups = "
+                  f"{waves} waves per CU ({waves / 4:.2f} per SIMD)")
     work = sum(items[i % npairs].sum() for i in range(ITEMS_PER_XCD))
     ideal = work / WAVE_SLOTS_PER_XCD
-    # (W, workgroup slots of an XCD): LDS comes in 1280-byte granules, so a lone wave's 12 992 B take 14 080 and only 11
-    # single-wave workgroups fit into a CU's 160 KB (tools/gpu/lds_granule_probe.hip); 3 x 4 and 6 x 2 waves do fit
+    # (W, workgroup slots of an XCD): LDS comes in 1280-byte granules.  A lone wave's 27-column tiles, 12 528 B, take ten
+    # granules and twelve single-wave workgroups fit into a CU's 160 KB; at 28 columns (12 992 B, eleven granules) only
+    # eleven did -- the last line -- while 3 x 4 and 6 x 2 waves fit at either width
     for W, slots in ((4, 96), (2, 192), (1, 384), (1, 32 * 11)):
         wgs = [item_workgroups(c, W) for c in items]
         life = np.concatenate(wgs)
